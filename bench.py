@@ -3,6 +3,13 @@
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch-per-gpu B] [--imax I]
     torchrun --nproc-per-node N bench.py --gpus N ...      (one process per GPU, RCCL)
     python bench.py --config C1|C2|C3|C5                   (BASELINE.json's other configs)
+    python bench.py --full ...                             (plus the roofline and the CPU baseline)
+    python bench.py --dump-outputs DIR ...                 (the last timed step's outputs as DIR/*.npy)
+
+A plain run sets up, warms up, times --steps decode calls and prints the result line (codewords/s, ms_per_step,
+the algorithmic HBM GB/s and the decoded batch's error count); its roofline and cpu_baseline fields are null.
+--full adds the two measurements the headline does not need: HIP events around every launch of the last timed
+step with the roofline priced from them, and the CPU baseline with its comparison against the GPU's outputs.
 
 Default = BASELINE config C4 (the headline metric). The other presets measure the remaining
 configs of BASELINE.json: C1 regular (3,6) N=8000 IB T=16 i_max=10, 1000 codewords (the reference's
@@ -19,7 +26,7 @@ plan in BASELINE.md prescribes). Inputs are generated on the device before the t
 as N grows (weak scaling); codeword ranges are disjoint per rank and no collective runs inside
 the timed region.
 
-Rank 0 prints one JSON line with the whole-job codewords/s, the algorithmic HBM GB/s, the
+Rank 0 prints one JSON line with the whole-job codewords/s, the algorithmic HBM GB/s and, with --full, the
 roofline of the dominant kernel (HIP-event timed per launch in the last step of the timed region — events
 around every launch of every step cost ~1.3 % of a C4 step, round 6; priced at the
 bytes the kernel actually moves: 4-bit messages on the IB fast path, LDS bytes for the fused on-chip
@@ -75,7 +82,18 @@ def parse(argv=None):
                    help="global batch index of rank 0's batch: rank r decodes global batch offset + r, whose channel "
                         "is Philox key 2 at counter (offset + r) * philox_blocks(N, B) (SURVEY H9)")
     p.add_argument("--pmc", default=os.path.join(ROOT, "profiles", "pmc_traffic.json"))
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: HIP events around the launches of the last timed "
+                        "step and the roofline priced from them (unless --no-kernel-events), and the CPU baseline with "
+                        "its comparison against the GPU's outputs (unless --no-cpu-baseline)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps write what the last one computed as DIR/<name>.npy (float32 / float64): "
+                        "decoded.npy, the decoder's [N][k] output for a fixed seeded choice of k of the batch's codewords "
+                        "(all of them when they fit in 48 MiB), decoded_columns.npy, their indices in the batch, and "
+                        "stop_iteration.npy, the iteration the decoder stopped at")
     a = p.parse_args(argv)
+    if a.steps < 1:
+        p.error("--steps must be at least 1")
     presets = {"C1": ("regular", "ib", 10, 1000), "C2": ("regular", "ib", 50, 65536),
                "C3": ("wlan", "minsum", 50, 262144), "C4": ("dvbs2", "ib", 50, 8192), "C5": ("dvbs2", "bp", 100, 8192)}
     if a.config:
@@ -523,8 +541,34 @@ def decoder_path(a, dec, B):
     return {"fused": bool(fused), "small": bool(small), "folded": int(folded), "name": name}
 
 
-def main():
-    a = parse()
+DUMP_BYTES = 48 << 20    # cap on decoded.npy (float32)
+
+
+def dump_columns(n_v: int, B: int) -> np.ndarray:
+    """The codewords of a batch of B that --dump-outputs writes: all of them when [N][B] float32 fits in
+    DUMP_BYTES, else a fixed choice (seed 0, ascending) of as many as fit — a function of (N, B) alone, so
+    two builds run with the same arguments write the same codewords."""
+    k = max(1, min(B, DUMP_BYTES // (4 * n_v)))
+    if k == B:
+        return np.arange(B, dtype=np.int64)
+    return np.sort(np.random.default_rng(0).choice(B, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(path: str, out, stop_it) -> None:
+    """Write the last timed step's results as float32 / float64 .npy files under `path`: what a caller of
+    decode() receives — the [N][B] output (cluster ids for IB, APP LLRs for min-sum / BP), here its
+    dump_columns(), and the stop iteration."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    cols = dump_columns(out.shape[0], out.shape[1])
+    sel = out.index_select(1, torch.from_numpy(cols).to(out.device)).to(torch.float32).cpu().numpy()
+    np.save(os.path.join(path, "decoded.npy"), sel)
+    np.save(os.path.join(path, "decoded_columns.npy"), cols.astype(np.float64))
+    np.save(os.path.join(path, "stop_iteration.npy"), np.asarray(stop_it, dtype=np.float32).reshape(1))
+
+
+def main(argv=None):
+    a = parse(argv)
     import torch
 
     from informationbottleneckdecodingldpc_amd import distributed, engine
@@ -590,6 +634,7 @@ def main():
         timing_read_fn(dec._h, ctypes.byref(cm), ctypes.byref(cn_), ctypes.byref(vm), ctypes.byref(vn_))
         return cm.value, cn_.value, vm.value, vn_.value
 
+    events = a.full and not a.no_kernel_events
     for _ in range(a.warmup):
         run()
     torch.cuda.synchronize(dev)
@@ -599,7 +644,7 @@ def main():
     t0 = time.perf_counter()
     for k in range(a.steps):
         step_k[0] = k
-        if k == a.steps - 1 and not a.no_kernel_events:
+        if k == a.steps - 1 and events:
             timing_on(True)      # HIP events around the launches of the last timed step only
         run()
     torch.cuda.synchronize(dev)
@@ -607,8 +652,12 @@ def main():
         torch.distributed.barrier()
     torch.cuda.synchronize(dev)
     elapsed_local = time.perf_counter() - t0
-    timing_on(False)
-    cn_ms, cn_n, vn_ms, vn_n = timing_read()
+    cn_ms, cn_n, vn_ms, vn_n = 0.0, 0, 0.0, 0
+    if a.full:
+        timing_on(False)
+        cn_ms, cn_n, vn_ms, vn_n = timing_read()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, out, its[a.steps - 1].item())
 
     # errors of the decoded batch (sanity: counted on device, outside the timed region)
     errs = int(engine.count_below(out, g.data_len, 8 if a.kind == "ib" else 0.0).item())
@@ -628,13 +677,15 @@ def main():
     fmt = "u4" if fast else ("u8" if a.kind == "ib" else "f32")
     if a.kind == "ib":
         dtype = fmt
-    roof = roofline(a, g, n_v, B, I, w, ws, fmt, match, fused, cn_avg, vn_avg, cn_ms, vn_ms, cn_n, vn_n, dec,
-                    folded=folded, small=small)
+    roof = None
+    if a.full:
+        roof = roofline(a, g, n_v, B, I, w, ws, fmt, match, fused, cn_avg, vn_avg, cn_ms, vn_ms, cn_n, vn_n, dec,
+                        folded=folded, small=small)
     # HBM bytes the decode moves per codeword at the stored widths (channel in, output out: u8 for IB, fp32 float)
     moved = moved_bytes_per_cw(g.n_e, n_v, I, "fused" if fused else "passes", ws, w, w, w_stage=w, folded=folded)
     cpu = None
     code_name, code_desc = CODES[a.code]
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not early:   # the baseline times fixed iterations
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline and not early:   # the baseline times fixed iterations
         cpu = cpu_baseline(a, g, arrays, I, B, match, ch if a.kind == "ib" else llr, out, code_name)
 
     if rank == 0:
@@ -648,6 +699,7 @@ def main():
             "steps": a.steps,
             "warmup": a.warmup,
             "ms_per_step": round(elapsed / a.steps * 1e3, 3),
+            "full": bool(a.full),
             "higher_is_better": True,
             "scaling": "weak",
             "vs_baseline": None,

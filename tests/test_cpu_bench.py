@@ -163,3 +163,18 @@ def test_bench_arguments(monkeypatch):
     monkeypatch.setattr(sys, "argv", ["bench.py", "--config", "C1", "--ebn0", "2.5"])
     a = bench.parse()
     assert a.no_match and a.ebn0 == 2.5 and a.batch_per_gpu == 1000
+    assert not a.full and a.dump_outputs is None           # a plain run: the headline alone
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2", "--full", "--dump-outputs", "d"])
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, True, "d")
+    with pytest.raises(SystemExit):
+        bench.parse(["--steps", "0"])
+
+
+def test_dump_columns_are_fixed_and_bounded():
+    """--dump-outputs writes every codeword of a small batch and a fixed, sorted choice of a large one's, at
+    most 48 MiB of float32 (the headline batch: 194 of 8192 codewords of 64800 values)."""
+    assert np.array_equal(bench.dump_columns(8000, 64), np.arange(64))
+    c = bench.dump_columns(64800, 8192)
+    assert c.size == 194 and 4 * 64800 * c.size <= 48 << 20
+    assert np.all(np.diff(c) > 0) and c[0] >= 0 and c[-1] < 8192
+    assert np.array_equal(c, bench.dump_columns(64800, 8192))

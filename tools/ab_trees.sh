@@ -20,7 +20,7 @@ for rep in $(seq 1 ${REPS:-2}); do
       tree:*) cmd="python $R/${arm#tree:}/bench.py"; lib="";;
       lib:*)  cmd="python $R/bench.py"; lib=$R/informationbottleneckdecodingldpc_amd/variants/libibldpc_${arm#lib:}.so;;
     esac
-    env IBLDPC_LIB=$lib $ev timeout -k 10 300 $cmd --config $CFG --no-cpu-baseline ${AB_ARGS:-} > $O/${CFG}_${name}_$rep.json 2> $O/${CFG}_${name}_$rep.err
+    env IBLDPC_LIB=$lib $ev timeout -k 10 300 $cmd --config $CFG --full --no-cpu-baseline ${AB_ARGS:-} > $O/${CFG}_${name}_$rep.json 2> $O/${CFG}_${name}_$rep.err
     rc=$?
     v=$(python3 -c "import json,sys; d=json.load(open(sys.argv[1])); r=d['roofline']; print(d['value'], r.get('avg_ms'), r.get('frac'))" $O/${CFG}_${name}_$rep.json 2>/dev/null)
     echo "$CFG $arm rep$rep rc=$rc $v" >> $O/summary.txt

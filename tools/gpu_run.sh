@@ -19,7 +19,7 @@ chk() {
   case $1 in 0) return 0;; 124|134|137|139) echo "crash-like exit $1 in $2, stopping" >> $O/summary.txt;; esac
   echo "$2 failed rc=$1" >> $O/summary.txt; exit $1
 }
-jf() { python3 -c "import json,sys; d=json.load(open(sys.argv[1])); r=d['roofline']; print(d['value'], r.get('avg_ms'), r.get('frac'), d['decoded_bit_errors'], (d.get('cpu_baseline') or {}).get('value'))" $1 2>/dev/null; }
+jf() { python3 -c "import json,sys; d=json.load(open(sys.argv[1])); r=d['roofline'] or {}; print(d['value'], r.get('avg_ms'), r.get('frac'), d['decoded_bit_errors'], (d.get('cpu_baseline') or {}).get('value'))" $1 2>/dev/null; }
 pmc() {  # pmc <outdir-name> <config> <counters...>: one rocprofv3 counter pass over one bench step
   local n=$1 c=$2; shift 2
   (cd /tmp && timeout -s KILL 300 rocprofv3 --pmc "$@" -d $O/$n -o run --output-format csv -- python3 $R/bench.py --config $c --no-cpu-baseline --steps 1 --warmup 0 > $O/$n.json 2> $O/$n.err)
@@ -39,7 +39,7 @@ for s in $STEPS; do
       rc=$?; echo "smoke rc=$rc" >> $O/summary.txt; chk $rc smoke;;
     bench)
       for c in $CONFIGS; do
-        timeout -k 10 600 python $R/bench.py --config $c ${BENCH_ARGS:-} > $O/bench_$c.json 2> $O/bench_$c.err
+        timeout -k 10 600 python $R/bench.py --config $c --full ${BENCH_ARGS:-} > $O/bench_$c.json 2> $O/bench_$c.err
         rc=$?; echo "bench $c rc=$rc $(jf $O/bench_$c.json)" >> $O/summary.txt; chk $rc bench_$c
       done;;
     prof)
@@ -62,14 +62,14 @@ for s in $STEPS; do
       done;;
     bsweep)
       for b in ${BATCHES:-4096 16384}; do
-        timeout -k 10 400 python $R/bench.py --batch-per-gpu $b --steps 3 --no-cpu-baseline > $O/bench_b$b.json 2> $O/bench_b$b.err
+        timeout -k 10 400 python $R/bench.py --batch-per-gpu $b --steps 3 --full --no-cpu-baseline > $O/bench_b$b.json 2> $O/bench_b$b.err
         rc=$?; echo "bench B=$b rc=$rc $(jf $O/bench_b$b.json)" >> $O/summary.txt; chk $rc bsweep
       done;;
     ab)    # A/B of kernel variants, two alternating repetitions
       for rep in 1 2; do
         for v in ${AB_VARIANTS:-base}; do
           LIBV=""; [ $v = base ] || LIBV=$VL/libibldpc_$v.so
-          IBLDPC_LIB=$LIBV timeout -k 10 300 python $R/bench.py --no-cpu-baseline ${AB_ARGS:-} > $O/ab_${v}_$rep.json 2> $O/ab_${v}_$rep.err
+          IBLDPC_LIB=$LIBV timeout -k 10 300 python $R/bench.py --full --no-cpu-baseline ${AB_ARGS:-} > $O/ab_${v}_$rep.json 2> $O/ab_${v}_$rep.err
           rc=$?; echo "ab $v rep$rep rc=$rc $(jf $O/ab_${v}_$rep.json)" >> $O/summary.txt; chk $rc ab_$v
         done
       done;;
