@@ -161,7 +161,8 @@ int ibl_float_create(const ibl_graph* g, int32_t kind, int32_t imax, double llr_
  * sends is clamped to +-llr_max, its APP LLR is +-inf), and every message stays finite.  BP box-pluses raw
  * channel values in the first check pass (later box-plus inputs are clamped to +-llr_max): the fp64 decoder
  * (the reference's formula log((1 + e^(a+b)) / (e^a + e^b)), kernels_min_and_BP.cl:5-9) needs
- * |x| <= ln(DBL_MAX) = 709.78 — beyond it e^a overflows and the reference gives NaN; below it an overflowing
+ * |x| <= 709.089, just under ln(DBL_MAX / 2) = 709.0895657... — beyond that, two same-sign values overflow the
+ * denominator beside an infinite numerator and the reference gives NaN (inf / inf); within it an overflowing
  * numerator or vanishing denominator gives +-inf, clamped to +-llr_max as in the reference — and the fp32
  * decoder (an overflow-free form of the same function) needs finite values.  The float kernels take min /
  * max / median as single instructions that assume non-NaN operands: a NaN input gives unspecified outputs.
@@ -183,6 +184,13 @@ void ibl_float_destroy(ibl_float* h);
 int ibl_float_set_path(ibl_float* h, int32_t path);
 int ibl_float_path_in_use(const ibl_float* h, int32_t* fused);
 /*
+ * Launch geometry of the fused kernel for a batch of B (no reference counterpart; read-only, the values
+ * ibl_float_decode uses): *ngroups = groups of 4 fp32 / 2 fp64 codewords, ceil(B / 4) or ceil(B / 2);
+ * *grid = workgroups launched, min(ngroups, blocks per CU x CUs) — workgroup w decodes groups w, w + grid,
+ * w + 2 grid, ...  Both 0 when decodes do not run the fused kernel.
+ */
+int ibl_float_fused_geometry(const ibl_float* h, int32_t B, int32_t* ngroups, int32_t* grid);
+/*
  * Degree-2 variable fold of the per-pass path (no reference counterpart; outputs are identical with and
  * without it): the check pass that produces a degree-2 variable's input also computes that variable's
  * output message (clamp(ch + m), kernels_min_and_BP.cl:110-118) into the next check pass's inbox, and the
@@ -200,7 +208,7 @@ int ibl_float_set_small_batch(ibl_float* h, int32_t max_b);
 int ibl_float_small_batch(const ibl_float* h, int32_t* max_b);
 /*
  * Channel-LLR precondition check (no reference counterpart).  The staging step of every ibl_float_decode
- * counts the channel LLRs that break ibl_float_decode's precondition — NaN (min-sum); NaN or |x| > 709.78
+ * counts the channel LLRs that break ibl_float_decode's precondition — NaN (min-sum); NaN or |x| > 709.089
  * (BP, fp64 decoder); NaN or +-inf (BP, fp32 decoder) — on the device, without a host sync, into one counter
  * per decoder.  This call synchronises the decoder's DEVICE (every stream: the count covers all decodes of
  * this decoder enqueued since the previous call, whatever their stream; `stream` is unused), stores that

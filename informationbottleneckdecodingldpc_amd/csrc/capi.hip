@@ -1069,6 +1069,14 @@ int ib_fused_setup(ibl_ib* h) {
   return IBL_OK;
 }
 
+// Launch geometry of the fused float kernel for a batch of B: groups of 4 fp32 / 2 fp64 codewords, one per
+// workgroup round (fl_fused's group loop); ibl_float_decode and ibl_float_fused_geometry both take it from here.
+void float_fused_geometry(const ibl_float* h, int B, int32_t* ngroups, int32_t* grid) {
+  const int cwl = h->prec == kF32 ? 4 : 2;
+  *ngroups = (B + cwl - 1) / cwl;
+  *grid = std::min(*ngroups, h->f_grid);
+}
+
 bool ib_fused_in_use(const ibl_ib* h) { return h->fused_ok && h->path != IBL_PATH_PASSES; }
 
 // The fold's device state (second check inbox, per-check records, unfolded variable list) once a batch can reach
@@ -1145,10 +1153,18 @@ int ibl_float_input_check(ibl_float* h, int32_t* violations, void* stream) {
   if (violations) *violations = n;
   if (n > 0)
     return fail(IBL_EINVAL, std::to_string(n) + (h->kind == IBL_BP
-                                                     ? (h->prec == kF64 ? " channel LLR(s) NaN or |x| > 709.78 (BP precondition)"
+                                                     ? (h->prec == kF64 ? " channel LLR(s) NaN or |x| > 709.089 (BP precondition)"
                                                                           : " channel LLR(s) NaN or infinite (BP precondition)")
                                                      : " channel LLR(s) NaN (min-sum precondition)") +
                                 ": those decodes' outputs are unspecified");
+  return IBL_OK;
+}
+
+int ibl_float_fused_geometry(const ibl_float* h, int32_t B, int32_t* ngroups, int32_t* grid) {
+  if (!h || !ngroups || !grid) return fail(IBL_EINVAL, "NULL argument");
+  if (B < 1 || B > h->max_batch) return fail(IBL_EINVAL, "B must lie in [1, max_batch]");
+  *ngroups = *grid = 0;
+  if (h->fused_ok && h->path != IBL_PATH_PASSES) float_fused_geometry(h, B, ngroups, grid);
   return IBL_OK;
 }
 
@@ -1252,7 +1268,7 @@ int ibl_float_decode(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32_t
   const int cwl = h->prec == kF32 ? 4 : 2;
   const int nchunks = (B + 64 * cwl - 1) / (64 * cwl);
   // the staging kernels count precondition violations (float_kernels.hip llr_bad): min-sum NaN; BP NaN and, for
-  // the fp64 decoder, |x| > ln(DBL_MAX), for the fp32 decoder +-inf
+  // the fp64 decoder, |x| > 709.089 (just under ln(DBL_MAX / 2)), for the fp32 decoder +-inf
   const int rule = h->kind == IBL_BP ? (h->prec == kF64 ? 2 : 3) : 1;
   if (early) HIPCHK(hipMemsetAsync(h->flags, 0, sizeof(int32_t) * (size_t)I * kShards, s));
   if (h->fused_ok && h->path != IBL_PATH_PASSES) {
@@ -1262,7 +1278,8 @@ int ibl_float_decode(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32_t
     fa.vn_slot = h->f_vn_slot; fa.out = d_out; fa.unsat = early ? h->flags : nullptr; fa.dL = nullptr;
     fa.llr_max = h->llr_max; fa.n_e = (int32_t)g->n_e; fa.n_v = g->n_v; fa.n_cn_tasks = h->f_ncn;
     fa.n_vn_tasks = h->f_nvn; fa.n_vs = h->f_nvs; fa.ldb = h->ldb; fa.B = B; fa.imax = I; fa.out_dtype = out_dtype;
-    fa.ngroups = (B + cwl - 1) / cwl;
+    int grid = 0;
+    float_fused_geometry(h, B, &fa.ngroups, &grid);
 #if IBL_DIAG
     const char* ftrace = getenv("IBL_TRACE_FUSED");   // diagnostic builds: phase clocks of block 0's first group
     const size_t ntr = (size_t)kFlTraceWords * (2 * I + 4);
@@ -1273,7 +1290,6 @@ int ibl_float_decode(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32_t
 #endif
     const size_t esz = out_dtype == kF32 ? 4 : 8;
     fa.aligned = ((B % cwl) == 0 && ((uintptr_t)d_out % (cwl * esz)) == 0) ? 1 : 0;
-    const int grid = std::min(fa.ngroups, h->f_grid);
     HIPCHK(h->timer.timed(0, s, [&] { return launch_fl_fused(fa, h->kind, h->prec, g->dcm, g->dvm, grid, h->f_lds, s); }));
 #if IBL_DIAG
     if (ftrace) {

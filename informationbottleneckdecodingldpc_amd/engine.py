@@ -196,6 +196,15 @@ class FloatDecoder:
         _lib.check(_lib.load().ibl_float_path_in_use(self._h, ctypes.byref(f)), "ibl_float_path_in_use")
         return bool(f.value)
 
+    def fused_geometry(self, B: int):
+        """``(ngroups, grid)`` the fused kernel decodes a batch of ``B`` with: groups of 4 fp32 / 2 fp64
+        codewords and workgroups launched (workgroup w takes groups w, w + grid, ...); ``(0, 0)`` when the
+        fused kernel is not in use — ``ibl_float_fused_geometry``."""
+        n, g = ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(_lib.load().ibl_float_fused_geometry(self._h, int(B), ctypes.byref(n), ctypes.byref(g)),
+                   "ibl_float_fused_geometry")
+        return int(n.value), int(g.value)
+
     @property
     def small_batch(self) -> int:
         """Largest batch the small-batch float kernels decode (``ibl_float_small_batch``; 0 = off)."""
@@ -216,7 +225,7 @@ class FloatDecoder:
 
     def input_violations(self, raise_on_error: bool = True) -> int:
         """Channel LLRs of this decoder's decodes since the last call (on any stream) that broke the
-        precondition (NaN; BP fp64 also |x| > 709.78, BP fp32 also +-inf): synchronises the device and clears
+        precondition (NaN; BP fp64 also |x| > 709.089, BP fp32 also +-inf): synchronises the device and clears
         the count (``ibl_float_input_check``). Raises :class:`_lib.IBLError` when there were any, unless
         ``raise_on_error`` is False."""
         v = ctypes.c_int32()

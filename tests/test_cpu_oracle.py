@@ -94,6 +94,28 @@ def test_oracle_boxplus_formula():
     assert oracle.boxplus(140.0, 140.0) <= 150.0
 
 
+def test_oracle_boxplus_same_sign_overflow_bound():
+    """Why the fp64 BP precondition is |x| <= 709.089 (float_kernels.hip llr_bad, rule 2): for two same-sign raw
+    channel values the numerator e^(a+b) is inf, and the formula stays defined only while e^a + e^b is finite,
+    i.e. below ln(DBL_MAX / 2) = 709.0895657...; at the bound it gives inf -> clamped to llr_max, above it
+    inf / inf = NaN, which the oracle's sign-based clamp turns into 0 (and the device's fmin/fmax clamp into
+    -llr_max: the two disagree, so such inputs are rejected rather than decoded)."""
+    lm = 150.0
+    assert 709.089 < np.log(np.finfo(np.float64).max / 2) < 709.0896
+    for x in (709.089, -709.089):
+        r = oracle.boxplus(x, x, lm)
+        assert np.isfinite(r) and r == lm
+    assert oracle.boxplus(709.089, -709.089, lm) == -lm
+    with np.errstate(over="ignore", invalid="ignore"):
+        a = b = np.float64(709.5)
+        assert np.isfinite(np.exp(a))                       # e^a alone does not overflow below 709.78 ...
+        raw = np.log((1 + np.exp(a + b)) / (np.exp(a) + np.exp(b)))
+        assert np.isnan(raw)                                # ... but the sum does: inf / inf
+        a = b = np.float64(709.089)
+        assert np.log((1 + np.exp(a + b)) / (np.exp(a) + np.exp(b))) == np.inf
+    assert oracle.boxplus(709.5, 709.5, lm) == 0.0          # the NaN route through sign() = 0
+
+
 def test_llr_tables_decode_on_oracle(wlan_H):
     """The LLR-quantised table generator yields a working decoder (all-zero codeword, 5 dB)."""
     from informationbottleneckdecodingldpc_amd.channel import UniformQuantizer, sigma2_from_ebn0

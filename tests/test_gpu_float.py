@@ -48,13 +48,39 @@ def _llrs(g, B, ebn0, seed, quantised=True):
     return 2 * y / q.sigma_n2
 
 
-def _gpu(eng, g, kind, imax, llr, prec, early, graph_obj=None, path="auto"):
-    G = graph_obj or eng.Graph(g, DEV)
-    dec = eng.FloatDecoder(G, kind, imax, llr.shape[1], precision=prec, path=path)
+def _gpu(eng, g, kind, imax, llr, prec, early, graph_obj=None, path="auto", dec=None):
+    if dec is None:
+        G = graph_obj or eng.Graph(g, DEV)
+        dec = eng.FloatDecoder(G, kind, imax, llr.shape[1], precision=prec, path=path)
     it = torch.zeros(1, dtype=torch.int32, device=DEV)
     out = dec.decode(torch.from_numpy(llr).to(DEV).to(prec), early_stop=early, iters=it)
     torch.cuda.synchronize()
     return out.double().cpu().numpy(), int(it.item())
+
+
+def _assert_three_rounds(dec, B):
+    """Premise of the multi-group tests: fl_fused's group loop (workgroup w decodes groups w, w + grid, ...)
+    gives at least one workgroup three groups. Returns (ngroups, grid, codewords per group)."""
+    n = 4 if dec.precision == torch.float32 else 2
+    ngroups, grid = dec.fused_geometry(B)
+    print(f"fused geometry: B={B} {dec.precision} kind={dec.kind}: ngroups={ngroups} grid={grid}")
+    assert grid > 0 and ngroups >= 2 * grid + 1, (
+        f"no workgroup reaches a third group: B={B} gives ngroups={ngroups} on grid={grid} "
+        f"({n} codewords per group); this device needs B >= {n * 2 * grid + 1}")
+    return ngroups, grid, n
+
+
+def _round_columns(B, n, grid, spread=150, seed=0):
+    """Column subset for fixed-iteration decodes (columns are independent there): the batch's first and last
+    column, the first and last column of every workgroup round (boundaries at multiples of n * grid), and
+    `spread` columns drawn from the second round on."""
+    edge = n * grid
+    cols = {0, B - 1}
+    for r in range(1, (B - 1) // edge + 1):
+        cols |= {r * edge - 1, r * edge}
+    later = np.arange(edge, B)
+    cols |= set(np.random.default_rng(seed).choice(later, size=min(spread, later.size), replace=False).tolist())
+    return np.array(sorted(cols))
 
 
 @pytest.mark.parametrize("kind", [oracle.MINSUM, oracle.BP])
@@ -285,7 +311,10 @@ def test_count_below_matches_numpy(eng):
     ("wlan", 30, 64, True, 4.0),       # batch-global stop before imax-1: pass 2 re-runs to L
     ("wlan", 2, 5, True, 1.0),
     ("reg", 12, 130, True, 3.0),
-    ("wlan1944", 8, 1000, False, 1.5)])
+    ("wlan1944", 8, 1000, False, 1.5),
+    # >= 3 groups per workgroup (asserted below; fp32 BP has no fp32 oracle, so this is its multi-group check):
+    ("wlan1944", 12, 2101, True, 5.0),      # ragged last group, batch-global stop: pass 2 re-runs every group
+    ("wlan1944", 6, 2104, False, 1.5)])     # whole groups, aligned stores
 def test_fused_equals_passes(eng, prec, kind, name, imax, B, early, ebn0, wlan_H, reg_H):
     from informationbottleneckdecodingldpc_amd import codes
     H = {"wlan": wlan_H, "reg": reg_H}.get(name)
@@ -294,7 +323,10 @@ def test_fused_equals_passes(eng, prec, kind, name, imax, B, early, ebn0, wlan_H
     g = graph.build_graph(H)
     G = eng.Graph(g, DEV)
     llr = _llrs(g, B, ebn0, seed=imax * 7 + B, quantised=True)
-    fused, it_f = _gpu(eng, g, kind, imax, llr, prec, early, graph_obj=G, path="fused")
+    fdec = eng.FloatDecoder(G, kind, imax, B, precision=prec, path="fused")
+    if B > 2100:
+        _assert_three_rounds(fdec, B)
+    fused, it_f = _gpu(eng, g, kind, imax, llr, prec, early, dec=fdec)
     passes, it_p = _gpu(eng, g, kind, imax, llr, prec, early, graph_obj=G, path="passes")
     assert it_f == it_p
     np.testing.assert_array_equal(fused, passes)
@@ -351,6 +383,145 @@ def test_fused_path_selection(eng, wlan_H, dvb_H):
         if not fits:
             with pytest.raises(IBLError):
                 eng.FloatDecoder(R, 0, 5, 16, path="fused")
+
+
+def test_fused_geometry_query(eng, wlan_H):
+    """ibl_float_fused_geometry: groups of 4 fp32 / 2 fp64 codewords, grid = min(ngroups, blocks per CU x CUs);
+    (0, 0) off the fused path; B outside [1, max_batch] is an error, as for a decode."""
+    from informationbottleneckdecodingldpc_amd._lib import IBLError
+    G = eng.Graph(graph.build_graph(wlan_H), DEV)
+    assert eng.FloatDecoder(G, 0, 5, 16, path="fused").fused_geometry(5) == (2, 2)
+    assert eng.FloatDecoder(G, 1, 5, 16, precision=torch.float64).fused_geometry(5) == (3, 3)
+    assert eng.FloatDecoder(G, 0, 5, 16, path="passes").fused_geometry(5) == (0, 0)
+    big = eng.FloatDecoder(G, 0, 5, 8192, path="fused")
+    ngroups, grid = big.fused_geometry(8192)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    assert ngroups == 2048 and 0 < grid <= ngroups and grid % cus == 0, (ngroups, grid, cus)
+    with pytest.raises(IBLError):
+        big.fused_geometry(8193)
+
+
+# ------------------------------------------------------------------ fused path, several groups per workgroup
+# fl_fused's grid is min(ngroups, blocks per CU x CUs): a workgroup reaches a second group only when the batch
+# has more groups than that (WLAN N=1944 on an MI355X: one block per CU, 256 workgroups, so above 1024 fp32 /
+# 512 fp64 codewords). What can be wrong only from the second group on: cw0 / valid / the channel slot taken
+# from the block index instead of the group, the two LDS ticket counters and the phase parity carried across
+# groups (2L+1 phases per group: the parity flips every group), stale messages of the previous group, a
+# ragged last group on a later round, the early-stop re-run over several groups, syndrome flags set by the
+# padded codewords of a ragged group. Every test asserts three rounds on some workgroup (_assert_three_rounds).
+@pytest.fixture(scope="module")
+def wlan1944(eng):
+    g = graph.build_graph(codes.wlan_80211n(81))
+    return g, eng.Graph(g, DEV)
+
+
+@pytest.fixture(scope="module")
+def converging_2101(wlan1944):
+    """B = 2101 at 4.5 dB (526 fp32 groups, the last with one valid codeword), i_max = 30, early stop: the fp32
+    oracle's outputs and stop iteration (shared by the tests below; not modified)."""
+    g, _ = wlan1944
+    llr = _llrs(g, 2101, 4.5, seed=11).astype(np.float32)
+    ref, ref_it = oracle.float32_decode(g, 30, llr, early_stop=True, return_iters=True)
+    assert 1 <= ref_it < 30 - 1, ref_it          # premise: the batch-global stop comes before i_max - 1
+    return llr, ref.astype(np.float64), ref_it
+
+
+def test_fused_multigroup_f32_minsum_early_stop(eng, wlan1944, converging_2101):
+    """fp32 min-sum, whole batch, early stop before i_max - 1 (both fused launches, the second re-running every
+    group to L), ragged last group on a workgroup's third round: stop iteration and every APP LLR equal the
+    fp32 oracle's."""
+    g, G = wlan1944
+    llr, ref, ref_it = converging_2101
+    dec = eng.FloatDecoder(G, oracle.MINSUM, 30, 2101, precision=torch.float32, path="fused")
+    _assert_three_rounds(dec, 2101)
+    out, it = _gpu(eng, g, oracle.MINSUM, 30, llr, torch.float32, True, dec=dec)
+    assert it == ref_it
+    np.testing.assert_array_equal(out, ref)
+
+
+def test_fused_multigroup_f32_minsum_fixed_aligned(eng, wlan1944):
+    """fp32 min-sum, fixed i_max = 50, B = 2104 (B % 4 == 0: the aligned float4 store path), non-converging
+    batch at 1.5 dB. Without early stop the columns are independent, so a column subset — the batch's and every
+    workgroup round's first and last column plus 150 columns of rounds two and three — is compared with the fp32
+    oracle bit for bit."""
+    g, G = wlan1944
+    B, imax = 2104, 50
+    llr = _llrs(g, B, 1.5, seed=13).astype(np.float32)
+    dec = eng.FloatDecoder(G, oracle.MINSUM, imax, B, precision=torch.float32, path="fused")
+    _, grid, n = _assert_three_rounds(dec, B)
+    cols = _round_columns(B, n, grid, seed=14)
+    assert {0, B - 1, n * grid - 1, n * grid, 2 * n * grid - 1, 2 * n * grid} <= set(cols.tolist())
+    assert (cols >= n * grid).sum() >= 150
+    ref = oracle.float32_decode(g, imax, np.ascontiguousarray(llr[:, cols])).astype(np.float64)
+    assert (ref < 0).any(0).sum() >= cols.size // 4          # premise: a non-converging batch
+    out, _ = _gpu(eng, g, oracle.MINSUM, imax, llr, torch.float32, False, dec=dec)
+    np.testing.assert_array_equal(out[:, cols], ref)
+
+
+@pytest.mark.parametrize("kind", [oracle.MINSUM, oracle.BP])
+def test_fused_multigroup_f64_early_stop(eng, wlan1944, kind):
+    """fp64 (2 codewords per group), B = 1101: 551 groups, ragged, i_max = 20, 5.0 dB, early stop, whole batch
+    against the fp64 oracle: equal stop iteration; min-sum bit-equal, BP within the file's fp64 bar (1e-9)."""
+    g, G = wlan1944
+    B, imax = 1101, 20
+    llr = _llrs(g, B, 5.0, seed=12)
+    ref, ref_it = oracle.float_decode(g, kind, imax, llr, early_stop=True, return_iters=True)
+    assert 1 <= ref_it < imax - 1, ref_it
+    dec = eng.FloatDecoder(G, kind, imax, B, precision=torch.float64, path="fused")
+    _assert_three_rounds(dec, B)
+    out, it = _gpu(eng, g, kind, imax, llr, torch.float64, True, dec=dec)
+    assert it == ref_it
+    if kind == oracle.MINSUM:
+        np.testing.assert_array_equal(out, ref)
+    else:
+        np.testing.assert_allclose(out, ref, rtol=0, atol=1e-9)
+
+
+def test_fused_multigroup_reused_decoder(eng, wlan1944, converging_2101):
+    """One decoder, two batches: a noisy B = 2104 batch (1.5 dB, early stop requested, never satisfied) and then
+    the converging ragged B = 2101 batch. The second decode's stop iteration and outputs equal the oracle's — it
+    would not stop (or stop late) if the first batch's codewords, left in the staged channel rows beside the
+    ragged group's one valid codeword, fed the syndrome flags."""
+    g, G = wlan1944
+    llr, ref, ref_it = converging_2101
+    imax = 30
+    dec = eng.FloatDecoder(G, oracle.MINSUM, imax, 2104, precision=torch.float32, path="fused")
+    _assert_three_rounds(dec, 2104)
+    _assert_three_rounds(dec, 2101)
+    noisy = _llrs(g, 2104, 1.5, seed=13).astype(np.float32)
+    _, it0 = _gpu(eng, g, oracle.MINSUM, imax, noisy, torch.float32, True, dec=dec)
+    assert it0 == imax - 1, it0                   # premise: the first batch ran every iteration
+    out, it = _gpu(eng, g, oracle.MINSUM, imax, llr, torch.float32, True, dec=dec)
+    assert it == ref_it
+    np.testing.assert_array_equal(out, ref)
+
+
+def test_fused_multigroup_small_code(eng, wlan_H):
+    """The N = 1296 fixture code, fp32 min-sum, fixed i_max = 10, B = 4 * (2 grid) + 5 with grid read from the
+    geometry query (a probe decoder whose batch has more groups than any grid): three rounds, the third of two
+    groups, the last ragged. A column subset chosen as in test_fused_multigroup_f32_minsum_fixed_aligned equals
+    the fp32 oracle bit for bit. The smaller code was meant to put more than one block on a CU; its messages,
+    channel and slot indices still take more than half of the CU's 160 KiB LDS, so on an MI355X the grid is the
+    CU count (256) here too — the test then differs from the N = 1944 ones in the code, its task tables and the
+    unaligned ragged stores."""
+    g = graph.build_graph(wlan_H)
+    G = eng.Graph(g, DEV)
+    imax = 10
+    probe = eng.FloatDecoder(G, oracle.MINSUM, imax, 8192, precision=torch.float32, path="fused")
+    ngroups, grid = probe.fused_geometry(8192)
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    print(f"fused geometry probe (N=1296): ngroups={ngroups} grid={grid} CUs={cus}")
+    assert 0 < grid < ngroups, f"probe batch too small to show the grid: ngroups={ngroups} grid={grid}"
+    del probe
+    B = 4 * (2 * grid) + 5
+    llr = _llrs(g, B, 1.5, seed=15).astype(np.float32)
+    dec = eng.FloatDecoder(G, oracle.MINSUM, imax, B, precision=torch.float32, path="fused")
+    _, grid_b, n = _assert_three_rounds(dec, B)
+    assert grid_b == grid
+    cols = _round_columns(B, n, grid, seed=16)
+    ref = oracle.float32_decode(g, imax, np.ascontiguousarray(llr[:, cols])).astype(np.float64)
+    out, _ = _gpu(eng, g, oracle.MINSUM, imax, llr, torch.float32, False, dec=dec)
+    np.testing.assert_array_equal(out[:, cols], ref)
 
 
 @pytest.mark.parametrize("path", ["auto", "passes"])
@@ -474,8 +645,8 @@ def test_float_fold_absent_without_degree2(eng, reg_H):
 @pytest.mark.parametrize("path", ["auto", "passes"])
 def test_float_input_check(eng, wlan_H, path):
     """ibl_float_input_check: the staging kernels count channel LLRs that break
-    ibl_float_decode's precondition — BP fp64: NaN, |x| > ln(DBL_MAX) = 709.78 (where the reference's box-plus
-    e^a overflows to NaN); BP fp32: NaN, +-inf (the value the decoder stages); min-sum: NaN only (+-inf is a
+    ibl_float_decode's precondition — BP fp64: NaN, |x| > 709.089 (just under ln(DBL_MAX / 2), where the
+    reference's box-plus of two same-sign raw values overflows e^a + e^b beside an infinite numerator: NaN); BP fp32: NaN, +-inf (the value the decoder stages); min-sum: NaN only (+-inf is a
     known bit) — and the query returns IBL_EINVAL with the count; valid inputs count 0. The BP case with +-inf
     inputs is the one that failed in round 4 (gpurun_out/r4c2) before the precondition was narrowed."""
     from informationbottleneckdecodingldpc_amd._lib import IBLError
@@ -488,7 +659,7 @@ def test_float_input_check(eng, wlan_H, path):
     bad_inf = llr.copy()
     bad_inf[pos] = np.where(rng.random(pos.sum()) < 0.8, np.inf, -np.inf)
     big = llr.copy()
-    # fp64 BP: 709.8, -1e6, 1e30, 1e300 break |x| <= 709.78; fp32 BP: only 1e300 (inf once staged in fp32)
+    # fp64 BP: 709.8, -1e6, 1e30, 1e300, 709.78 break |x| <= 709.089; fp32 BP: only 1e300 (inf once staged in fp32)
     big[0, :8] = [709.0, -709.0, 709.8, -1e6, 500.0, 1e30, 1e300, 709.78]
     nan = llr.copy()
     nan[3, 7] = np.nan
@@ -507,17 +678,18 @@ def test_float_input_check(eng, wlan_H, path):
         ms.decode(torch.from_numpy(bad_inf).to(DEV).to(prec), early_stop=False)
         assert ms.input_violations() == 0                       # +-inf allowed for min-sum
         bp.decode(torch.from_numpy(big).to(DEV).to(torch.float64), early_stop=False)
-        assert bp.input_violations(raise_on_error=False) == (4 if prec == torch.float64 else 1)
+        assert bp.input_violations(raise_on_error=False) == (5 if prec == torch.float64 else 1)
         bp.decode(torch.from_numpy(big.astype(np.float32)).to(DEV), early_stop=False)   # f32 caller values
-        assert bp.input_violations(raise_on_error=False) == (4 if prec == torch.float64 else 1)
+        assert bp.input_violations(raise_on_error=False) == (5 if prec == torch.float64 else 1)
         for dec in (bp, ms):
             dec.decode(torch.from_numpy(nan).to(DEV).to(prec), early_stop=False)
             assert dec.input_violations(raise_on_error=False) == 1
 
 
 def test_bp_large_finite_channel_llrs(eng, wlan_H):
-    """BP takes every channel LLR the reference decodes without NaN. fp64: |x| up to ln(DBL_MAX) —
-    e^(a+b) may overflow (the reference then gets log(inf) = inf, clamped to +-llr_max) while e^a does not — equals
+    """BP takes every channel LLR the reference decodes without NaN. fp64: |x| up to 709.089 (just under
+    ln(DBL_MAX / 2)) — e^(a+b) may overflow (the reference then gets log(inf) = inf, clamped to +-llr_max) while
+    e^a + e^b does not; test_bp_same_sign_pair_on_one_check plants the pairs that meet raw — equals
     the fp64 oracle (1e-9) with no violation counted. fp32 (overflow-free box-plus): any finite value; channel
     values of +-1e30 decode like +-4000 (beyond any sum of clamped messages, so both clamp to +-llr_max in every
     message), so every APP LLR other than those channel positions' own equals the +-4000 decode, and theirs keep its
@@ -530,8 +702,8 @@ def test_bp_large_finite_channel_llrs(eng, wlan_H):
     pos = rng.random(llr.shape) < 0.02
     sgn = np.where(rng.random(pos.sum()) < 0.8, 1.0, -1.0)
     big = llr.copy()
-    big[pos] = sgn * rng.uniform(354.0, 709.78, pos.sum())
-    big[0, :2] = [709.78, 709.78]                           # both inputs of one check near the limit
+    big[pos] = sgn * rng.uniform(354.0, 709.089, pos.sum())
+    big[0, :2] = [709.089, 709.089]                         # one variable of two codewords at the limit
     dec = eng.FloatDecoder(G, oracle.BP, 15, B, precision=torch.float64)
     out = dec.decode(torch.from_numpy(big).to(DEV), early_stop=False)
     assert dec.input_violations() == 0
@@ -548,6 +720,71 @@ def test_bp_large_finite_channel_llrs(eng, wlan_H):
     assert np.isfinite(oh).all()
     np.testing.assert_array_equal(oh[~pos], oc[~pos])
     assert ((oh[pos] < 0) == (oc[pos] < 0)).all()
+
+
+def _raw_pair_variables(g):
+    """Variables whose channel values meet raw in a first-pass box-plus fold, taken from the graph's own edge
+    order (check c's input k comes from variable csr_cols[cn_start[c] + k]): inputs (0, 1) of one check — the
+    fold of every output w >= 2 starts with them — (D-2, D-1) of a second (the pair a backward fold starts with)
+    and (1, 2) of a third (the start of output 0's fold), the three checks sharing no planted variable.
+    Returns three (variable, variable) pairs."""
+    pairs, used = [], set()
+    for lo in ("first", "last", "second"):
+        for c in range(g.n_c):
+            d, s = int(g.cn_deg[c]), int(g.cn_start[c])
+            k = {"first": 0, "last": d - 2, "second": 1}[lo]
+            row = set(g.csr_cols[s:s + d].tolist())
+            v = (int(g.csr_cols[s + k]), int(g.csr_cols[s + k + 1]))
+            if d >= 4 and not (row & used):
+                pairs.append(v)
+                used |= row
+                break
+    assert len(pairs) == 3
+    return pairs
+
+
+def test_bp_same_sign_pair_on_one_check(eng, wlan_H):
+    """Two same-sign channel values at the fp64 BP bound on ONE check of ONE codeword — the case the bound is
+    about: the first check pass box-pluses them raw, log((1 + e^(a+b)) / (e^a + e^b)) with e^(a+b) = inf, and
+    e^a + e^b must stay finite (|x| <= 709.089 < ln(DBL_MAX / 2)) or the quotient is inf / inf = NaN. Column 0
+    carries (+, +) on the first check's pair, (-, -) on the second's, (+, +) on the third's; column 1 the mirrored
+    signs. At 709.089: no violation, no NaN on the GPU or in the oracle, both paths equal the oracle (1e-9). At
+    709.5 in the same places: every planted value is counted and the reference-named class raises; nothing is
+    asserted about those outputs."""
+    from informationbottleneckdecodingldpc_amd._lib import IBLError
+    from informationbottleneckdecodingldpc_amd.bp_decoder_irreg import BeliefPropagationDecoderClassIrregular
+    g = graph.build_graph(wlan_H)
+    G = eng.Graph(g, DEV)
+    B, imax = 8, 15
+    base = _llrs(g, B, 1.5, seed=93)
+    pairs = _raw_pair_variables(g)
+
+    def planted(x):
+        llr = base.copy()
+        for i, (u, v) in enumerate(pairs):
+            s = -1.0 if i == 1 else 1.0
+            llr[[u, v], 0] = s * x
+            llr[[u, v], 1] = -s * x
+        return llr
+
+    n_planted = 2 * 2 * len(pairs)
+    ok = planted(709.089)
+    assert (np.abs(ok) == 709.089).sum() == n_planted
+    ref = oracle.float_decode(g, oracle.BP, imax, ok)
+    assert not np.isnan(ref).any()
+    for path in ("auto", "passes"):
+        dec = eng.FloatDecoder(G, oracle.BP, imax, B, precision=torch.float64, path=path)
+        out = dec.decode(torch.from_numpy(ok).to(DEV), early_stop=False).cpu().numpy()
+        assert dec.input_violations() == 0
+        assert not np.isnan(out).any()
+        np.testing.assert_allclose(out, ref, rtol=1e-15, atol=1e-9)
+        dec.decode(torch.from_numpy(planted(709.5)).to(DEV), early_stop=False)
+        assert dec.input_violations(raise_on_error=False) == n_planted
+    bp = BeliefPropagationDecoderClassIrregular(wlan_H, imax, 16, B, precision=torch.float64)
+    bp.init_OpenCL_decoding(B)
+    bp.decode_OpenCL_belief_propagation(ok)
+    with pytest.raises(IBLError, match="BP precondition"):
+        bp.decode_OpenCL_belief_propagation(planted(709.5))
 
 
 def test_dropin_bp_raises_on_invalid_channel(wlan_H):
