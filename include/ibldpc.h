@@ -115,6 +115,20 @@ int ibl_ib_path_in_use(const ibl_ib* h, int32_t* fused);
 int ibl_ib_set_small_batch(ibl_ib* h, int32_t max_b);
 int ibl_ib_small_batch(const ibl_ib* h, int32_t* max_b);
 /*
+ * Degree-2 variable fold of the per-pass fast path (no reference counterpart; outputs and stop iterations
+ * are identical with and without it): the message of a degree-2 variable to one of its checks is one
+ * table lookup F2(channel, message from the other check), so the check pass that computes that message
+ * applies the lookup itself and writes the result into the next check pass's inbox; the variable pass
+ * skips the variable.  A variable is folded when in both of its checks its edge is one of the last two
+ * inputs (ascending column order) of a check of degree >= 3 — every staircase parity variable of a code
+ * whose parity columns come last.  *n_folded = number of folded variables (0: none qualify, a check
+ * degree above 8, no fast path, or the fold's table does not fit the check pass's LDS).
+ * ibl_ib_set_fold switches the fold off / on (default: on); the small-batch kernels and the fused path
+ * never fold.
+ */
+int ibl_ib_folded(const ibl_ib* h, int32_t* n_folded);
+int ibl_ib_set_fold(ibl_ib* h, int32_t on);
+/*
  * Codewords per workgroup the fused kernel runs a batch of B with (no reference counterpart; results are
  * identical either way): 8, or 4 (half groups) when 2 * ceil(B / 8) workgroups fit the grid or the
  * environment IBL_FUSED_NCW=4 forces them and the half-group kernel fits the device; 0 when decodes do

@@ -205,6 +205,15 @@ struct ibl_ib {
   int8_t cn_ccol[kMaxD + 1][4] = {{0}}, vn_ccol[kMaxD + 1][4] = {{0}};
   KCfg kcn, kvn, kdec;
   KTimer timer;
+  // degree-2 variable fold of the per-pass path (plan.h plan_ib_fold; ib_cn_fast<8, ., FOLD>): the host plan
+  // (per-check records, class-sorted check work order, work order of the variables left to the variable pass),
+  // uploaded with the second check inbox once a batch reaches the folding kernels (ib_fold_alloc); fold_slot =
+  // LDS slot of the transposed degree-2 variable table in every check pass's image
+  int32_t n_folded = 0, fold_slot = -1, n_rest = 0, rest_heavy = 0;
+  bool fold_on = true;
+  std::vector<int32_t> fold_rec, fold_cn_info, fold_vn_info;
+  uint8_t* cin2 = nullptr;
+  int32_t *fold = nullptr, *cn_info_f = nullptr, *vn_info_r = nullptr;
   // fused on-chip path (IbFusedArgs, short codes): task tables, LDS bytes per workgroup, grid
   int32_t path = IBL_PATH_AUTO;
   bool fused_ok = false, f_half_ok = false;   // f_half_ok: the 4-codeword-group kernel is usable too
@@ -415,6 +424,7 @@ int pick_cfg(int which, int maxd, int nt, int ncs, int num_cus, KCfg* k) {
 }
 
 int ib_fused_setup(ibl_ib* h);           // fused on-chip IB decoder (defined with the float one below)
+int ib_fold_alloc(ibl_ib* h);            // the fold's device state (likewise)
 bool ib_fused_in_use(const ibl_ib* h);
 
 // Codewords per workgroup of the fused IB kernel for a batch of B: 4-codeword half groups when even the
@@ -520,6 +530,27 @@ int ibl_ib_create(const ibl_graph* g, int32_t Tc, int32_t T, int32_t imax, const
   h->fast = !(flags & IBL_FLAG_FORCE_GENERIC) && Tc == T && T <= kTP && deg_ok && cn_nt <= max_nt &&
             vn_nt <= max_nt && VM <= max_nt && cn_nt > 0 && lds_ok;
 
+  if (h->fast && CM <= 8) {
+    // Degree-2 variable fold: planned when the folding kernels exist for this code (the degree <= 8 bodies) and
+    // the transposed degree-2 variable table fits the check pass's LDS — a free slot of its quads (DVB-S2: 6 of
+    // 8 used), or one more quad if the LDS has room for it.
+    std::vector<int32_t> rec, rest;
+    const int32_t n = plan_ib_fold(*g, &rec, &rest);
+    if (n > 0 && cn_nt + 1 <= max_nt && fast_lds(cn_nt + 1, h->cn_ncs) <= (size_t)kLdsBytes) {
+      h->n_folded = n;
+      h->fold_slot = cn_nt++;
+      std::vector<int32_t> cls((size_t)g->n_c), all((size_t)g->n_c);
+      for (int32_t c = 0; c < g->n_c; ++c) {
+        cls[c] = rec[(size_t)kIbFoldRec * c];
+        all[c] = c;
+      }
+      int32_t heavy = 0;
+      h->fold_cn_info = work_order_keyed(all, g->h_cn_start, g->h_cn_deg, &cls, &heavy);
+      h->fold_vn_info = work_order_keyed(rest, g->h_vn_start, g->h_vn_deg, nullptr, &h->rest_heavy);
+      h->n_rest = (int32_t)rest.size();
+      h->fold_rec.swap(rec);
+    }
+  }
   if (h->fast) {
     // ---------------- CN images: pass p = 0 (iteration 0 ops) .. imax-1
     std::vector<uint32_t> cimg, vimg, dimg, ccimg, vcimg;
@@ -548,6 +579,16 @@ int ibl_ib_create(const ibl_graph* g, int32_t Tc, int32_t T, int32_t imax, const
         if (d == 2) tbs.push_back(make_table(T, [&](int t, int) { return match_cn[mrow + t]; }));
         else tbs.push_back(make_table(T, [&](int t, int m) { return match_cn[mrow + cn_raw(p, d - 3, t, m)]; }));
         h->cn_fslot[d] = slot++;
+      }
+      if (h->fold_slot >= 0) {
+        // the update of a degree-2 variable, transposed: row = the check's output, column = the channel value;
+        // the table (matching composed) the variable pass after check pass p looks up as (channel, message)
+        const int64_t mrow = (int64_t)p * T * VM + (int64_t)T;
+        tbs.resize((size_t)h->fold_slot, Table(256, 0));
+        tbs.push_back(make_table(T, [&](int t, int m) {
+          const int r = vn_raw(p, 0, m, t);
+          return h->match ? match_vn[mrow + r] : r;
+        }));
       }
       append_pass(cimg, tbs, regions_of(cn_nt));
       append_cols(ccimg, tbs, ccol_slot);
@@ -671,6 +712,18 @@ int ibl_ib_path_in_use(const ibl_ib* h, int32_t* fused) {
   return IBL_OK;
 }
 
+int ibl_ib_folded(const ibl_ib* h, int32_t* n_folded) {
+  if (!h || !n_folded) return fail(IBL_EINVAL, "NULL argument");
+  *n_folded = h->n_folded;
+  return IBL_OK;
+}
+
+int ibl_ib_set_fold(ibl_ib* h, int32_t on) {
+  if (!h) return fail(IBL_EINVAL, "decoder is NULL");
+  h->fold_on = on != 0;
+  return IBL_OK;
+}
+
 int ibl_ib_timing(ibl_ib* h, int32_t enable) {
   if (!h) return fail(IBL_EINVAL, "decoder is NULL");
   h->timer.on = enable != 0;
@@ -696,6 +749,7 @@ void ibl_ib_destroy(ibl_ib* h) {
   dfree(h->cin); dfree(h->vin); dfree(h->ch8); dfree(h->flags); dfree(h->dL);
   dfree(h->cn_img); dfree(h->vn_img); dfree(h->dec_img); dfree(h->cn_cimg); dfree(h->vn_cimg);
   dfree(h->cn_lut); dfree(h->vn_lut); dfree(h->mc); dfree(h->mv);
+  dfree(h->cin2); dfree(h->fold); dfree(h->cn_info_f); dfree(h->vn_info_r);
   dfree(h->f_cn_task); dfree(h->f_vn_task); dfree(h->f_vn_node); dfree(h->f_vn_slot);
   delete h;
 }
@@ -838,6 +892,24 @@ int ibl_ib_decode(ibl_ib* h, const void* d_ch, int32_t ch_dtype, int32_t B, void
     vn.info = g->vn_info; vn.tgt = g->tgt_vn; vn.out = h->cin; vn.in = h->vin;
     cn.n_nodes = g->n_c; vn.n_nodes = g->n_v;
     cn.n_heavy = g->cn_heavy; vn.n_heavy = g->vn_heavy;
+    // Degree-2 variable fold: check pass j < I-1 applies the folded variables' update itself and writes the
+    // result into the inbox check pass j+1 reads, cb[(j + 1) & 1]; variable pass j writes the rest there. The
+    // last check pass folds nothing (the decision reads every variable-inbox row); with early stop any pass
+    // from 1 on may be the last, so those also write the folded edges' variable-inbox rows (fold_mode 2).
+    const bool fold = h->fold_on && h->n_folded > 0 && I > 1;
+    if (fold) {
+      const int rc = ib_fold_alloc(h);
+      if (rc) return rc;
+      vn.info = h->vn_info_r; vn.n_nodes = h->n_rest; vn.n_heavy = h->rest_heavy;
+      cn.fold = h->fold; cn.fold_slot = h->fold_slot;
+    }
+    uint8_t* cb[2] = {h->cin, fold ? h->cin2 : h->cin};
+    auto cn_fold = [&](int j) {   // check pass j's work order and fold mode
+      const bool f = fold && j < I - 1;
+      cn.info = f ? h->cn_info_f : g->cn_info;
+      cn.fold_mode = f ? ((early && j >= 1) ? 2 : 1) : 0;
+      cn.fout = f ? cb[(j + 1) & 1] : nullptr;
+    };
 #if IBL_DIAG
     // diagnostic builds only (timing, outputs are not decodes): IBL_VN_PART=heavy / light runs the variable
     // pass over one item class only (the degree > kLightD items, or the rest)
@@ -866,6 +938,7 @@ int ibl_ib_decode(ibl_ib* h, const void* d_ch, int32_t ch_dtype, int32_t B, void
     // pass 0: send + checknode_update_iter0, inputs gathered from the staged channel rows
     cn.in = nullptr; cn.gather = g->csr_cols; cn.img = h->cn_img; cn.gate = nullptr; cn.unsat = nullptr;
     cn.cimg = h->cn_cimg;
+    cn_fold(0);
     auto launch_cn = [&]() { return launch_ib_cn_fast(cn, h->CM, h->kcn.grid, h->kcn.block, h->kcn.lds, s); };
     HIPCHK(h->timer.timed(0, s, launch_cn));
     cn.gather = nullptr;
@@ -885,13 +958,15 @@ int ibl_ib_decode(ibl_ib* h, const void* d_ch, int32_t ch_dtype, int32_t B, void
       vn.cimg = h->vn_cimg + (size_t)(j - 1) * h->vn_ncs * 32;
       vn.gate = gate;
       vn.trace = (trace && j == I / 2) ? trace : nullptr;
+      vn.out = cb[j & 1];
       HIPCHK(h->timer.timed(1, s, [&] { return launch_ib_vn_fast(vn, h->VM, h->kvn.grid, h->kvn.block, h->kvn.lds, s); }));
       cn.img = h->cn_img + (size_t)j * h->cn_nt * 256;
       cn.cimg = h->cn_cimg + (size_t)j * h->cn_ncs * 32;
       cn.gate = gate;
       cn.unsat = early ? h->flags + (size_t)j * kShards : nullptr;
       cn.trace = (trace && j == I / 2) ? trace + 3 * nwv : nullptr;
-      cn.in = h->cin;
+      cn.in = cb[j & 1];
+      cn_fold(j);
       HIPCHK(h->timer.timed(0, s, launch_cn));
     }
 #if IBL_DIAG
@@ -1078,6 +1153,30 @@ void float_fused_geometry(const ibl_float* h, int B, int32_t* ngroups, int32_t* 
 }
 
 bool ib_fused_in_use(const ibl_ib* h) { return h->fused_ok && h->path != IBL_PATH_PASSES; }
+
+// The IB fold's device state, allocated by the first decode that reaches the folding kernels (a batch above the
+// small-batch threshold on the per-pass path with the fold on): second check inbox, per-check records, the
+// class-sorted check work order and the work order of the variables the variable pass still updates.
+int ib_fold_alloc(ibl_ib* h) {
+  if (h->n_folded == 0 || h->cin2) return IBL_OK;
+  const size_t inbox = (size_t)h->g->n_e * h->ldb;
+  uint8_t* c2 = nullptr;
+  int rc = dalloc(&c2, inbox);
+  if (rc) return rc;
+  if (hipMemset(c2, 0, inbox) != hipSuccess) {
+    dfree(c2);
+    return fail(IBL_EHIP, "hipMemset failed");
+  }
+  if ((rc = dupload(&h->fold, h->fold_rec.data(), h->fold_rec.size())) ||
+      (rc = dupload(&h->cn_info_f, h->fold_cn_info.data(), h->fold_cn_info.size())) ||
+      (rc = dupload(&h->vn_info_r, h->fold_vn_info.data(), h->fold_vn_info.size()))) {
+    dfree(c2); dfree(h->fold); dfree(h->cn_info_f); dfree(h->vn_info_r);
+    h->fold = h->cn_info_f = h->vn_info_r = nullptr;
+    return rc;
+  }
+  h->cin2 = c2;
+  return IBL_OK;
+}
 
 // The fold's device state (second check inbox, per-check records, unfolded variable list) once a batch can reach
 // the per-pass kernels (max_batch > small_b): decoders that only ever run the small-batch kernels — the

@@ -108,6 +108,14 @@ struct IbFastArgs {
   // {first position, count, degree, 0}; a wave item is (task, word), nwords = ceil(B / 8)
   const int32_t* task;
   int32_t n_tasks, nwords;
+  // degree-2 variable fold (folding check passes ib_cn_fast<8, ., FOLD>; plan.h plan_ib_fold): per check
+  // kIbFoldRec ints {class, var0, var1, dst0, dst1, ...}; a folded output goes through the transposed degree-2
+  // variable table at LDS slot fold_slot and to row dst of fout, the NEXT check pass's inbox. fold_mode 0: off
+  // (the plain kernels); 1: folded outputs go to fout only; 2: their unfolded values also to the variable
+  // inbox (early stop: any pass may be the last).
+  const int32_t* fold;
+  uint8_t* fout;
+  int32_t fold_mode, fold_slot;
 };
 
 struct IbDecArgs {

@@ -262,6 +262,9 @@ struct ItemBuf {
   int d, st, node;
   uint32_t off;            // byte offset of this lane's words in a row
   int cwb;                 // first codeword of this lane
+  // folding check pass (IbFastArgs::fold, scalars): class, channel rows of inputs D-2 / D-1, rows of their
+  // variables' other edges in the next check inbox
+  int fc, fv0, fv1, fd0, fd1;
 };
 
 // Items of a phase: item = first + (pos - pos0) * nch + chunk (nch chunks of 512*W codewords per node)
@@ -269,7 +272,7 @@ struct PhaseItems {
   int first, pos0, nch;
 };
 
-template <class Buf, bool VN, bool GATHER>
+template <class Buf, bool VN, bool GATHER, int FOLD = 0>
 __device__ __forceinline__ void fetch_item(const IbFastArgs& a, int item, int lane, Buf& b, const PhaseItems& pi) {
   constexpr int W = Buf::W, MAXD = Buf::kMax;
   const int rel = item - pi.first;
@@ -280,6 +283,14 @@ __device__ __forceinline__ void fetch_item(const IbFastArgs& a, int item, int la
   b.node = node;
   b.st = sload(a.info, 4 * pos + 1);
   b.d = sload(a.info, 4 * pos + 2);
+  if constexpr (FOLD != 0) {   // the check's fold record, with the other item words (scalar loads)
+    const int32_t* rec = a.fold + (size_t)kIbFoldRec * node;
+    b.fc = sload(rec, 0);
+    b.fv0 = sload(rec, 1);
+    b.fv1 = sload(rec, 2);
+    b.fd0 = sload(rec, 3);
+    b.fd1 = sload(rec, 4);
+  }
   b.off = (uint32_t)(chunk * (256 * W) + lane * 4 * W);
   b.cwb = chunk * (512 * W) + lane * 8 * W;
   // always MAXD loads (rows past the degree repeat the last row and hit in cache), so the number
@@ -343,17 +354,52 @@ __device__ __forceinline__ void cn_word(uint32_t lane4, const uint32_t (&in)[D],
   for (int k0 = 0; k0 < NCW; k0 += cn_sched_s(D)) cn_group<D>(lane4, in, fbase, cb, outw, k0);
 }
 
+// the folding bodies (degree-2 variable fold): class FC, lane4c = lane term with the fold table's slot,
+// ch0 / ch1 = channel words of the variables at inputs D-2 / D-1
+template <int D, int FC>
+__device__ __forceinline__ void cn_word_fold(uint32_t lane4, const uint32_t (&in)[D], uint32_t fbase,
+                                             const uint32_t (&cb)[4], uint32_t lane4c, uint32_t ch0, uint32_t ch1,
+                                             uint32_t (&outw)[D]) {
+#pragma unroll 1
+  for (int k0 = 0; k0 < 8; k0 += cn_sched_s(D)) cn_group_fold<D, FC>(lane4, in, fbase, cb, lane4c, ch0, ch1, outw, k0);
+}
+// the fold of a finished output word (the keeping passes, which need the unfolded word too): nibble out,
+// lookup against the channel word's column term, nibble back in
+__device__ __forceinline__ uint32_t fold_word(uint32_t w, uint32_t ch, uint32_t lane4c) {
+  uint32_t r = 0;
+#pragma unroll
+  for (int g = 0; g < 2; ++g) {
+    uint32_t t[4];
+#pragma unroll
+    for (int s = 0; s < 4; ++s) t[s] = luc(nib(w, 4 * g + s), colq(ch, 4 * g + s, lane4c), 0u);
+    r |= pack4n(t, g);
+  }
+  return r;
+}
+
 // column-image addresses of the column-fetched inputs of a degree-D node (cb of colf)
 __device__ __forceinline__ void col_bases(const int8_t (&cc)[4], uint32_t lane8c, uint32_t (&cb)[4]) {
 #pragma unroll
   for (int i = 0; i < 4; ++i) cb[i] = lane8c + ((uint32_t)cc[i] << 12);
 }
 
-template <int D, bool GATHER, class Buf>
+// FC / KEEP (folding check pass, D >= 3): bit 0 / 1 of FC = the degree-2 variable at input D-2 / D-1 is folded.
+// Its update F2(channel, this check's output) is one more link of that output's chain (cn_group_fold), and the
+// result goes straight to the row of the variable's other edge in the NEXT iteration's check inbox (fout).
+// With KEEP the unfolded output is also written to the variable inbox (early stop: any pass may be the last
+// and the decision reads every row): the body is the plain one and the fold runs over the finished words
+// (fold_word; both values in registers through the chains would spill). The channel words are loaded here, for the current item (pass 0 gathers
+// them as inputs anyway): they are first used after the output chains, so they need no one-item-ahead buffer.
+template <int D, bool GATHER, class Buf, int FC = 0, bool KEEP = false>
 __device__ __forceinline__ void cn_compute(const IbFastArgs& a, uint32_t lane4, uint32_t lane8c, const Buf& b,
-                                           int fslot, bool do_par, bool& unsat) {
+                                           int fslot, bool do_par, bool& unsat, uint8_t* fout = nullptr) {
   constexpr int W = Buf::W;
   uint32_t outw[D][W], trow[D], cb[4];
+  uint32_t chf[2][W] = {};
+  if constexpr (FC != 0 && !GATHER) {
+    if constexpr ((FC & 1) != 0) load_row<W>(a.ch8 + (size_t)b.fv0 * (uint32_t)a.ldb + b.off, chf[0]);
+    if constexpr ((FC & 2) != 0) load_row<W>(a.ch8 + (size_t)b.fv1 * (uint32_t)a.ldb + b.off, chf[1]);
+  }
   col_bases(a.ccol[D], lane8c, cb);
 #pragma unroll
   for (int w = 0; w < D; ++w) trow[w] = __builtin_amdgcn_readlane(b.tgv, w);
@@ -402,14 +448,64 @@ __device__ __forceinline__ void cn_compute(const IbFastArgs& a, uint32_t lane4, 
         o[0] = in[1];
         o[1] = in[0];
       }
+    } else if constexpr (FC != 0 && !KEEP) {
+      const uint32_t c0 = GATHER ? in[D - 2] : chf[0][i], c1 = GATHER ? in[D - 1] : chf[1][i];
+      cn_word_fold<D, FC>(lane4, in, fbase, cb, lane4 + slot_off(a.fold_slot), c0, c1, o);
     } else {
       cn_word<D>(lane4, in, fbase, cb, o);
     }
 #pragma unroll
     for (int w = 0; w < D; ++w) outw[w][i] = o[w];
   }
+  if constexpr (FC == 0 || KEEP) {
 #pragma unroll
-  for (int w = 0; w < D; ++w) store_row<W, (bool)IBL_NT_CN>(a.out + (size_t)trow[w] * (uint32_t)a.ldb + b.off, outw[w]);
+    for (int w = 0; w < D; ++w) store_row<W, (bool)IBL_NT_CN>(a.out + (size_t)trow[w] * (uint32_t)a.ldb + b.off, outw[w]);
+  }
+  if constexpr (FC != 0 && KEEP) {
+    const uint32_t lane4c = lane4 + slot_off(a.fold_slot);
+#pragma unroll
+    for (int fa = 0; fa < 2; ++fa) {
+      if (!((FC >> fa) & 1)) continue;
+      uint32_t fw[W];
+#pragma unroll
+      for (int i = 0; i < W; ++i) fw[i] = fold_word(outw[D - 2 + fa][i], GATHER ? b.row[D - 2 + fa][i] : chf[fa][i], lane4c);
+      store_row<W, (bool)IBL_NT_CN>(fout + (size_t)(uint32_t)(fa ? b.fd1 : b.fd0) * (uint32_t)a.ldb + b.off, fw);
+    }
+  } else if constexpr (FC != 0) {
+#pragma unroll
+    for (int w = 0; w < D - 2; ++w) store_row<W, (bool)IBL_NT_CN>(a.out + (size_t)trow[w] * (uint32_t)a.ldb + b.off, outw[w]);
+    // the two trailing outputs: compile-time destinations (a run-time choice of the base pointer would go
+    // through a pointer table in scratch)
+    if constexpr ((FC & 1) != 0) {
+      store_row<W, (bool)IBL_NT_CN>(fout + (size_t)(uint32_t)b.fd0 * (uint32_t)a.ldb + b.off, outw[D - 2]);
+    } else {
+      store_row<W, (bool)IBL_NT_CN>(a.out + (size_t)trow[D - 2] * (uint32_t)a.ldb + b.off, outw[D - 2]);
+    }
+    if constexpr ((FC & 2) != 0) {
+      store_row<W, (bool)IBL_NT_CN>(fout + (size_t)(uint32_t)b.fd1 * (uint32_t)a.ldb + b.off, outw[D - 1]);
+    } else {
+      store_row<W, (bool)IBL_NT_CN>(a.out + (size_t)trow[D - 1] * (uint32_t)a.ldb + b.off, outw[D - 1]);
+    }
+  }
+}
+
+// folding check pass: the item's class is wave-uniform (one check per item)
+template <int D, bool GATHER, bool KEEP, class Buf>
+__device__ __forceinline__ void cn_compute_fold(const IbFastArgs& a, uint32_t lane4, uint32_t lane8c, const Buf& b,
+                                                int fslot, bool do_par, bool& unsat) {
+  if constexpr (D >= 3 && D <= 8) {
+    // the next check inbox as an opaque scalar: the classes' store sequences differ only in their base
+    // pointers, and merged into one block they would pick the pointer from a copy of the arguments in scratch
+    uint8_t* fout = a.fout;
+    asm volatile("" : "+s"(fout));
+    switch (b.fc) {
+      case 1: cn_compute<D, GATHER, Buf, 1, KEEP>(a, lane4, lane8c, b, fslot, do_par, unsat, fout); return;
+      case 2: cn_compute<D, GATHER, Buf, 2, KEEP>(a, lane4, lane8c, b, fslot, do_par, unsat, fout); return;
+      case 3: cn_compute<D, GATHER, Buf, 3, KEEP>(a, lane4, lane8c, b, fslot, do_par, unsat, fout); return;
+      default: break;
+    }
+  }
+  cn_compute<D, GATHER>(a, lane4, lane8c, b, fslot, do_par, unsat);
 }
 
 // ---------------------------------------------------------------- variable node
@@ -532,7 +628,7 @@ __device__ __forceinline__ void stage_pass(uint8_t* lds, const IbFastArgs& a) {
 #ifndef IBL_LIGHT_DEPTH
 #define IBL_LIGHT_DEPTH 2
 #endif
-template <class Buf, bool VN, bool GATHER, int DLO, int DEPTH = 2>
+template <class Buf, bool VN, bool GATHER, int DLO, int DEPTH = 2, int FOLD = 0>
 __device__ __forceinline__ void ib_phase(const IbFastArgs& a, uint32_t lane4, uint32_t lane8c, int lane, int first,
                                          int end, int nw, int wpb, int* ctr, bool do_par, bool& unsat,
                                          uint64_t* trace_items, const PhaseItems pi) {
@@ -549,7 +645,9 @@ __device__ __forceinline__ void ib_phase(const IbFastArgs& a, uint32_t lane4, ui
       }
     } else {
       switch (cur.d) {
-#define X(D) case D: if constexpr (D > DLO && D <= Buf::kMax) cn_compute<D, GATHER>(a, lane4, lane8c, cur, a.fslot[D], do_par, unsat); break;
+#define X(D) case D: if constexpr (D > DLO && D <= Buf::kMax) { \
+          if constexpr (FOLD != 0) cn_compute_fold<D, GATHER, FOLD == 2>(a, lane4, lane8c, cur, a.fslot[D], do_par, unsat); \
+          else cn_compute<D, GATHER>(a, lane4, lane8c, cur, a.fslot[D], do_par, unsat); } break;
         IBL_DEG_CASES(X)
 #undef X
         default: break;
@@ -573,25 +671,25 @@ __device__ __forceinline__ void ib_phase(const IbFastArgs& a, uint32_t lane4, ui
     Buf A, Bb, Cc;
     int ia = item_of(take_ticket(ctr, lane));
     if (ia >= end) return;
-    fetch_item<Buf, VN, GATHER>(a, ia, lane, A, pi);
+    fetch_item<Buf, VN, GATHER, FOLD>(a, ia, lane, A, pi);
     int ib = item_of(take_ticket(ctr, lane));
-    fetch_item<Buf, VN, GATHER>(a, min(ib, end - 1), lane, Bb, pi);
+    fetch_item<Buf, VN, GATHER, FOLD>(a, min(ib, end - 1), lane, Bb, pi);
     int kn = take_ticket(ctr, lane);
     for (;;) {
       int ic = item_of(kn);
-      fetch_item<Buf, VN, GATHER>(a, min(ic, end - 1), lane, Cc, pi);
+      fetch_item<Buf, VN, GATHER, FOLD>(a, min(ic, end - 1), lane, Cc, pi);
       kn = take_ticket(ctr, lane);
       compute(A);
       ++done;
       if (ib >= end) break;
       ia = item_of(kn);
-      fetch_item<Buf, VN, GATHER>(a, min(ia, end - 1), lane, A, pi);
+      fetch_item<Buf, VN, GATHER, FOLD>(a, min(ia, end - 1), lane, A, pi);
       kn = take_ticket(ctr, lane);
       compute(Bb);
       ++done;
       if (ic >= end) break;
       ib = item_of(kn);
-      fetch_item<Buf, VN, GATHER>(a, min(ib, end - 1), lane, Bb, pi);
+      fetch_item<Buf, VN, GATHER, FOLD>(a, min(ib, end - 1), lane, Bb, pi);
       kn = take_ticket(ctr, lane);
       compute(Cc);
       ++done;
@@ -601,18 +699,18 @@ __device__ __forceinline__ void ib_phase(const IbFastArgs& a, uint32_t lane4, ui
     Buf A, Bb;
     int item = item_of(take_ticket(ctr, lane));
     if (item >= end) return;
-    fetch_item<Buf, VN, GATHER>(a, item, lane, A, pi);
+    fetch_item<Buf, VN, GATHER, FOLD>(a, item, lane, A, pi);
     int kn = take_ticket(ctr, lane);
     for (;;) {
       int next = item_of(kn);
-      fetch_item<Buf, VN, GATHER>(a, min(next, end - 1), lane, Bb, pi);
+      fetch_item<Buf, VN, GATHER, FOLD>(a, min(next, end - 1), lane, Bb, pi);
       kn = take_ticket(ctr, lane);
       compute(A);
       ++done;
       if (next >= end) break;
       item = next;
       next = item_of(kn);
-      fetch_item<Buf, VN, GATHER>(a, min(next, end - 1), lane, A, pi);
+      fetch_item<Buf, VN, GATHER, FOLD>(a, min(next, end - 1), lane, A, pi);
       kn = take_ticket(ctr, lane);
       compute(Bb);
       ++done;
@@ -684,7 +782,7 @@ __device__ __forceinline__ void ib_phase_mix3(const IbFastArgs& a, uint32_t lane
                                                    trace_items, pil);
 }
 
-template <int MAXD, bool VN, bool GATHER>
+template <int MAXD, bool VN, bool GATHER, int FOLD = 0>
 __device__ __forceinline__ void ib_pass(const IbFastArgs& a, const uint8_t* lds) {
   const int lane = threadIdx.x & 63;
   const uint32_t lane4 = (uint32_t)(lane & 31) << 2;  // LDS address = byte offset (base checked 0)
@@ -732,10 +830,10 @@ __device__ __forceinline__ void ib_pass(const IbFastArgs& a, const uint8_t* lds)
 #pragma unroll 1
   for (int r = 0; r < 2; ++r) {
     if ((r == 0) != light_first)
-      ib_phase<ItemBuf<MAXD, W>, VN, GATHER, kLightD, 2>(a, lane4, lane8c, lane, 0, heavy_end, nw, wpb, ctr, do_par, unsat,
+      ib_phase<ItemBuf<MAXD, W>, VN, GATHER, kLightD, 2, FOLD>(a, lane4, lane8c, lane, 0, heavy_end, nw, wpb, ctr, do_par, unsat,
                                                       trace_items, PhaseItems{0, 0, a.nchunks});
     else
-      ib_phase<ItemBuf<kLightD, LW>, VN, GATHER, 0, (VN ? IBL_LIGHT_DEPTH : 2)>(a, lane4, lane8c, lane, heavy_end, nitems, nw, wpb, ctr + 1, do_par,
+      ib_phase<ItemBuf<kLightD, LW>, VN, GATHER, 0, (VN ? IBL_LIGHT_DEPTH : 2), FOLD>(a, lane4, lane8c, lane, heavy_end, nitems, nw, wpb, ctr + 1, do_par,
                                                    unsat, trace_items, PhaseItems{heavy_end, a.n_heavy, nch_l});
   }
   if (a.trace && lane == 0) {
@@ -765,14 +863,17 @@ __device__ __forceinline__ void ib_pass(const IbFastArgs& a, const uint8_t* lds)
 #ifndef IBL_WPE8C
 #define IBL_WPE8C IBL_WPE8
 #endif
-template <int MAXD, bool GATHER>
+// FOLD (MAXD = 8 only): 1 = degree-2 variable fold (cn_compute), 2 = also keeping the folded edges' variable-
+// inbox rows. The folding kernels take the class-sorted work order and the fold records (IbFastArgs::fold).
+template <int MAXD, bool GATHER, int FOLD = 0>
 __global__ __launch_bounds__(MAXD <= 8 ? IBL_LB8C : IBL_LB16, MAXD <= 8 ? IBL_WPE8C : 1) void ib_cn_fast(IbFastArgs a) {
+  static_assert(FOLD == 0 || MAXD <= 8, "the max-degree-16 bodies do not fold");
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   if (!gate_open(a.gate, threadIdx.x & 63)) return;  // every wave reads the same words: uniform exit
   lds_at_zero(lds);
   stage_pass(lds, a);
   __syncthreads();
-  ib_pass<MAXD, false, GATHER>(a, lds);
+  ib_pass<MAXD, false, GATHER, FOLD>(a, lds);
 }
 
 template <int MAXD>
@@ -1755,7 +1856,18 @@ hipError_t launch_ib_stage4(const void* ch, int dtype, int n, int B, uint8_t* ch
     hipLaunchKernelGGL(ib_stage4<kI32>, dim3(grid), dim3(256), 0, s, ch, n, B, ch4, ldb_bytes, words, nseg, vec);
   return hipGetLastError();
 }
+static bool ib_fold_args_ok(const IbFastArgs& a, int maxd) {
+  return maxd <= 8 && a.fold && a.fout && a.fold_slot >= 0 && a.fold_slot < 8 * (int)(kLdsBytes / kSuper) &&
+         !(a.gather && a.fold_mode == 2);
+}
 hipError_t launch_ib_cn_fast(const IbFastArgs& a, int maxd, int grid, int block, size_t lds, hipStream_t s) {
+  if (a.fold_mode != 0) {
+    if (!ib_fold_args_ok(a, maxd)) return hipErrorInvalidValue;
+    if (a.gather) hipLaunchKernelGGL((ib_cn_fast<8, true, 1>), dim3(grid), dim3(block), lds, s, a);
+    else if (a.fold_mode == 2) hipLaunchKernelGGL((ib_cn_fast<8, false, 2>), dim3(grid), dim3(block), lds, s, a);
+    else hipLaunchKernelGGL((ib_cn_fast<8, false, 1>), dim3(grid), dim3(block), lds, s, a);
+    return hipGetLastError();
+  }
   if (a.gather) {
     if (maxd <= 8) hipLaunchKernelGGL((ib_cn_fast<8, true>), dim3(grid), dim3(block), lds, s, a);
     else hipLaunchKernelGGL((ib_cn_fast<16, true>), dim3(grid), dim3(block), lds, s, a);
@@ -1826,7 +1938,9 @@ hipError_t launch_ib_dec_fast(const IbDecArgs& a, int grid, int block, size_t ld
 }
 hipError_t ib_fast_occupancy(int which, int maxd, int block, size_t lds, int* blocks_per_cu) {
   if (which == 0) {  // every variant must accept the LDS size; report the non-gather one
-    for (const void* g : {(const void*)ib_cn_fast<8, true>, (const void*)ib_cn_fast<16, true>}) {
+    for (const void* g : {(const void*)ib_cn_fast<8, true>, (const void*)ib_cn_fast<16, true>,
+                          (const void*)ib_cn_fast<8, true, 1>, (const void*)ib_cn_fast<8, false, 1>,
+                          (const void*)ib_cn_fast<8, false, 2>}) {
       hipError_t e = hipFuncSetAttribute(g, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
       if (e != hipSuccess) return e;
     }
@@ -1848,7 +1962,11 @@ hipError_t ib_fast_private_bytes(int cn_maxd, int vn_maxd, size_t* bytes, const 
       {c8 ? (const void*)ib_cn_fast<8, true> : (const void*)ib_cn_fast<16, true>, c8 ? "ib_cn_fast<8,gather>" : "ib_cn_fast<16,gather>"},
       {c8 ? (const void*)ib_cn_fast<8, false> : (const void*)ib_cn_fast<16, false>, c8 ? "ib_cn_fast<8>" : "ib_cn_fast<16>"},
       {v8 ? (const void*)ib_vn_fast<8> : (const void*)ib_vn_fast<16>, v8 ? "ib_vn_fast<8>" : "ib_vn_fast<16>"},
-      {(const void*)ib_dec_fast, "ib_dec_fast"}};
+      {(const void*)ib_dec_fast, "ib_dec_fast"},
+      // the folding check passes (launched only when cn_maxd <= 8; checked with every build all the same)
+      {(const void*)ib_cn_fast<8, true, 1>, "ib_cn_fast<8,gather,fold>"},
+      {(const void*)ib_cn_fast<8, false, 1>, "ib_cn_fast<8,fold>"},
+      {(const void*)ib_cn_fast<8, false, 2>, "ib_cn_fast<8,fold,keep>"}};
   *bytes = 0;
   *name = "";
   for (const auto& k : ks) {

@@ -1,8 +1,8 @@
 // Host-side planning of the decoders and the encoder: pure C++17, no HIP.
 //
 // Everything the C ABI derives on the host before a launch lives here — the edge index arrays
-// (map_node_connections), the fast path's work orders and small-batch tasks, the float path's degree-2
-// fold plan, the fused kernels' task tables and the encoder's substitution / factorisation plan — so the
+// (map_node_connections), the fast path's work orders and small-batch tasks, the float and IB paths' degree-2
+// fold plans (the IB one under tests/asan/fold_plan_check.cpp), the fused kernels' task tables and the encoder's substitution / factorisation plan — so the
 // same code is built twice: into libibldpc.so (capi.hip includes this header) and, with AddressSanitizer
 // and UndefinedBehaviorSanitizer, into the CPU-only checker tests/asan/plan_check.cpp
 // (tests/test_cpu_host.py::test_host_planning_under_sanitizers).
@@ -140,6 +140,81 @@ inline int32_t plan_fold(const HostGraph& g, std::vector<int32_t>* rec, std::vec
   for (int32_t v = 0; v < nv; ++v)
     if (!folded[v]) rest->push_back(v);
   return n;
+}
+
+// Degree-2 variable fold of the IB fast path (ib_cn_fast<8, ., true>, IbFastArgs::fold). The check bodies are
+// straight-line code per degree, so the fold sits at fixed positions: a degree-2 variable is folded only when
+// in BOTH of its checks its edge is one of the last two inputs (CSR order) of a check of degree >= 3 — a
+// position holds one variable, so "both or neither" needs no further pruning. Per check kIbFoldRec ints
+// {class, var0, var1, dst0, dst1, 0, 0, 0}: class bit 0 / 1 = the input at position D-2 / D-1 is folded (not
+// necessarily a suffix: DVB-S2's last check holds a degree-2 variable next to the degree-1 one), var = that
+// input's variable (its channel row), dst = the check-order row of the variable's other edge (-1: not folded).
+// Returns the folded count; `rest` gets the variables the variable pass still updates.
+constexpr int kIbFoldRec = 8;
+inline int32_t plan_ib_fold(const HostGraph& g, std::vector<int32_t>* rec, std::vector<int32_t>* rest) {
+  const int32_t nc = g.n_c, nv = g.n_v;
+  rec->assign((size_t)nc * kIbFoldRec, 0);
+  std::vector<int32_t> chk_of(g.h_cols.size());
+  for (int32_t c = 0; c < nc; ++c) {
+    int32_t* r = &(*rec)[(size_t)kIbFoldRec * c];
+    const int32_t d = g.h_cn_deg[c], st = g.h_cn_start[c];
+    for (int32_t k = 0; k < d; ++k) chk_of[(size_t)st + k] = c;
+    for (int a = 0; a < 2; ++a) {
+      r[1 + a] = d >= 2 ? g.h_cols[(size_t)st + d - 2 + a] : 0;
+      r[3 + a] = -1;
+    }
+  }
+  auto tail_pos = [&](int32_t e) {   // 0 / 1: edge e is input D-2 / D-1 of a check of degree >= 3; else -1
+    const int32_t c = chk_of[(size_t)e], d = g.h_cn_deg[c], k = e - g.h_cn_start[c];
+    return d >= 3 && k >= d - 2 ? k - (d - 2) : -1;
+  };
+  rest->clear();
+  int32_t n = 0;
+  for (int32_t v = 0; v < nv; ++v) {
+    int32_t a1 = -1, a2 = -1, e1 = 0, e2 = 0;
+    if (g.h_vn_deg[v] == 2) {
+      e1 = g.h_tgt_vn[(size_t)g.h_vn_start[v]];
+      e2 = g.h_tgt_vn[(size_t)g.h_vn_start[v] + 1];
+      a1 = tail_pos(e1);
+      a2 = tail_pos(e2);
+    }
+    if (a1 < 0 || a2 < 0) {
+      rest->push_back(v);
+      continue;
+    }
+    int32_t* r1 = &(*rec)[(size_t)kIbFoldRec * chk_of[(size_t)e1]];
+    int32_t* r2 = &(*rec)[(size_t)kIbFoldRec * chk_of[(size_t)e2]];
+    r1[0] |= 1 << a1;
+    r1[3 + a1] = e2;
+    r2[0] |= 1 << a2;
+    r2[3 + a2] = e1;
+    ++n;
+  }
+  return n;
+}
+
+// Work order of a node subset (the variables the fold leaves to the variable pass) or with a secondary key (the
+// checks' fold class, so a wave item's class is uniform and equal classes run together): heaviest first, then
+// ascending key, stable; field 3 of a position = its key.
+inline std::vector<int32_t> work_order_keyed(const std::vector<int32_t>& nodes, const std::vector<int32_t>& start,
+                                             const std::vector<int32_t>& deg, const std::vector<int32_t>* key,
+                                             int32_t* heavy) {
+  std::vector<int32_t> idx(nodes);
+  auto kof = [&](int32_t x) { return key ? (*key)[(size_t)x] : 0; };
+  std::stable_sort(idx.begin(), idx.end(), [&](int32_t x, int32_t y) {
+    return deg[x] != deg[y] ? deg[x] > deg[y] : kof(x) < kof(y);
+  });
+  std::vector<int32_t> info(idx.size() * 4);
+  *heavy = 0;
+  for (size_t p = 0; p < idx.size(); ++p) {
+    const int32_t v = idx[p];
+    info[4 * p] = v;
+    info[4 * p + 1] = start[v];
+    info[4 * p + 2] = deg[v];
+    info[4 * p + 3] = kof(v);
+    if (deg[v] > kLightD) ++*heavy;
+  }
+  return info;
 }
 
 // Task tables of the fused kernels (FlFusedArgs, IbFusedArgs).

@@ -79,12 +79,13 @@ class IBDecoder:
 
     ``path`` (fast path only): "auto" (the fused on-chip kernel when the code fits in LDS), "passes"
     (one launch per check / variable pass) or "fused" (raises when the code does not fit); both give
-    identical results (``ibl_ib_set_path``). ``fused`` tells which one decodes run."""
+    identical results (``ibl_ib_set_path``). ``fused`` tells which one decodes run. ``fold`` switches the per-pass
+    path's degree-2 variable fold (``ibl_ib_set_fold``; ``folded`` = variables it folds, results identical)."""
 
     _PATHS = {"auto": _lib.IBL_PATH_AUTO, "passes": _lib.IBL_PATH_PASSES, "fused": _lib.IBL_PATH_FUSED}
 
     def __init__(self, graph: Graph, tables: IBTables, match: bool, max_batch: int, force_generic: bool = False,
-                 path: str = "auto"):
+                 path: str = "auto", fold: bool = True):
         self.graph = graph
         self.tables = tables
         self.match = bool(match)
@@ -106,6 +107,8 @@ class IBDecoder:
         if path not in self._PATHS:
             raise ValueError(f"path must be one of {sorted(self._PATHS)}")
         _lib.check(L.ibl_ib_set_path(h, self._PATHS[path]), "ibl_ib_set_path")
+        if not fold:
+            self.fold = False
 
     @property
     def fused(self) -> bool:
@@ -123,6 +126,23 @@ class IBDecoder:
     @small_batch.setter
     def small_batch(self, max_b: int) -> None:
         _lib.check(_lib.load().ibl_ib_set_small_batch(self._h, int(max_b)), "ibl_ib_set_small_batch")
+
+    @property
+    def folded(self) -> int:
+        """Degree-2 variables the per-pass fast path folds into the check pass (``ibl_ib_folded``)."""
+        f = ctypes.c_int32()
+        _lib.check(_lib.load().ibl_ib_folded(self._h, ctypes.byref(f)), "ibl_ib_folded")
+        return int(f.value)
+
+    @property
+    def fold(self) -> bool:
+        """Whether per-pass decodes fold (``ibl_ib_set_fold``; on by default, a no-op when ``folded`` is 0)."""
+        return getattr(self, "_fold", True)
+
+    @fold.setter
+    def fold(self, on: bool) -> None:
+        _lib.check(_lib.load().ibl_ib_set_fold(self._h, int(bool(on))), "ibl_ib_set_fold")
+        self._fold = bool(on)
 
     def fused_ncw(self, B: int) -> int:
         """Codewords per workgroup the fused kernel decodes a batch of ``B`` with (8, or 4 for half

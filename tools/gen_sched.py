@@ -14,6 +14,13 @@ after another. This script list-schedules the chains onto L concurrent lanes (cr
 and emits straight-line code with one SSA name per value (no register copies): each time step
 issues the lookups of every running lane for all S sub-slots back to back.
 
+Degree-2 variable fold (cn_group_fold<D, FC>, check degrees 3..8). The message of a degree-2 variable to
+one of its checks is F2(channel, message from its other check): one lookup on a value the check pass has
+just computed. The folding bodies append it to the chains of outputs D-2 / D-1 (bit 0 / 1 of the class
+FC) as one more link, t' = luc(t, q_ch, 0) with q_ch the v_perm_b32 column term of the variable's channel
+word (lane term = lane4c, which holds the slot of the transposed degree-2 table) - the price of any
+other lookup, taken while t is still alone in a register. The plain bodies are emitted unchanged.
+
 Column fetches. Input in_j meets the SAME table in every chain that did not fold it into its
 prefix: B_{j-2}(., in_j) in the out0 chain and in chains w = 1..j-1 of a check node (j uses),
 V_{j-1}(., in_j) likewise for a variable node. For the last NC inputs of a node (cn_ncols(D) /
@@ -112,7 +119,7 @@ def schedule(chains, L):
     return out
 
 
-def emit_body(kind, D, S, L, NC):
+def emit_body(kind, D, S, L, NC, fold=False):
     chains = cn_chains(D) if kind == "cn" else vn_chains(D)
     by_id = {c["id"]: c for c in chains}
     sched = schedule(chains, L)
@@ -137,6 +144,10 @@ def emit_body(kind, D, S, L, NC):
     for j in col_in:
         for s in range(S):
             lines.append(f"  const uint64_t C{j}_{s} = colf(nib(in[{j}], k0 + {s}), cb[{j - (D - NC)}]);")
+    if fold:   # column terms of the two trailing variables' channel words (fold table slot in the lane term)
+        for a in range(2):
+            for s in range(S):
+                lines.append(f"  const uint32_t qc{a}_{s} = (FC & {1 << a}) ? colq(ch{a}, k0 + {s}, lane4c) : 0u;")
     if kind == "vn":   # channel nibble as a row term: luc merges it with a column term in one v_lshl_or
         for s in range(S):
             lines.append(f"  const uint32_t c_{s} = nib(chw, k0 + {s});")
@@ -170,6 +181,11 @@ def emit_body(kind, D, S, L, NC):
             if k == len(c["steps"]) - 1:
                 col = is_col(c["steps"][k])
                 vals = [f"({name(cid, k, s)} & 15u)" if col else name(cid, k, s) for s in range(S)]
+                a = c["out"] - (D - 2)
+                if fold and a >= 0:   # fold link: the degree-2 variable's update, F2(channel, this output)
+                    for s in range(S):
+                        lines.append(f"  const uint32_t f_{cid}_{s} = (FC & {1 << a}) ? luc({vals[s]}, qc{a}_{s}, 0u) : {vals[s]};")
+                    vals = [f"f_{cid}_{s}" for s in range(S)]
                 pk = vals[0]
                 for s in range(1, S):
                     pk = f"{pk} | ({vals[s]} << {4 * s})"
@@ -208,6 +224,22 @@ def main():
         print(f"                                                         uint32_t (&o)[{D}], int k0) {{")
         print("\n".join(emit_body("cn", D, *cfg(Sc, Lc, D), cn_ncols(D, NCc))))
         print("}")
+    # Degree-2 variable fold (degrees 3..8): outputs D-2 / D-1 take one more link when bit 0 / 1 of FC is set,
+    # t' = T(t, channel) against the transposed degree-2 variable table at the slot held in lane4c.
+    fargs = ("uint32_t fbase, const uint32_t (&cb)[4], uint32_t lane4c, uint32_t ch0, uint32_t ch1,")
+    for D in range(3, 9):
+        print(f"template <int FC> __device__ __forceinline__ void cn_group_fold{D}(uint32_t lane4, const uint32_t (&in)[{D}],")
+        print(f"    {fargs}")
+        print(f"    uint32_t (&o)[{D}], int k0) {{")
+        print("\n".join(emit_body("cn", D, *cfg(Sc, Lc, D), cn_ncols(D, NCc), fold=True)))
+        print("}")
+    print("template <int D, int FC> __device__ __forceinline__ void cn_group_fold(uint32_t lane4, const uint32_t (&in)[D],")
+    print(f"    {fargs}")
+    print("    uint32_t (&o)[D], int k0) {")
+    print("  static_assert(D >= 3 && D <= 8, \"the fold exists for the degree <= 8 bodies\");")
+    for D in range(3, 9):
+        print(f"  if constexpr (D == {D}) cn_group_fold{D}<FC>(lane4, in, fbase, cb, lane4c, ch0, ch1, o, k0);")
+    print("}")
     for D in range(2, KMAXD + 1):
         print(f"template <> __device__ __forceinline__ void vn_group<{D}>(uint32_t lane4, const uint32_t (&in)[{D}],")
         print("                                                         uint32_t chw, uint32_t fbase, const uint32_t (&cb)[4],")
