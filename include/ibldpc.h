@@ -236,6 +236,62 @@ int ibl_float_timing(ibl_float* h, int32_t enable);
 int ibl_float_timing_read(ibl_float* h, double* cn_ms, int32_t* cn_launches, double* vn_ms, int32_t* vn_launches);
 
 /*
+ * Layered min-sum: layered (row-serial) normalised / offset min-sum decoding, fp32 (no reference counterpart:
+ * the reference's decoders are flooding decoders with uncorrected min-sum).
+ *
+ * Layers: an ordered list of disjoint sets of checks that together cover all checks; within one layer no
+ * variable appears in two checks.  layer_ptr[n_layers + 1] (layer_ptr[0] = 0) delimits the layers in
+ * layer_checks[n_c].  For a quasi-cyclic code the block rows are layers.  (Pointer for later: in a DVB-S2 code
+ * the q = (n - k) / 360 residue classes {r, r + q, r + 2q, ...} of the checks are valid layers — bit m of an
+ * information group meets check (x + m q) mod (n - k), one check of a class per address as long as a group has no
+ * two addresses of one residue, and a staircase parity variable joins checks j and j + 1, never two of a class.)
+ *
+ * Semantics, per codeword; every operation is one individually rounded fp32 operation (no FMA):
+ *   P[v] = channel LLR;  R[e] = 0 for every edge
+ *   for it = 1..imax:
+ *     for each layer in order, for each check c of the layer (any order):
+ *       for the edges e = (c, v) of c in ascending column order:
+ *           Q_e = clamp(P[v] - R[e], -llr_max, +llr_max);  neg_e = (Q_e < 0)
+ *       m1 = min |Q_e|, at the FIRST position attaining it;  m2 = min over the other positions;  s = XOR neg_e
+ *       for each e:  mag = (e is that first position) ? m2 : m1
+ *                    mag = max(alpha * mag - beta, 0)      (the product rounded, then the difference rounded)
+ *                    R[e] = (s ^ neg_e) ? -mag : mag;   P[v] = Q_e + R[e]
+ *     if early_stop: x = (P < 0); a codeword whose syndrome H x is zero for the first time now has
+ *                    out[:, b] = P[:, b], iters[b] = it, and is finished
+ *   codewords never finished: out[:, b] = P after imax iterations, iters[b] = imax
+ *   early_stop = 0: no syndrome, every codeword runs imax iterations, iters[b] = imax
+ * alpha = 1, beta = 0 is plain layered min-sum.  The early stop is PER CODEWORD (the flooding decoders above
+ * stop the whole batch together, as the reference does).
+ * Preconditions: channel LLRs finite; check degrees in [2, 16] (else IBL_EUNSUPPORTED).
+ *
+ * ibl_layers_validate  (host only, no device) checks cover, disjointness, no variable shared within a layer
+ *   (IBL_EINVAL) and the degree range (IBL_EUNSUPPORTED); ibl_last_error names the first offending check.
+ * ibl_layered_create   validates the layers, builds the device plan and allocates a [max_batch][N] fp32 staging
+ *   buffer.  alpha, beta >= 0, llr_max > 0 (the project's value: 150).  precision: IBL_F32; IBL_F64 returns
+ *   IBL_EUNSUPPORTED (fp64 and layered BP are not built).
+ *   Fit rule: the decoder is one fused on-chip kernel — one wave owns one codeword, whose APP LLRs (4 N bytes)
+ *   and compressed check state (12 bytes per check: corrected m1, m2, argmin position | sign bits) stay in LDS
+ *   through all iterations.  A workgroup holds cw_per_group = min(8, floor(160 KiB / (4 N + 12 n_c))) codewords;
+ *   IBL_EUNSUPPORTED when that is 0 (N = 1944 rate 1/2: 19,440 B, 8 codewords; DVB-S2 N = 64800: 648 KB, does
+ *   not fit).  A per-layer path over HBM for such long codes is deliberately not part of this interface yet.
+ * ibl_layered_decode   d_llr [N][B] IBL_F32 in, d_out [N][B] IBL_F32 APP LLRs out, d_iters [B] int32 (or NULL):
+ *   iterations run per codeword.  Asynchronous on `stream`, no host synchronisation.
+ * ibl_layered_geometry the launch geometry ibl_layered_decode uses for a batch of B: codewords per workgroup,
+ *   *ngroups = ceil(B / cw_per_group) groups of consecutive codewords, *grid = workgroups launched,
+ *   min(ngroups, blocks per CU x CUs) — workgroup w decodes groups w, w + grid, w + 2 grid, ...
+ */
+typedef struct ibl_layered ibl_layered;
+int ibl_layers_validate(int32_t n_v, int32_t n_c, const int32_t* csr_indptr, const int32_t* csr_cols,
+                        int32_t n_layers, const int32_t* layer_ptr, const int32_t* layer_checks);
+int ibl_layered_create(const ibl_graph* g, int32_t n_layers, const int32_t* layer_ptr, const int32_t* layer_checks,
+                       int32_t imax, float alpha, float beta, float llr_max, int32_t precision, int32_t max_batch,
+                       ibl_layered** out);
+int ibl_layered_decode(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out,
+                       int32_t out_dtype, int32_t early_stop, int32_t* d_iters, void* stream);
+int ibl_layered_geometry(const ibl_layered* h, int32_t B, int32_t* cw_per_group, int32_t* ngroups, int32_t* grid);
+void ibl_layered_destroy(ibl_layered* h);
+
+/*
  * Error counter.  Replaces return_errors_all_zero (discrete_LDPC_decoder_irreg.py:343-349,
  * discrete_LDPC_decoder.py:297-300, min_sum_decoder_irreg.py:290-295): counts entries
  * x[r][b] < threshold for r < rows, b < B (row stride ld) into the device int64 *d_count

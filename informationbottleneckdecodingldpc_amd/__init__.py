@@ -8,6 +8,10 @@ Drop-in for the decoder classes of mx-strk/InformationBottleneckDecodingLDPC:
     from informationbottleneckdecodingldpc_amd.min_sum_decoder_irreg import Min_Sum_Decoder_class_irregular
     from informationbottleneckdecodingldpc_amd.bp_decoder_irreg import BeliefPropagationDecoderClassIrregular
 
+plus a layered normalised / offset min-sum decoder the reference does not have:
+
+    from informationbottleneckdecodingldpc_amd import Min_Sum_Layered_Decoder_class_irregular
+
 and for the channel side / drivers:
 
     from informationbottleneckdecodingldpc_amd.awgn_quantizer import AWGN_Channel_Quantizer  # device sampling
@@ -19,6 +23,14 @@ Decoding runs only in the hand-written HIP kernels of ``libibldpc.so`` (gfx950);
 from . import codes, graph, tables, tables_io  # noqa: F401  (host-side set-up, importable without a GPU)
 
 __version__ = "0.2.0"
+
+
+def __getattr__(name):
+    # the layered min-sum class (no reference counterpart); imported on first use: it needs torch
+    if name == "Min_Sum_Layered_Decoder_class_irregular":
+        from .min_sum_layered_decoder_irreg import Min_Sum_Layered_Decoder_class_irregular
+        return Min_Sum_Layered_Decoder_class_irregular
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 
 def library_path() -> str:

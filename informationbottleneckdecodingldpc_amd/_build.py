@@ -11,7 +11,8 @@ ROOT = os.path.dirname(PKG)
 CSRC = os.path.join(PKG, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 LIB = os.path.join(PKG, "libibldpc.so")
-SOURCES = ["ib_kernels.hip", "float_kernels.hip", "channel_kernels.hip", "encoder_kernels.hip", "capi.hip", "comm.hip"]
+SOURCES = ["ib_kernels.hip", "float_kernels.hip", "channel_kernels.hip", "encoder_kernels.hip", "layered_kernels.hip",
+           "capi.hip", "comm.hip"]
 ARCH = os.environ.get("IBLDPC_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", INCLUDE, "-I", CSRC,
@@ -22,7 +23,11 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", INCLUDE, 
 # The IEEE-mode attribute differs from the device libraries', which then do not inline: the source
 # takes its work-item geometry from builtins (fl_tid ...), so only the fp64 box-plus's exp / log (the
 # strict-precision build) remain calls.
-SRC_FLAGS = {"float_kernels.hip": ["-fno-honor-nans", "-mno-amdgpu-ieee"]}
+# layered_kernels: the layered decoder's arithmetic is specified as individually rounded fp32 operations
+# (include/ibldpc.h "Layered min-sum"), and HIP device code contracts a * b + c into an FMA by default: no
+# contraction there. It takes none of float_kernels' flags.
+SRC_FLAGS = {"float_kernels.hip": ["-fno-honor-nans", "-mno-amdgpu-ieee"],
+             "layered_kernels.hip": ["-ffp-contract=off"]}
 
 
 def _stale(out: str, deps) -> bool:

@@ -43,6 +43,7 @@ EXPORTS = [
     "ibl_count_errors",
     "ibl_shard_range", "ibl_comm_unique_id", "ibl_comm_create", "ibl_comm_broadcast", "ibl_comm_allreduce_sum_i64",
     "ibl_comm_destroy",
+    "ibl_layers_validate", "ibl_layered_create", "ibl_layered_decode", "ibl_layered_geometry", "ibl_layered_destroy",
 ]
 IBL_COMM_ID_BYTES = 128
 
@@ -123,6 +124,13 @@ def load():
     L.ibl_comm_allreduce_sum_i64.argtypes = [_vp, _vp, _i64, _vp]
     L.ibl_comm_destroy.argtypes = [_vp]
     L.ibl_comm_destroy.restype = None
+    L.ibl_layers_validate.argtypes = [_i32, _i32, _i32p, _i32p, _i32, _i32p, _i32p]
+    _f32 = ctypes.c_float
+    L.ibl_layered_create.argtypes = [_vp, _i32, _i32p, _i32p, _i32, _f32, _f32, _f32, _i32, _i32, ctypes.POINTER(_vp)]
+    L.ibl_layered_decode.argtypes = [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]
+    L.ibl_layered_geometry.argtypes = [_vp, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i32)]
+    L.ibl_layered_destroy.argtypes = [_vp]
+    L.ibl_layered_destroy.restype = None
     for name in EXPORTS:
         getattr(L, name)
     _lib = L
@@ -162,3 +170,21 @@ def shard_range(total: int, rank: int, world: int):
     a, b = _i64(0), _i64(0)
     check(load().ibl_shard_range(int(total), int(rank), int(world), ctypes.byref(a), ctypes.byref(b)), "ibl_shard_range")
     return int(a.value), int(b.value)
+
+
+def pack_layers(layers):
+    """List of check-index sequences -> (n_layers, layer_ptr int32 [n_layers + 1], layer_checks int32)."""
+    layers = [np.asarray(l, dtype=np.int64).ravel() for l in layers]
+    ptr = np.zeros(len(layers) + 1, np.int32)
+    ptr[1:] = np.cumsum([l.size for l in layers])
+    chk = np.ascontiguousarray(np.concatenate(layers) if layers else np.zeros(0), dtype=np.int32)
+    return len(layers), ptr, chk
+
+
+def layers_validate(n_v: int, n_c: int, indptr: np.ndarray, cols: np.ndarray, layers) -> None:
+    """``ibl_layers_validate`` (host only, no device): raises :class:`IBLError` naming the first offending check."""
+    nl, ptr, chk = pack_layers(layers)
+    if chk.size == 0:
+        chk = np.zeros(1, np.int32)
+    check(load().ibl_layers_validate(int(n_v), int(n_c), np.ascontiguousarray(indptr, dtype=np.int32),
+                                     np.ascontiguousarray(cols, dtype=np.int32), nl, ptr, chk), "ibl_layers_validate")

@@ -43,6 +43,9 @@ __all__ = [
     "WLAN_R12_BASE_Z81",
     "regular_code",
     "dvbs2_structured",
+    "qc_layers",
+    "greedy_layers",
+    "validate_layers",
     "code_rate",
 ]
 
@@ -277,6 +280,63 @@ def dvbs2_structured(seed: int = 0, n: int = 64800, k: int = 32400,
     if H.nnz != rows.size:
         raise RuntimeError("duplicate edges in DVB-S2-structured construction")
     return H
+
+
+def qc_layers(H, Z: int):
+    """Layers of a quasi-cyclic code for layered decoding: the n_c / Z block rows of Z checks each (a block row's
+    circulants have one 1 per column, so its checks share no variable; :func:`validate_layers` checks that)."""
+    n_c = canonical_csr(H).shape[0]
+    Z = int(Z)
+    if Z < 1 or n_c % Z:
+        raise ValueError(f"the number of checks ({n_c}) is not a multiple of Z = {Z}")
+    return [np.arange(i * Z, (i + 1) * Z, dtype=np.int64) for i in range(n_c // Z)]
+
+
+def greedy_layers(H):
+    """Layers for any H: checks in row order, each put into the first layer none of whose checks shares a
+    variable with it (a new last layer if there is none)."""
+    A = canonical_csr(H)
+    layers, used = [], []          # per layer: its checks, the set of its checks' variables
+    for c in range(A.shape[0]):
+        vs = A.indices[A.indptr[c]:A.indptr[c + 1]].tolist()
+        for l, u in enumerate(used):
+            if u.isdisjoint(vs):
+                layers[l].append(c)
+                u.update(vs)
+                break
+        else:
+            layers.append([c])
+            used.append(set(vs))
+    return [np.asarray(l, dtype=np.int64) for l in layers]
+
+
+def validate_layers(H, layers) -> None:
+    """Raise ``ValueError`` unless ``layers`` (sequences of check indices) are disjoint, cover every check of H,
+    hold no two checks sharing a variable within one layer, and every check has degree 2..16 (what the layered
+    decoder supports). The message names the first offending check."""
+    A = canonical_csr(H)
+    n_c, n_v = A.shape
+    layer_of = np.full(n_c, -1, dtype=np.int64)
+    for l, layer in enumerate(layers):
+        owner = {}
+        for c in np.asarray(layer, dtype=np.int64).ravel().tolist():
+            if c < 0 or c >= n_c:
+                raise ValueError(f"layer {l} names check {c} out of range")
+            if layer_of[c] >= 0:
+                raise ValueError(f"check {c} is listed twice (layers {layer_of[c]} and {l})")
+            layer_of[c] = l
+        for c in np.asarray(layer, dtype=np.int64).ravel().tolist():
+            for v in A.indices[A.indptr[c]:A.indptr[c + 1]].tolist():
+                if owner.setdefault(v, c) != c:
+                    raise ValueError(f"checks {owner[v]} and {c} of layer {l} share variable {v}")
+    missing = np.nonzero(layer_of < 0)[0]
+    if missing.size:
+        raise ValueError(f"check {int(missing[0])} is in no layer")
+    deg = np.diff(A.indptr)
+    bad = np.nonzero((deg < 2) | (deg > 16))[0]
+    if bad.size:
+        raise ValueError(f"check {int(bad[0])} has degree {int(deg[bad[0]])}: layered decoding supports check "
+                         "degrees 2..16")
 
 
 def code_rate(H) -> float:

@@ -20,6 +20,7 @@
 
 #include "common.h"
 #include "ibldpc.h"
+#include "layered_plan.h"
 
 using namespace ibl;
 
@@ -1685,6 +1686,142 @@ int ibl_count_below(const void* d_x, int32_t dtype, int64_t rows, int32_t B, int
   if (rows == 0 || B == 0) return IBL_OK;
   HIPCHK(launch_count_below(d_x, dtype, rows, B, ld, threshold, reinterpret_cast<unsigned long long*>(d_count), s));
   return IBL_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------ layered min-sum (layered_kernels.hip)
+struct ibl_layered {
+  const ibl_graph* g = nullptr;
+  int32_t imax = 0, max_batch = 0, n_tasks = 0, cw_per_group = 0, bpc = 1;
+  float alpha = 1.f, beta = 0.f, llr_max = 150.f;
+  size_t cw_bytes = 0;
+  int32_t *task = nullptr, *idx = nullptr;
+  float* buf = nullptr;     // [max_batch][n_v] codeword rows
+};
+
+namespace {
+std::vector<int32_t> graph_indptr(const ibl_graph* g) {
+  std::vector<int32_t> ip((size_t)g->n_c + 1, 0);
+  for (int32_t c = 0; c < g->n_c; ++c) ip[(size_t)c + 1] = ip[c] + g->h_cn_deg[c];
+  return ip;
+}
+void layered_geometry(const ibl_layered* h, int B, int32_t* ngroups, int32_t* grid) {
+  *ngroups = (B + h->cw_per_group - 1) / h->cw_per_group;
+  *grid = std::min(*ngroups, h->bpc * h->g->num_cus);
+}
+}  // namespace
+
+extern "C" {
+
+int ibl_layers_validate(int32_t n_v, int32_t n_c, const int32_t* indptr, const int32_t* cols, int32_t n_layers,
+                        const int32_t* layer_ptr, const int32_t* layer_checks) {
+  std::string err;
+  const int rc = validate_layers(n_v, n_c, indptr, cols, n_layers, layer_ptr, layer_checks, &err);
+  if (rc) return fail(rc == -2 ? IBL_EUNSUPPORTED : IBL_EINVAL, err);
+  return IBL_OK;
+}
+
+int ibl_layered_create(const ibl_graph* g, int32_t n_layers, const int32_t* layer_ptr, const int32_t* layer_checks,
+                       int32_t imax, float alpha, float beta, float llr_max, int32_t precision, int32_t max_batch,
+                       ibl_layered** out) {
+  if (!out) return fail(IBL_EINVAL, "out is NULL");
+  *out = nullptr;
+  if (!g) return fail(IBL_EINVAL, "graph is NULL");
+  if (precision == kF64) return fail(IBL_EUNSUPPORTED, "the layered decoder is fp32 only (fp64 is not built)");
+  if (precision != kF32) return fail(IBL_EINVAL, "precision must be IBL_F32");
+  if (imax < 1 || max_batch < 1) return fail(IBL_EINVAL, "imax and max_batch must be >= 1");
+  if (!(alpha >= 0.f) || !(beta >= 0.f) || !(llr_max > 0.f) || std::isinf(alpha) || std::isinf(beta))
+    return fail(IBL_EINVAL, "alpha and beta must be finite and >= 0, llr_max > 0");
+  const std::vector<int32_t> ip = graph_indptr(g);
+  int rc = ibl_layers_validate(g->n_v, g->n_c, ip.data(), g->h_cols.data(), n_layers, layer_ptr, layer_checks);
+  if (rc) return rc;
+  LayeredPlan pl;
+  plan_layered(g->n_v, g->n_c, ip.data(), g->h_cols.data(), n_layers, layer_ptr, layer_checks, &pl);
+  if (pl.cw_per_group < 1)
+    return fail(IBL_EUNSUPPORTED, "code does not fit the layered kernel: one codeword needs 4 N + 12 n_c = " +
+                                      std::to_string(pl.cw_bytes) + " bytes of LDS, a workgroup has " +
+                                      std::to_string(kLayLds));
+  HIPCHK(hipSetDevice(g->device));
+  auto* h = new ibl_layered();
+  h->g = g; h->imax = imax; h->max_batch = max_batch; h->alpha = alpha; h->beta = beta; h->llr_max = llr_max;
+  h->n_tasks = pl.n_tasks; h->cw_per_group = pl.cw_per_group; h->cw_bytes = pl.cw_bytes;
+  auto bail = [&](int r) { ibl_layered_destroy(h); return r; };
+  if ((rc = dupload(&h->task, pl.task.data(), pl.task.size())) || (rc = dupload(&h->idx, pl.idx.data(), pl.idx.size())) ||
+      (rc = dalloc(&h->buf, (size_t)max_batch * (size_t)g->n_v)))
+    return bail(rc);
+  int bpc = 0;
+  size_t priv = 0;
+  const hipError_t e = lay_fused_occupancy(h->cw_per_group, (size_t)h->cw_per_group * h->cw_bytes, &bpc, &priv);
+  if (e != hipSuccess) return bail(fail(IBL_EHIP, std::string("layered kernel occupancy: ") + hipGetErrorString(e)));
+  if (bpc < 1) return bail(fail(IBL_EHIP, "no occupancy for the layered kernel"));
+  if (priv != 0)   // same guard as the other fused kernels: built to run without scratch
+    return bail(fail(IBL_EHIP, "layered kernel has a " + std::to_string(priv) +
+                                   "-byte private segment (register spill): rebuild required"));
+  h->bpc = bpc;
+  *out = h;
+  return IBL_OK;
+}
+
+int ibl_layered_geometry(const ibl_layered* h, int32_t B, int32_t* cw_per_group, int32_t* ngroups, int32_t* grid) {
+  if (!h || !cw_per_group || !ngroups || !grid) return fail(IBL_EINVAL, "NULL argument");
+  if (B < 1 || B > h->max_batch) return fail(IBL_EINVAL, "B must lie in [1, max_batch]");
+  *cw_per_group = h->cw_per_group;
+  layered_geometry(h, B, ngroups, grid);
+  return IBL_OK;
+}
+
+int ibl_layered_decode(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out,
+                       int32_t out_dtype, int32_t early_stop, int32_t* d_iters, void* stream) {
+  if (!h) return fail(IBL_EINVAL, "decoder is NULL");
+  if (B < 1 || B > h->max_batch) return fail(IBL_EINVAL, "B must lie in [1, max_batch]");
+  if (llr_dtype == kF64 || out_dtype == kF64) return fail(IBL_EUNSUPPORTED, "the layered decoder is fp32 only");
+  if (llr_dtype != kF32 || out_dtype != kF32) return fail(IBL_EINVAL, "LLR dtypes must be IBL_F32");
+  if (!d_llr || !d_out) return fail(IBL_EINVAL, "NULL buffer");
+  const ibl_graph* g = h->g;
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(hipSetDevice(g->device));
+  HIPCHK(launch_lay_transpose(static_cast<const float*>(d_llr), h->buf, g->n_v, B, s));
+  LayeredArgs a{};
+  a.buf = h->buf; a.task = h->task; a.idx = h->idx; a.iters = d_iters;
+  a.alpha = h->alpha; a.beta = h->beta; a.llr_max = h->llr_max;
+  a.n_v = g->n_v; a.n_c = g->n_c; a.n_tasks = h->n_tasks; a.B = B; a.imax = h->imax;
+  a.early = early_stop ? 1 : 0;
+  a.cw_per_group = h->cw_per_group; a.cw_bytes = (int32_t)h->cw_bytes;
+  int32_t grid = 0;
+  layered_geometry(h, B, &a.ngroups, &grid);
+#if IBL_DIAG
+  // diagnostic builds only: IBL_TRACE_LAYERED=<file> records workgroup 0 / wave 0's clocks at every task of its
+  // first codeword's second iteration (with -DIBL_LAY_TRACE=1 kernels, tools/variants.py laytrace)
+  const char* ltrace = getenv("IBL_TRACE_LAYERED");
+  const size_t ntr = (size_t)3 * h->n_tasks;
+  if (ltrace) {
+    HIPCHK(hipMalloc((void**)&a.trace, sizeof(uint64_t) * ntr));
+    HIPCHK(hipMemsetAsync(a.trace, 0, sizeof(uint64_t) * ntr, s));
+  }
+#endif
+  HIPCHK(launch_lay_fused(a, grid, (size_t)h->cw_per_group * h->cw_bytes, s));
+#if IBL_DIAG
+  if (ltrace) {
+    std::vector<uint64_t> hv(ntr);
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpy(hv.data(), a.trace, sizeof(uint64_t) * ntr, hipMemcpyDeviceToHost));
+    (void)hipFree(a.trace);
+    if (FILE* fp = fopen(ltrace, "wb")) {
+      fwrite(hv.data(), sizeof(uint64_t), ntr, fp);
+      fclose(fp);
+    }
+  }
+#endif
+  HIPCHK(launch_lay_transpose(h->buf, static_cast<float*>(d_out), B, g->n_v, s));
+  return IBL_OK;
+}
+
+void ibl_layered_destroy(ibl_layered* h) {
+  if (!h) return;
+  (void)hipSetDevice(h->g->device);
+  dfree(h->task); dfree(h->idx); dfree(h->buf);
+  delete h;
 }
 
 }  // extern "C"

@@ -353,4 +353,20 @@ hipError_t launch_fl_fused(const FlFusedArgs& a, int kind, int prec, int cmax, i
                            hipStream_t s);
 hipError_t fl_fused_occupancy(int kind, int prec, int cmax, int vmax, size_t lds, int* blocks_per_cu, int* block);
 
+// ------------------------------------------------------------ layered min-sum (layered_kernels.hip)
+// One wave per codeword, cw_per_group waves per workgroup; the plan's arrays as in layered_plan.h.
+struct LayeredArgs {
+  float* buf;               // [B][n_v] codeword rows: channel LLRs in, APP LLRs out (in place)
+  const int32_t* task;      // per task {first idx, count, degree, first state slot}
+  const int32_t* idx;       // variable of edge k of lane i of a task at [first + 64 k + i]
+  int32_t* iters;           // [B] iterations run per codeword, or nullptr
+  float alpha, beta, llr_max;
+  int32_t n_v, n_c, n_tasks, B, imax, early, ngroups, cw_per_group, cw_bytes;
+  uint64_t* trace;          // diagnostics (IBL_TRACE_LAYERED, -DIBL_LAY_TRACE=1 builds): 3 clocks per task, else nullptr
+};
+hipError_t lay_fused_occupancy(int cw_per_group, size_t lds, int* blocks_per_cu, size_t* private_bytes);
+hipError_t launch_lay_fused(const LayeredArgs& a, int grid, size_t lds, hipStream_t s);
+// dst[c][r] = src[r][c], fp32
+hipError_t launch_lay_transpose(const float* src, float* dst, int rows, int cols, hipStream_t s);
+
 }  // namespace ibl

@@ -286,6 +286,76 @@ class FloatDecoder:
             self._h = None
 
 
+class LayeredDecoder:
+    """Layered (row-serial) normalised / offset min-sum decoder, fp32 (``ibl_layered``; semantics in
+    include/ibldpc.h "Layered min-sum"). ``layers``: ordered sequences of check indices (``codes.qc_layers``,
+    ``codes.greedy_layers``). ``alpha`` scales and ``beta`` offsets the check magnitudes (1, 0: plain layered
+    min-sum). The early stop is per codeword; ``decode(..., iters=)`` receives each codeword's iteration count.
+    Raises :class:`_lib.IBLError` (``IBL_EUNSUPPORTED``) when a codeword does not fit in LDS or ``precision``
+    is not float32."""
+
+    def __init__(self, graph: Graph, layers, imax: int, max_batch: int, alpha: float = 1.0, beta: float = 0.0,
+                 llr_max: float = 150.0, precision=torch.float32):
+        self.graph = graph
+        self.imax = int(imax)
+        self.max_batch = int(max_batch)
+        self.alpha, self.beta, self.llr_max = float(alpha), float(beta), float(llr_max)
+        self.device = graph.device
+        if precision not in _DT_FL:
+            raise ValueError("precision must be torch.float32 (float64 is refused by the library)")
+        nl, ptr, chk = _lib.pack_layers(layers)
+        if chk.size == 0:
+            chk = np.zeros(1, np.int32)
+        self.n_layers = nl
+        h = ctypes.c_void_p()
+        _lib.check(_lib.load().ibl_layered_create(graph.handle, nl, ptr, chk, self.imax, self.alpha, self.beta,
+                                                  self.llr_max, _DT_FL[precision], self.max_batch, ctypes.byref(h)),
+                   "ibl_layered_create")
+        self._h = h
+
+    def geometry(self, B: int):
+        """``(cw_per_group, ngroups, grid)`` a batch of ``B`` is decoded with (``ibl_layered_geometry``): a
+        workgroup decodes ``cw_per_group`` consecutive codewords at a time, workgroup w the groups w, w + grid, ..."""
+        c, n, g = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(_lib.load().ibl_layered_geometry(self._h, int(B), ctypes.byref(c), ctypes.byref(n),
+                                                    ctypes.byref(g)), "ibl_layered_geometry")
+        return int(c.value), int(n.value), int(g.value)
+
+    def decode(self, llr: torch.Tensor, out: Optional[torch.Tensor] = None, early_stop: bool = True,
+               iters: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``llr`` [N][B] float32 on the decoder's device -> APP LLRs [N][B] float32; ``iters``: int32 [B] device
+        tensor receiving the iterations each codeword ran."""
+        n = self.graph.edges.n_v
+        _check_tensor(llr, self.device, n, "channel LLRs")
+        if llr.dtype != torch.float32:
+            raise ValueError("channel LLRs must be float32")
+        B = llr.shape[1]
+        if out is None:
+            out = torch.empty((n, B), dtype=torch.float32, device=self.device)
+        _check_tensor(out, self.device, n, "output")
+        if out.dtype != torch.float32 or out.shape[1] != B:
+            raise ValueError("output must be float32 [N][B]")
+        it_ptr = None
+        if iters is not None:
+            if iters.dtype != torch.int32 or iters.device != self.device or iters.numel() < B \
+                    or not iters.is_contiguous():
+                raise ValueError("iters must be a contiguous int32 device tensor of at least B entries")
+            it_ptr = iters.data_ptr()
+        _lib.check(_lib.load().ibl_layered_decode(self._h, llr.data_ptr(), _lib.IBL_F32, B, out.data_ptr(),
+                                                  _lib.IBL_F32, int(bool(early_stop)), it_ptr,
+                                                  _stream_ptr(self.device)), "ibl_layered_decode")
+        return out
+
+    def __del__(self):
+        h = getattr(self, "_h", None)
+        if h is not None and h.value:
+            try:
+                _lib.load().ibl_layered_destroy(h)
+            except Exception:  # interpreter shutdown
+                pass
+            self._h = None
+
+
 def count_below(x: torch.Tensor, rows: int, threshold: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Device count of ``x[:rows] < threshold`` (the reference's error counters) -> int64 tensor."""
     if x.dim() != 2 or not x.is_contiguous() or x.device.type != "cuda":

@@ -1,0 +1,80 @@
+"""Layered normalised / offset min-sum LDPC decoder with the interface of the float min-sum class
+(:mod:`.min_sum_decoder_irreg`), running on the fused MI355X HIP kernel (``ibl_layered_*``).
+
+The reference has no layered decoder; this class keeps ``Min_Sum_Decoder_class_irregular``'s constructor shape
+and method names so the same drivers (``ber.run_ber``) take it. Keyword-only extensions:
+
+* ``layers`` — ordered sequences of check indices; or ``Z`` — the lifting size of a quasi-cyclic code, whose
+  block rows become the layers (``codes.qc_layers``); neither: ``codes.greedy_layers``;
+* ``alpha``, ``beta`` — normalisation factor and offset of the check magnitudes, max(alpha * m - beta, 0).
+
+fp32 only. The early stop is per codeword; ``last_iterations`` holds the int32 device tensor of the last
+decode's iteration counts.
+"""
+from __future__ import annotations
+
+import numpy as np
+import torch
+
+from . import codes
+from ._dropin import CodeMixin, resolve_device, to_device_input
+from .engine import LayeredDecoder, count_below
+
+
+class Min_Sum_Layered_Decoder_class_irregular(CodeMixin):
+
+    def __init__(self, filename, imax_, cardinality_T_channel_, msg_at_time_, *, layers=None, Z=None,
+                 alpha: float = 1.0, beta: float = 0.0, llr_max: float = 150.0):
+        self._init_code(filename)
+        self.imax = int(imax_)
+        self.cardinality_T_channel = int(cardinality_T_channel_)
+        self.set_code_parameters()
+        self.data_len = int(self.R_c * self.codeword_len)
+        self.msg_at_time = int(msg_at_time_)
+        self.map_node_connections()
+        if layers is not None and Z is not None:
+            raise ValueError("give layers or Z, not both")
+        if layers is None:
+            layers = codes.qc_layers(self.H_sparse, Z) if Z is not None else codes.greedy_layers(self.H_sparse)
+        self.layers = [np.asarray(l, dtype=np.int64) for l in layers]
+        codes.validate_layers(self.H_sparse, self.layers)
+        self.alpha, self.beta, self.llr_max = float(alpha), float(beta), float(llr_max)
+        self.precision = torch.float32
+        self.last_iterations = None
+        self._dec = None
+        self.device = None
+
+    def init_OpenCL_decoding(self, msg_at_time_, context_=False):
+        dev = resolve_device(context_)
+        self.device = dev
+        self.context = dev
+        self.msg_at_time = int(msg_at_time_)
+        self._dec = LayeredDecoder(self._graph_on(dev), self.layers, self.imax, self.msg_at_time, alpha=self.alpha,
+                                   beta=self.beta, llr_max=self.llr_max)
+
+    def _decode(self, received_blocks, buffer_in, return_buffer, early_stop=True):
+        if self._dec is None:
+            self.init_OpenCL_decoding(self.msg_at_time)
+        llr = to_device_input(received_blocks, buffer_in, self.device, (torch.float32,))
+        if llr.shape[1] > self._dec.max_batch:
+            self.init_OpenCL_decoding(llr.shape[1], self.device)
+        if not return_buffer and not bool(torch.isfinite(llr).all().item()):
+            # host output synchronises anyway: the decoder's precondition is checked instead of returning
+            # unspecified values
+            raise ValueError("channel LLRs must be finite (layered min-sum precondition)")
+        iters = torch.empty(llr.shape[1], dtype=torch.int32, device=self.device)
+        out = self._dec.decode(llr, early_stop=early_stop, iters=iters)
+        self.last_iterations = iters
+        if return_buffer:
+            return out
+        return out.cpu().numpy()
+
+    def decode_OpenCL_min_sum(self, received_blocks, buffer_in=False, return_buffer=False):
+        return self._decode(received_blocks, buffer_in, return_buffer)
+
+    def return_errors_all_zero(self, varnode_output_buffer):
+        """Count of negative APP LLRs in the first data_len rows, as a float."""
+        buf = varnode_output_buffer
+        if not isinstance(buf, torch.Tensor):
+            buf = torch.from_numpy(np.ascontiguousarray(buf, dtype=np.float32)).to(self.device)
+        return float(count_below(buf.contiguous(), self.data_len, 0.0).item())

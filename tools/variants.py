@@ -59,6 +59,8 @@ VARIANTS = {
     "contig0": ["IBL_SMALL_CONTIG=0"],
     # fused IB kernel phase trace (IBL_TRACE_FUSED=<file>)
     "ftrace": ["IBL_FUSED_TRACE=1", "IBL_DIAG=1"],
+    # layered min-sum kernel task trace (IBL_TRACE_LAYERED=<file>; tools/trace_layered.py)
+    "laytrace": ["IBL_LAY_TRACE=1", "IBL_DIAG=1"],
     # timing-only host hooks (IBL_VN_PART, IBL_TRACE_WAVES, IBL_DEBUG_SYNC): not in the product build
     "diag": ["IBL_DIAG=1"],
     # column fetches (tools/gen_sched.py "Column fetches"; the schedule file is generated on demand).
