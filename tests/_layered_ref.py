@@ -6,8 +6,10 @@ import numpy as np
 import scipy.sparse as sp
 
 
-def layered_decode(H, layers, llr, imax, alpha=1.0, beta=0.0, llr_max=150.0, early_stop=True):
-    """-> (out [N][B] float32, iters [B] int32)."""
+def layered_decode(H, layers, llr, imax, alpha=1.0, beta=0.0, llr_max=150.0, early_stop=True, hook=None):
+    """-> (out [N][B] float32, iters [B] int32). `hook` (tests/_layered_census.py) observes every update of the
+    checks of one degree of a layer and changes nothing: hook(it, checks [n], D = P - R before the clamp, Q, pos,
+    m1, m2, mag, R_new (all [n][d][B] or [n][B]), done [B])."""
     A = sp.csr_matrix(H)
     A.sort_indices()
     indptr, cols = A.indptr.astype(np.int64), A.indices.astype(np.int64)
@@ -24,13 +26,14 @@ def layered_decode(H, layers, llr, imax, alpha=1.0, beta=0.0, llr_max=150.0, ear
         for d in np.unique(deg[layer]):
             cs = layer[deg[layer] == d]
             e = indptr[cs][:, None] + np.arange(d)[None, :]
-            groups.append((e, cols[e]))
+            groups.append((cs, e, cols[e]))
     out = np.empty_like(P)
     iters = np.full(B, imax, dtype=np.int32)
     done = np.zeros(B, dtype=bool)
     for it in range(1, imax + 1):
-        for e, v in groups:
-            Q = np.clip(P[v] - R[e], -L, L)                       # [checks][d][B]
+        for cs, e, v in groups:
+            D = P[v] - R[e]
+            Q = np.clip(D, -L, L)                                 # [checks][d][B]
             neg = Q < 0
             a = np.abs(Q)
             pos = np.argmin(a, axis=1)                            # first position attaining the minimum
@@ -45,6 +48,8 @@ def layered_decode(H, layers, llr, imax, alpha=1.0, beta=0.0, llr_max=150.0, ear
             Rn = np.where(s[:, None, :] ^ neg, -mag, mag).astype(f32)
             R[e] = Rn
             P[v] = Q + Rn
+            if hook is not None:
+                hook(it, cs, D, Q, pos, m1, m2, mag, Rn, done)
         if early_stop:
             x = (P < 0).astype(np.int32)
             ok = ((A @ x) % 2 == 0).all(axis=0) & ~done

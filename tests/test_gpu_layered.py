@@ -1,8 +1,8 @@
 """GPU: the layered normalised / offset min-sum decoder (ibl_layered_*, csrc/layered_kernels.hip) against the
 numpy float32 restatement of its specification (tests/_layered_ref.py): outputs equal as values
-(np.array_equal: -0.0 equals +0.0) and per-codeword iteration counts exactly."""
-import functools
-
+(np.array_equal: -0.0 equals +0.0) and per-codeword iteration counts exactly. Continuous AWGN LLRs never tie,
+cancel, saturate or go subnormal: the input families of tests/_layered_census.py do (tests/test_cpu_layered.py
+holds them to it), and the reference itself is pinned there by an independent scalar restatement."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -10,24 +10,11 @@ import torch
 
 from informationbottleneckdecodingldpc_amd import _lib, codes
 from tests._codes import mixed_code
+from tests._layered_census import (AB, FAMILIES, FAMILY_B, FAMILY_IMAX, MIXED_BATCH_COLUMNS, awgn_llr, mixed,
+                                   mixed_batch_llr, quantised_llr, wlan)
 from tests._layered_ref import layered_decode
 
 pytestmark = pytest.mark.gpu
-
-AB = [(1.0, 0.0), (0.75, 0.0), (1.0, 0.5), (0.8125, 0.25)]
-
-
-@functools.lru_cache(maxsize=None)
-def wlan(Z):
-    H = codes.wlan_80211n(Z)
-    return H, codes.qc_layers(H, Z)
-
-
-def awgn_llr(n, B, ebn0_dB, seed, R=0.5):
-    """LLRs of the all-zero codeword (BPSK +1) over AWGN: sigma^2 = 1 / (2 R 10^(Eb/N0 / 10)), LLR = 2 y / sigma^2."""
-    s2 = 1.0 / (2.0 * R * 10 ** (ebn0_dB / 10))
-    y = 1.0 + np.sqrt(s2) * np.random.default_rng(seed).standard_normal((n, B))
-    return (2.0 * y / s2).astype(np.float32)
 
 
 @pytest.fixture(scope="module")
@@ -42,12 +29,12 @@ def gpu_decode(dec, llr, early):
     return out.cpu().numpy(), it.cpu().numpy()
 
 
-def check(dec, H, layers, llr, imax, a, b, early, ref=None, cols=None):
-    """Decode on the GPU, compare (the columns `cols` of) out and iters with the reference."""
+def check(dec, H, layers, llr, imax, a, b, early, ref=None, cols=None, llr_max=150.0):
+    """Decode on the GPU, compare (the columns `cols` of) out and iters with the reference; -> the GPU's."""
     out, it = gpu_decode(dec, llr, early)
     if ref is None:
         sel = llr if cols is None else llr[:, cols]
-        ref = layered_decode(H, layers, sel, imax, a, b, early_stop=early)
+        ref = layered_decode(H, layers, sel, imax, a, b, llr_max, early_stop=early)
     if cols is not None:
         out, it = out[:, cols], it[cols]
     r_out, r_it = ref
@@ -55,6 +42,7 @@ def check(dec, H, layers, llr, imax, a, b, early, ref=None, cols=None):
           f"iters equal {np.array_equal(it, r_it)}, out mismatches {int((out != r_out).sum())}")
     assert np.array_equal(it, r_it)
     assert np.array_equal(out, r_out)
+    return out, it
 
 
 @pytest.mark.parametrize("ab", AB)
@@ -192,3 +180,118 @@ def test_drop_in_class_and_ber_driver():
         want += int((layered_decode(H, layers, ch, 8, 0.75, 0.0)[0][:dec.data_len] < 0).sum())
     print("BER point: errors", r.errors[0], "reference", want)
     assert want > 0 and r.errors[0] == float(want)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# arithmetic edges: ties, zeros of either sign, the clamp and llr_max, subnormals (tests/_layered_census.py)
+# ---------------------------------------------------------------------------------------------------------------
+def edge_code(name):
+    return mixed() if name == "mixed" else wlan(27)
+
+
+@pytest.mark.parametrize("family", list(FAMILIES))
+@pytest.mark.parametrize("code", ["mixed", "wlan27"])
+def test_edge_families(engine, code, family):
+    """quantised: integers with +-0.0 entries (m1 == m2, Q == 0, R = -0 on Q == 0; the sign-bit arithmetic and
+    the running two minima), all four (alpha, beta). saturating: the clamp at +-150, +-FLT_MAX. small_llr_max:
+    llr_max = 7.5 through the constructor. subnormal: LLRs below 2^-126 and across it, beta = 0 and 2^-140
+    (every operation keeps subnormals, as numpy does). B = 16, 6 iterations, early stop on and off."""
+    H, layers = edge_code(code)
+    G = engine.Graph(H, "cuda:0")
+    gen, params = FAMILIES[family]
+    llr = gen(H, FAMILY_B)
+    for a, b, L in params:
+        dec = engine.LayeredDecoder(G, layers, FAMILY_IMAX, FAMILY_B, alpha=a, beta=b, llr_max=L)
+        for early in (True, False):
+            check(dec, H, layers, llr, FAMILY_IMAX, a, b, early, llr_max=L)
+
+
+@pytest.mark.parametrize("code", ["mixed", "wlan27"])
+def test_mixed_batch(engine, code):
+    """Neighbouring columns from different families, three more than a workgroup's codewords: the waves of one
+    workgroup do unlike things and stop at unlike times. The all-zero columns (+0.0, -0.0) stop after one
+    iteration with an all-zero output."""
+    H, layers = edge_code(code)
+    G = engine.Graph(H, "cuda:0")
+    col = {k: i for i, k in enumerate(MIXED_BATCH_COLUMNS)}
+    for a, b in AB:
+        dec = engine.LayeredDecoder(G, layers, FAMILY_IMAX, 16, alpha=a, beta=b)
+        B = dec.geometry(1)[0] + 3
+        assert len(MIXED_BATCH_COLUMNS) <= B <= 16 and dec.geometry(B)[1] == 2
+        llr = mixed_batch_llr(H.shape[1], B, seed=31)
+        for early in (True, False):
+            out, it = check(dec, H, layers, llr, FAMILY_IMAX, a, b, early)
+            for z in (col["zeros"], col["negative_zeros"]):
+                assert it[z] == (1 if early else FAMILY_IMAX) and (out[:, z] == 0).all()
+            assert not early or len(set(it.tolist())) >= 2
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# API and layout (Z = 27, quantised input)
+# ---------------------------------------------------------------------------------------------------------------
+QAB = (0.8125, 0.25)
+
+
+@pytest.mark.parametrize("Z,widths", [(27, (63, 64, 65, 129)), (81, (65,))])
+def test_transposition_tiles(engine, Z, widths):
+    """lay_transpose through full and ragged 64 x 64 tiles in both directions: N = 648 is 10 tiles and 8 rows,
+    N = 1944 30 tiles and 24 rows; B one less than, equal to, one more than a tile and two tiles and one column.
+    1 and 3 iterations."""
+    H, layers = wlan(Z)
+    G = engine.Graph(H, "cuda:0")
+    a, b = QAB
+    llr = quantised_llr(H.shape[1], max(widths), seed=60 + Z)
+    for imax in (1, 3):
+        dec = engine.LayeredDecoder(G, layers, imax, max(widths), alpha=a, beta=b)
+        for early in (True, False):
+            ref = layered_decode(H, layers, llr, imax, a, b, early_stop=early)   # codewords decode independently
+            for B in widths:
+                check(dec, H, layers, llr[:, :B], imax, a, b, early, ref=(ref[0][:, :B], ref[1][:B]))
+
+
+@pytest.fixture(scope="module")
+def z27(engine):
+    """One decoder of max_batch 129 on Z = 27 and a quantised batch with its reference (early stop, 6 iterations)."""
+    H, layers = wlan(27)
+    a, b = QAB
+    dec = engine.LayeredDecoder(engine.Graph(H, "cuda:0"), layers, FAMILY_IMAX, 129, alpha=a, beta=b)
+    llr = quantised_llr(H.shape[1], FAMILY_B, seed=70)
+    return dec, H, layers, llr, layered_decode(H, layers, llr, FAMILY_IMAX, a, b)
+
+
+def test_descending_reuse(z27):
+    """One decoder decodes B = 129, then 5, then 1 (unlike inputs): stale rows of the staging buffer do not leak."""
+    dec, H, layers, _, _ = z27
+    for B, seed in ((129, 71), (5, 72), (1, 73)):
+        check(dec, H, layers, quantised_llr(H.shape[1], B, seed=seed), FAMILY_IMAX, *QAB, True)
+
+
+def test_in_place_and_no_iters(z27):
+    dec, H, layers, llr, ref = z27
+    t = torch.from_numpy(llr).to(dec.device)
+    out = dec.decode(t.clone(), iters=None)                    # no iters tensor
+    assert np.array_equal(out.cpu().numpy(), ref[0])
+    it = torch.full((llr.shape[1],), -1, dtype=torch.int32, device=dec.device)
+    same = dec.decode(t, out=t, iters=it)                      # in place
+    assert same is t
+    assert np.array_equal(t.cpu().numpy(), ref[0]) and np.array_equal(it.cpu().numpy(), ref[1])
+
+
+def test_side_stream(z27):
+    dec, H, layers, llr, ref = z27
+    t = torch.from_numpy(llr).to(dec.device)
+    it = torch.full((llr.shape[1],), -1, dtype=torch.int32, device=dec.device)
+    torch.cuda.synchronize(dec.device)
+    side = torch.cuda.Stream(device=dec.device)
+    with torch.cuda.stream(side):
+        out = dec.decode(t, iters=it)
+    side.synchronize()
+    assert np.array_equal(out.cpu().numpy(), ref[0]) and np.array_equal(it.cpu().numpy(), ref[1])
+
+
+def test_batch_too_large(z27):
+    dec, H, _, _, _ = z27
+    t = torch.zeros((H.shape[1], dec.max_batch + 1), dtype=torch.float32, device=dec.device)
+    with pytest.raises(_lib.IBLError) as e:
+        dec.decode(t)
+    assert f"rc={_lib.IBL_EINVAL}" in str(e.value)
