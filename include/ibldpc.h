@@ -144,6 +144,13 @@ int ibl_ib_fused_ncw(const ibl_ib* h, int32_t B, int32_t* ncw);
  *               0: run exactly imax iterations (benchmark / decode_on_host behaviour)
  *   d_iters     optional device int32 receiving the iteration index used for the output
  *               (the reference's i_num - 1), NULL to skip
+ * Buffers: d_ch and d_out are contiguous and need only their element type's alignment (1 byte for
+ * IBL_U8, 4 for IBL_I32) — the kernels take their vector loads and stores only where the pointer and B
+ * allow them, and write nothing outside the [N][B] elements of d_out.  d_out may be d_ch itself when
+ * both have the same dtype (the channel is staged into the decoder's own buffers before any output is
+ * written); buffers that overlap in any other way are not supported.  All work is enqueued on `stream`;
+ * a decoder serves one decode at a time (successive decodes of one handle belong on one stream, or are
+ * ordered by the caller).
  */
 int ibl_ib_decode(ibl_ib* h, const void* d_ch, int32_t ch_dtype, int32_t B, void* d_out, int32_t out_dtype,
                   int32_t early_stop, int32_t* d_iters, void* stream);
@@ -180,6 +187,18 @@ int ibl_float_create(const ibl_graph* g, int32_t kind, int32_t imax, double llr_
  * numerator or vanishing denominator gives +-inf, clamped to +-llr_max as in the reference — and the fp32
  * decoder (an overflow-free form of the same function) needs finite values.  The float kernels take min /
  * max / median as single instructions that assume non-NaN operands: a NaN input gives unspecified outputs.
+ * Dtypes: llr_dtype and out_dtype are independent of the decoder's precision.  A channel LLR of the other
+ * dtype is converted to the decoder's precision once, when it is staged: IBL_F32 -> fp64 exactly,
+ * IBL_F64 -> fp32 by round-to-nearest-even (a finite value beyond FLT_MAX becomes +-inf, and it is the
+ * staged value the precondition above applies to for the fp32 decoder); the decode is then the one of
+ * those staged values.  An APP LLR is converted from the decoder's precision to out_dtype the same way
+ * (fp32 -> IBL_F64 exactly, fp64 -> IBL_F32 by round-to-nearest-even).
+ * Buffers: d_llr and d_out are contiguous and need only their element type's alignment (4 bytes for
+ * IBL_F32, 8 for IBL_F64) — vector loads and stores are taken only where the pointer and B allow them, and
+ * nothing outside the [N][B] elements of d_out is written.  d_out may be d_llr itself when both have the
+ * same dtype (the channel is staged into the decoder's own buffers before any output is written); buffers
+ * that overlap in any other way are not supported.  All work is enqueued on `stream`; a decoder serves one
+ * decode at a time.
  */
 int ibl_float_decode(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out,
                      int32_t out_dtype, int32_t early_stop, int32_t* d_iters, void* stream);

@@ -472,8 +472,12 @@ def test_u8_staging_quad_words(eng, wlan_H):
 
 @pytest.mark.parametrize("path", ["fused", "passes"])
 def test_misaligned_u8_channel(eng, wlan_H, path):
-    """A contiguous u8 channel view at an odd byte offset (B % 4 == 0, so the staging kernels' dword path
-    would apply to an aligned pointer) decodes bit-exactly: the dword loads are taken only when aligned."""
+    """A contiguous u8 channel view at an odd byte offset decodes bit-exactly. B = 64 is 8 words a row: on
+    path="passes" that is the small-batch kernels, staged by ib_stage4_words (one thread per row and word, byte
+    loads only — launch_ib_stage4 sends every batch of up to 32 words, B <= 256, there), so no alignment guard is
+    exercised on that path; on path="fused" ib_stage_t's 8-byte loads (B % 8 == 0) are taken only for an 8-byte
+    aligned base and the odd pointer takes its byte loads. The guards of ib_stage4 (B > 256), of the int32
+    loads and of the output stores are exercised by tests/test_gpu_callers.py test_ib_offset_buffers."""
     g = graph.build_graph(wlan_H)
     tb = tables.random_tables(16, 16, g.d_c_max, g.d_v_max, 5, seed=8)
     B = 64
