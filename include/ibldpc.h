@@ -260,7 +260,7 @@ int ibl_float_timing_read(ibl_float* h, double* cn_ms, int32_t* cn_launches, dou
  *
  * Layers: an ordered list of disjoint sets of checks that together cover all checks; within one layer no
  * variable appears in two checks.  layer_ptr[n_layers + 1] (layer_ptr[0] = 0) delimits the layers in
- * layer_checks[n_c].  For a quasi-cyclic code the block rows are layers.  (Pointer for later: in a DVB-S2 code
+ * layer_checks[n_c].  For a quasi-cyclic code the block rows are layers.  (codes.dvbs2_layers: in a DVB-S2 code
  * the q = (n - k) / 360 residue classes {r, r + q, r + 2q, ...} of the checks are valid layers — bit m of an
  * information group meets check (x + m q) mod (n - k), one check of a class per address as long as a group has no
  * two addresses of one residue, and a staircase parity variable joins checks j and j + 1, never two of a class.)
@@ -292,12 +292,33 @@ int ibl_float_timing_read(ibl_float* h, double* cn_ms, int32_t* cn_launches, dou
  *   and compressed check state (12 bytes per check: corrected m1, m2, argmin position | sign bits) stay in LDS
  *   through all iterations.  A workgroup holds cw_per_group = min(8, floor(160 KiB / (4 N + 12 n_c))) codewords;
  *   IBL_EUNSUPPORTED when that is 0 (N = 1944 rate 1/2: 19,440 B, 8 codewords; DVB-S2 N = 64800: 648 KB, does
- *   not fit).  A per-layer path over HBM for such long codes is deliberately not part of this interface yet.
- * ibl_layered_decode   d_llr [N][B] IBL_F32 in, d_out [N][B] IBL_F32 APP LLRs out, d_iters [B] int32 (or NULL):
+ *   not fit).  It is ibl_layered_create_path with IBL_PATH_FUSED.
+ * ibl_layered_create_path  the same with a choice of kernels:
+ *     IBL_PATH_FUSED   the fused on-chip kernel above (IBL_EUNSUPPORTED when the code does not fit);
+ *     IBL_PATH_PASSES  per-layer kernels over HBM for codes of any length that pass ibl_layers_validate (codes
+ *                      that would fit the fused kernel included): lane = codeword, one launch per layer, a wave
+ *                      updating one check for 64 codewords;
+ *     IBL_PATH_AUTO    the fused kernel when the code fits, else the per-layer kernels;
+ *   any other value is IBL_EINVAL; IBL_F64 is IBL_EUNSUPPORTED on every path.  The semantics are those specified
+ *   above on every path, the per-codeword stop included: a finished codeword's APP values are frozen at its stop
+ *   iteration.  A per-layer handle owns, allocated at create for max_batch rounded up to 64 codewords, the APP
+ *   LLRs [N][ldb] fp32 and the compressed state of every check (3 x [n_c][ldb] 4-byte words: corrected m1, m2,
+ *   argmin position | sign bits), the packed hard decisions (one bit per variable and codeword), one 64-bit mask
+ *   of finished and one of unsatisfied codewords per 64 codewords and one counter of running codewords: about
+ *   (4 N + 12 n_c) bytes per codeword of max_batch (DVB-S2 N = 64800 rate 1/2 at 8192 codewords: 5.3 GB).
+ *   ibl_layered_decode on such a handle enqueues one staging launch, n_layers launches per iteration, three more
+ *   (pack the hard decisions, syndrome, finalise) after every iteration but the last when early_stop is set, and
+ *   one output launch, all on `stream`: no allocation, no host synchronisation and no host read-back, so a
+ *   caller may capture it.  Finished codewords are skipped per whole tile of 64.  IBL_LAY_SYNDROME=gather in the
+ *   environment at create selects the syndrome's other form (one launch that gathers the sign bits per check;
+ *   same results, measured slower: DESIGN.md); any value but gather / packed is IBL_EINVAL.
+ * ibl_layered_path_in_use  *fused = 1 when decodes run the fused kernel, 0 for the per-layer kernels.
+ * ibl_layered_decode  d_llr [N][B] IBL_F32 in, d_out [N][B] IBL_F32 APP LLRs out, d_iters [B] int32 (or NULL):
  *   iterations run per codeword.  Asynchronous on `stream`, no host synchronisation.
  * ibl_layered_geometry the launch geometry ibl_layered_decode uses for a batch of B: codewords per workgroup,
  *   *ngroups = ceil(B / cw_per_group) groups of consecutive codewords, *grid = workgroups launched,
- *   min(ngroups, blocks per CU x CUs) — workgroup w decodes groups w, w + grid, w + 2 grid, ...
+ *   min(ngroups, blocks per CU x CUs) — workgroup w decodes groups w, w + grid, w + 2 grid, ...  All three
+ *   are 0 on a per-layer handle (the convention of ibl_float_fused_geometry).
  */
 typedef struct ibl_layered ibl_layered;
 int ibl_layers_validate(int32_t n_v, int32_t n_c, const int32_t* csr_indptr, const int32_t* csr_cols,
@@ -305,6 +326,10 @@ int ibl_layers_validate(int32_t n_v, int32_t n_c, const int32_t* csr_indptr, con
 int ibl_layered_create(const ibl_graph* g, int32_t n_layers, const int32_t* layer_ptr, const int32_t* layer_checks,
                        int32_t imax, float alpha, float beta, float llr_max, int32_t precision, int32_t max_batch,
                        ibl_layered** out);
+int ibl_layered_create_path(const ibl_graph* g, int32_t n_layers, const int32_t* layer_ptr,
+                            const int32_t* layer_checks, int32_t imax, float alpha, float beta, float llr_max,
+                            int32_t precision, int32_t max_batch, int32_t path, ibl_layered** out);
+int ibl_layered_path_in_use(const ibl_layered* h, int32_t* fused);
 int ibl_layered_decode(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out,
                        int32_t out_dtype, int32_t early_stop, int32_t* d_iters, void* stream);
 int ibl_layered_geometry(const ibl_layered* h, int32_t B, int32_t* cw_per_group, int32_t* ngroups, int32_t* grid);

@@ -44,6 +44,7 @@ EXPORTS = [
     "ibl_shard_range", "ibl_comm_unique_id", "ibl_comm_create", "ibl_comm_broadcast", "ibl_comm_allreduce_sum_i64",
     "ibl_comm_destroy",
     "ibl_layers_validate", "ibl_layered_create", "ibl_layered_decode", "ibl_layered_geometry", "ibl_layered_destroy",
+    "ibl_layered_create_path", "ibl_layered_path_in_use",
 ]
 IBL_COMM_ID_BYTES = 128
 
@@ -127,7 +128,10 @@ def load():
     L.ibl_layers_validate.argtypes = [_i32, _i32, _i32p, _i32p, _i32, _i32p, _i32p]
     _f32 = ctypes.c_float
     L.ibl_layered_create.argtypes = [_vp, _i32, _i32p, _i32p, _i32, _f32, _f32, _f32, _i32, _i32, ctypes.POINTER(_vp)]
-    L.ibl_layered_decode.argtypes = [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]
+    L.ibl_layered_create_path.argtypes = [_vp, _i32, _i32p, _i32p, _i32, _f32, _f32, _f32, _i32, _i32, _i32,
+                                          ctypes.POINTER(_vp)]
+    L.ibl_layered_path_in_use.argtypes = [_vp, ctypes.POINTER(_i32)]
+    L.ibl_layered_decode.argtypes =[_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]
     L.ibl_layered_geometry.argtypes = [_vp, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i32)]
     L.ibl_layered_destroy.argtypes = [_vp]
     L.ibl_layered_destroy.restype = None

@@ -28,7 +28,7 @@ Generators (the reference ships no matrices):
 from __future__ import annotations
 
 import os
-from typing import Iterable, Sequence
+from typing import Iterable, Optional, Sequence
 
 import numpy as np
 import scipy.sparse as sp
@@ -44,6 +44,7 @@ __all__ = [
     "regular_code",
     "dvbs2_structured",
     "qc_layers",
+    "dvbs2_layers",
     "greedy_layers",
     "validate_layers",
     "code_rate",
@@ -290,6 +291,22 @@ def qc_layers(H, Z: int):
     if Z < 1 or n_c % Z:
         raise ValueError(f"the number of checks ({n_c}) is not a multiple of Z = {Z}")
     return [np.arange(i * Z, (i + 1) * Z, dtype=np.int64) for i in range(n_c // Z)]
+
+
+def dvbs2_layers(H, q: Optional[int] = None):
+    """Layers of a DVB-S2-structured code: the q residue classes ``[r, r + q, r + 2q, ...]``, r = 0..q-1, of its
+    checks (q = n_c / 360 by default). Bit m of an information group meets check (x + m q) mod n_c, one check of a
+    class per address, and a staircase parity variable joins checks j and j + 1, never two of one class. A group
+    with two addresses of one residue (real EN 302 307 tables have some) breaks that: :func:`validate_layers`
+    runs on the result and names the offending check."""
+    A = canonical_csr(H)
+    n_c = A.shape[0]
+    q = n_c // 360 if q is None else int(q)
+    if q < 1 or n_c % q:
+        raise ValueError(f"the number of checks ({n_c}) is not a multiple of q = {q}")
+    layers = [np.arange(r, n_c, q, dtype=np.int64) for r in range(q)]
+    validate_layers(A, layers)
+    return layers
 
 
 def greedy_layers(H):

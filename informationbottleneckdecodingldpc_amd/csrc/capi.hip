@@ -1698,6 +1698,16 @@ struct ibl_layered {
   size_t cw_bytes = 0;
   int32_t *task = nullptr, *idx = nullptr;
   float* buf = nullptr;     // [max_batch][n_v] codeword rows
+  // per-layer path over HBM (fused = 0): the plan's records, the layers' first slots and the scratch of
+  // layered_plan.h pass_bytes(n_v, n_c, max_batch)
+  int32_t fused = 1;
+  std::vector<int32_t> layer_slot;
+  int32_t* rec = nullptr;
+  float *P = nullptr, *M1 = nullptr, *M2 = nullptr;
+  uint32_t* PS = nullptr;
+  uint64_t *done = nullptr, *unsat = nullptr, *bits = nullptr;
+  int32_t* running = nullptr;
+  int32_t syn_packed = 1;   // syndrome form (IBL_LAY_SYNDROME=gather|packed at create; DESIGN.md for the numbers)
 };
 
 namespace {
@@ -1709,6 +1719,69 @@ std::vector<int32_t> graph_indptr(const ibl_graph* g) {
 void layered_geometry(const ibl_layered* h, int B, int32_t* ngroups, int32_t* grid) {
   *ngroups = (B + h->cw_per_group - 1) / h->cw_per_group;
   *grid = std::min(*ngroups, h->bpc * h->g->num_cus);
+}
+
+// The per-layer handle (layers already validated): plan, records and all scratch for max_batch.
+int layered_create_passes(const ibl_graph* g, const std::vector<int32_t>& ip, int32_t n_layers,
+                          const int32_t* layer_ptr, const int32_t* layer_checks, int32_t imax, float alpha, float beta,
+                          float llr_max, int32_t max_batch, ibl_layered** out) {
+  LayeredPassPlan pl;
+  plan_layered_passes(g->n_c, ip.data(), n_layers, layer_ptr, layer_checks, &pl);
+  const int64_t rows = std::max(g->n_v, g->n_c);
+  if (pass_grid(pl.max_layer, max_batch) > 0x7fffffffll || pass_grid(pass_syn_runs(g->n_c), max_batch) > 0x7fffffffll ||
+      (rows * pass_tiles(max_batch) + kLayPassWaves - 1) / kLayPassWaves > 0x7fffffffll)
+    return fail(IBL_EINVAL, "max_batch is too large for the per-layer kernels' grids");
+  HIPCHK(hipSetDevice(g->device));
+  size_t priv = 0;
+  HIPCHK(lay_pass_private_bytes(&priv));
+  if (priv != 0)
+    return fail(IBL_EHIP, "a per-layer layered kernel has a " + std::to_string(priv) +
+                              "-byte private segment (register spill): rebuild required");
+  auto* h = new ibl_layered();
+  h->g = g; h->imax = imax; h->max_batch = max_batch; h->alpha = alpha; h->beta = beta; h->llr_max = llr_max;
+  h->fused = 0;
+  h->layer_slot = pl.layer_slot;
+  const LayeredPassBytes by = pass_bytes(g->n_v, g->n_c, max_batch);
+  int rc;
+  if ((rc = dupload(&h->rec, pl.rec.data(), pl.rec.size())) || (rc = dalloc(&h->P, by.P / 4)) ||
+      (rc = dalloc(&h->M1, by.state / 4)) || (rc = dalloc(&h->M2, by.state / 4)) ||
+      (rc = dalloc(&h->PS, by.state / 4)) || (rc = dalloc(&h->done, by.mask / 8)) ||
+      (rc = dalloc(&h->unsat, by.mask / 8)) || (rc = dalloc(&h->running, 1)) ||
+      (rc = dalloc(&h->bits, by.bits / 8))) {
+    ibl_layered_destroy(h);
+    return rc;
+  }
+  if (const char* v = getenv("IBL_LAY_SYNDROME")) {
+    if (!strcmp(v, "gather")) h->syn_packed = 0;
+    else if (strcmp(v, "packed")) {
+      ibl_layered_destroy(h);
+      return fail(IBL_EINVAL, "IBL_LAY_SYNDROME must be gather or packed");
+    }
+  }
+  *out = h;
+  return IBL_OK;
+}
+
+int layered_decode_passes(ibl_layered* h, const float* d_llr, int32_t B, float* d_out, int32_t early_stop,
+                          int32_t* d_iters, hipStream_t s) {
+  const ibl_graph* g = h->g;
+  LayPassArgs a{};
+  a.P = h->P; a.M1 = h->M1; a.M2 = h->M2; a.PS = h->PS; a.done = h->done; a.unsat = h->unsat;
+  a.running = h->running; a.bits = h->bits; a.rec = h->rec; a.cols = g->csr_cols; a.iters = d_iters;
+  a.alpha = h->alpha; a.beta = h->beta; a.llr_max = h->llr_max;
+  a.n_v = g->n_v; a.n_c = g->n_c; a.B = B; a.ntiles = pass_tiles(B);
+  HIPCHK(launch_lay_stage_in(a, d_llr, h->imax, s));
+  const int32_t n_layers = (int32_t)h->layer_slot.size() - 1;
+  for (int32_t it = 1; it <= h->imax; ++it) {
+    for (int32_t l = 0; l < n_layers; ++l)
+      HIPCHK(launch_lay_layer(a, h->layer_slot[l], h->layer_slot[l + 1] - h->layer_slot[l], s));
+    if (early_stop && it < h->imax) {
+      HIPCHK(launch_lay_syndrome(a, h->syn_packed, s));
+      HIPCHK(launch_lay_finalise(a, it, s));
+    }
+  }
+  HIPCHK(launch_lay_stage_out(a, d_out, s));
+  return IBL_OK;
 }
 }  // namespace
 
@@ -1725,6 +1798,13 @@ int ibl_layers_validate(int32_t n_v, int32_t n_c, const int32_t* indptr, const i
 int ibl_layered_create(const ibl_graph* g, int32_t n_layers, const int32_t* layer_ptr, const int32_t* layer_checks,
                        int32_t imax, float alpha, float beta, float llr_max, int32_t precision, int32_t max_batch,
                        ibl_layered** out) {
+  return ibl_layered_create_path(g, n_layers, layer_ptr, layer_checks, imax, alpha, beta, llr_max, precision,
+                                 max_batch, IBL_PATH_FUSED, out);
+}
+
+int ibl_layered_create_path(const ibl_graph* g, int32_t n_layers, const int32_t* layer_ptr,
+                            const int32_t* layer_checks, int32_t imax, float alpha, float beta, float llr_max,
+                            int32_t precision, int32_t max_batch, int32_t path, ibl_layered** out) {
   if (!out) return fail(IBL_EINVAL, "out is NULL");
   *out = nullptr;
   if (!g) return fail(IBL_EINVAL, "graph is NULL");
@@ -1733,9 +1813,13 @@ int ibl_layered_create(const ibl_graph* g, int32_t n_layers, const int32_t* laye
   if (imax < 1 || max_batch < 1) return fail(IBL_EINVAL, "imax and max_batch must be >= 1");
   if (!(alpha >= 0.f) || !(beta >= 0.f) || !(llr_max > 0.f) || std::isinf(alpha) || std::isinf(beta))
     return fail(IBL_EINVAL, "alpha and beta must be finite and >= 0, llr_max > 0");
+  if (path != IBL_PATH_AUTO && path != IBL_PATH_PASSES && path != IBL_PATH_FUSED)
+    return fail(IBL_EINVAL, "path must be IBL_PATH_AUTO, IBL_PATH_PASSES or IBL_PATH_FUSED");
   const std::vector<int32_t> ip = graph_indptr(g);
   int rc = ibl_layers_validate(g->n_v, g->n_c, ip.data(), g->h_cols.data(), n_layers, layer_ptr, layer_checks);
   if (rc) return rc;
+  if (path == IBL_PATH_PASSES || (path == IBL_PATH_AUTO && layered_cw_per_group(g->n_v, g->n_c) < 1))
+    return layered_create_passes(g, ip, n_layers, layer_ptr, layer_checks, imax, alpha, beta, llr_max, max_batch, out);
   LayeredPlan pl;
   plan_layered(g->n_v, g->n_c, ip.data(), g->h_cols.data(), n_layers, layer_ptr, layer_checks, &pl);
   if (pl.cw_per_group < 1)
@@ -1766,8 +1850,18 @@ int ibl_layered_create(const ibl_graph* g, int32_t n_layers, const int32_t* laye
 int ibl_layered_geometry(const ibl_layered* h, int32_t B, int32_t* cw_per_group, int32_t* ngroups, int32_t* grid) {
   if (!h || !cw_per_group || !ngroups || !grid) return fail(IBL_EINVAL, "NULL argument");
   if (B < 1 || B > h->max_batch) return fail(IBL_EINVAL, "B must lie in [1, max_batch]");
+  if (!h->fused) {
+    *cw_per_group = *ngroups = *grid = 0;
+    return IBL_OK;
+  }
   *cw_per_group = h->cw_per_group;
   layered_geometry(h, B, ngroups, grid);
+  return IBL_OK;
+}
+
+int ibl_layered_path_in_use(const ibl_layered* h, int32_t* fused) {
+  if (!h || !fused) return fail(IBL_EINVAL, "NULL argument");
+  *fused = h->fused;
   return IBL_OK;
 }
 
@@ -1781,6 +1875,9 @@ int ibl_layered_decode(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int
   const ibl_graph* g = h->g;
   hipStream_t s = (hipStream_t)stream;
   HIPCHK(hipSetDevice(g->device));
+  if (!h->fused)
+    return layered_decode_passes(h, static_cast<const float*>(d_llr), B, static_cast<float*>(d_out), early_stop,
+                                 d_iters, s);
   HIPCHK(launch_lay_transpose(static_cast<const float*>(d_llr), h->buf, g->n_v, B, s));
   LayeredArgs a{};
   a.buf = h->buf; a.task = h->task; a.idx = h->idx; a.iters = d_iters;
@@ -1821,6 +1918,8 @@ void ibl_layered_destroy(ibl_layered* h) {
   if (!h) return;
   (void)hipSetDevice(h->g->device);
   dfree(h->task); dfree(h->idx); dfree(h->buf);
+  dfree(h->rec); dfree(h->P); dfree(h->M1); dfree(h->M2); dfree(h->PS); dfree(h->done); dfree(h->unsat);
+  dfree(h->running); dfree(h->bits);
   delete h;
 }
 

@@ -369,4 +369,29 @@ hipError_t launch_lay_fused(const LayeredArgs& a, int grid, size_t lds, hipStrea
 // dst[c][r] = src[r][c], fp32
 hipError_t launch_lay_transpose(const float* src, float* dst, int rows, int cols, hipStream_t s);
 
+// Per-layer path over HBM (long codes): lane = codeword, rows [row][ldb], ldb = ntiles * 64 (layered_plan.h
+// "per-layer path"). Every launcher only enqueues on `s`.
+struct LayPassArgs {
+  float* P;                 // [n_v][ldb] APP LLRs
+  float* M1;                // [n_c][ldb] corrected m1 per slot (checks in layer order)
+  float* M2;                // [n_c][ldb] corrected m2
+  uint32_t* PS;             // [n_c][ldb] argmin position << 16 | sign bits of R
+  uint64_t* done;           // [ntiles] bit b: codeword 64 tile + b is finished (padding lanes included)
+  uint64_t* unsat;          // [ntiles] bit b: some check of that codeword is unsatisfied (this iteration)
+  int32_t* running;         // codewords not finished
+  uint64_t* bits;           // [ntiles][n_v] packed hard decisions: bit b = (P[v][64 tile + b] < 0) (packed syndrome)
+  const int32_t* rec;      // per slot {CSR offset, degree}
+  const int32_t* cols;      // the graph's CSR column indices
+  int32_t* iters;           // [B] or nullptr
+  float alpha, beta, llr_max;
+  int32_t n_v, n_c, B, ntiles;
+};
+hipError_t launch_lay_stage_in(const LayPassArgs& a, const float* llr, int imax, hipStream_t s);
+hipError_t launch_lay_layer(const LayPassArgs& a, int slot0, int n_checks, hipStream_t s);
+// packed = 0: gather form, one launch; 1: pack the hard decisions, then XOR the packed words per check (two)
+hipError_t launch_lay_syndrome(const LayPassArgs& a, int packed, hipStream_t s);
+hipError_t launch_lay_finalise(const LayPassArgs& a, int it, hipStream_t s);
+hipError_t launch_lay_stage_out(const LayPassArgs& a, float* out, hipStream_t s);
+hipError_t lay_pass_private_bytes(size_t* bytes);
+
 }  // namespace ibl

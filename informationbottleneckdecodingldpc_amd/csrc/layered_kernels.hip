@@ -228,4 +228,300 @@ hipError_t launch_lay_transpose(const float* src, float* dst, int rows, int cols
   return hipLaunchKernel((const void*)lay_transpose, dim3((unsigned)tiles), dim3(256), p, 0, s);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Per-layer path over HBM (codes too long for LDS; include/ibldpc.h "Layered min-sum", IBL_PATH_PASSES).
+//
+// lane = codeword. P[n_v][ldb] and the compressed state M1 / M2 / PS [n_c][ldb] (the fused kernel's three words,
+// a row per check, rows in layer order) live in device memory; ldb = 64 ntiles. One launch per layer: a wave item
+// is (check of the layer, tile of 64 codewords) — the check's CSR offset, degree and variable indices are
+// wave-uniform scalar loads, every row access one coalesced 256-byte segment. A layer's checks share no
+// variable, so its items are independent; layers are ordered by the stream. Nothing here waits for another
+// workgroup.
+//
+// Per-codeword stop: done[tile] holds a bit per finished codeword (padding lanes are finished from the start).
+// After iteration it < imax, the syndrome — lay_pack + lay_syndrome_packed (default), or lay_syndrome, the gather
+// form — ORs the unsatisfied codewords of a tile into unsat[tile] and lay_finalise(it) finishes the running codewords whose bit stayed clear: iters[b] = it, done bit, `running`
+// decremented. A finished lane stores nothing in any later launch (its P row entries stay at the stop value), a
+// wave whose tile is all finished leaves before its first vector load, and every kernel leaves at once when
+// `running` is 0. The host enqueues all imax iterations up front and never reads anything back.
+namespace {
+
+__device__ __forceinline__ uint64_t lay_mask(const uint64_t* m, int tile) {
+  const int32_t* w = reinterpret_cast<const int32_t*>(m);
+  return (uint64_t)(uint32_t)sload(w, 2 * tile) | ((uint64_t)(uint32_t)sload(w, 2 * tile + 1) << 32);
+}
+
+// One check of degree D for the lane's codeword (column `col` of every row): the steps and values of lay_cn.
+template <int D>
+__device__ __forceinline__ void lay_cn_rows(const LayPassArgs& a, int e0, size_t srow, size_t col, size_t ldb) {
+  size_t v[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) v[k] = (size_t)sload(a.cols, e0 + k) * ldb + col;
+  float p[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) p[k] = a.P[v[k]];
+  const float m1o = a.M1[srow], m2o = a.M2[srow];
+  const uint32_t ps = a.PS[srow];
+  const uint32_t poso = ps >> 16;
+  const float alpha = a.alpha, beta = a.beta, L = a.llr_max;
+  float q[D];
+  float m1 = __builtin_inff(), m2 = __builtin_inff();
+  uint32_t pos = 0, sx = 0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    const float r = lay_signed((uint32_t)k == poso ? m2o : m1o, ps << (32 - D + k));
+    const float x = __builtin_amdgcn_fmed3f(p[k] - r, -L, L);
+    q[k] = x;
+    sx ^= lay_bits(x);
+    const float m = fabsf(x);
+    pos = m < m1 ? (uint32_t)k : pos;
+    m2 = __builtin_amdgcn_fmed3f(m1, m2, m);
+    m1 = fminf(m1, m);
+  }
+  const float m1n = fmaxf(alpha * m1 - beta, 0.f), m2n = fmaxf(alpha * m2 - beta, 0.f);
+  uint32_t sg = 0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    const uint32_t t = sx ^ lay_bits(q[k]);
+    a.P[v[k]] = q[k] + lay_signed((uint32_t)k == pos ? m2n : m1n, t);
+    sg = __builtin_amdgcn_alignbit(sg, t, 31);
+  }
+  a.M1[srow] = m1n;
+  a.M2[srow] = m2n;
+  a.PS[srow] = (pos << 16) | sg;
+}
+
+}  // namespace
+
+// P = llr + 0 (a -0 enters as +0), padding lanes 0; state rows 0; masks, counter and iters reset.
+// item = (row < max(n_v, n_c), tile)
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_stage_in(const LayPassArgs a, const float* __restrict__ llr,
+                                                                   int imax) {
+  const int lane = (int)(threadIdx.x & 63u);
+  const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + (int64_t)(threadIdx.x >> 6);
+  const int64_t rows = a.n_v > a.n_c ? a.n_v : a.n_c;
+  if (item >= rows * a.ntiles) return;
+  const int tile = (int)(item % a.ntiles);
+  const int64_t row = item / a.ntiles;
+  const size_t ldb = (size_t)a.ntiles * kLayTile;
+  const int b = tile * kLayTile + lane;
+  const size_t at = (size_t)row * ldb + (size_t)b;
+  if (row < a.n_v) a.P[at] = b < a.B ? llr[(size_t)row * (size_t)a.B + (size_t)b] + 0.f : 0.f;
+  if (row < a.n_c) {
+    a.M1[at] = 0.f;
+    a.M2[at] = 0.f;
+    a.PS[at] = 0u;
+  }
+  if (row == 0) {
+    if (a.iters && b < a.B) a.iters[b] = imax;
+    if (lane == 0) {
+      const int left = a.B - tile * kLayTile;   // >= 1
+      a.done[tile] = left >= kLayTile ? 0ull : ~0ull << left;
+      a.unsat[tile] = 0ull;
+      if (tile == 0) *a.running = a.B;
+    }
+  }
+}
+
+// item = (check slot0 + c of the layer, tile), tile fastest
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_layer(const LayPassArgs a, int slot0, int n_checks) {
+  if (sload(a.running, 0) == 0) return;
+  const int lane = (int)(threadIdx.x & 63u);
+  const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (item >= (int64_t)n_checks * a.ntiles) return;
+  const int tile = (int)(item % a.ntiles);
+  const int slot = slot0 + (int)(item / a.ntiles);
+  const uint64_t dm = lay_mask(a.done, tile);
+  if (dm == ~0ull) return;            // wave-uniform: the whole tile is finished
+  if ((dm >> lane) & 1ull) return;    // a finished (or padding) lane loads and stores nothing
+  const int e0 = sload(a.rec, 2 * slot), d = sload(a.rec, 2 * slot + 1);
+  const size_t ldb = (size_t)a.ntiles * kLayTile;
+  const size_t col = (size_t)tile * kLayTile + (size_t)lane;
+  const size_t srow = (size_t)slot * ldb + col;
+  switch (d) {
+#define LAY_CASE(D) case D: lay_cn_rows<D>(a, e0, srow, col, ldb); break;
+    LAY_CASE(2) LAY_CASE(3) LAY_CASE(4) LAY_CASE(5) LAY_CASE(6) LAY_CASE(7) LAY_CASE(8) LAY_CASE(9)
+    LAY_CASE(10) LAY_CASE(11) LAY_CASE(12) LAY_CASE(13) LAY_CASE(14) LAY_CASE(15) LAY_CASE(16)
+#undef LAY_CASE
+    default: break;
+  }
+}
+
+// Syndrome of x = (P < 0), gather form: item = (run of kLaySynRun consecutive slots, tile); a lane XORs the sign
+// bits of each check's variables and ORs the checks of the run; one 64-bit atomic OR per wave, only when some
+// running codeword of the tile has an unsatisfied check in the run.
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_syndrome(const LayPassArgs a) {
+  if (sload(a.running, 0) == 0) return;
+  const int lane = (int)(threadIdx.x & 63u);
+  const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int nruns = (a.n_c + kLaySynRun - 1) / kLaySynRun;
+  if (item >= (int64_t)nruns * a.ntiles) return;
+  const int tile = (int)(item % a.ntiles);
+  const int run = (int)(item / a.ntiles);
+  const uint64_t dm = lay_mask(a.done, tile);
+  if (dm == ~0ull) return;
+  const size_t ldb = (size_t)a.ntiles * kLayTile;
+  const size_t col = (size_t)tile * kLayTile + (size_t)lane;
+  const int s0 = run * kLaySynRun, s1 = s0 + kLaySynRun < a.n_c ? s0 + kLaySynRun : a.n_c;
+  bool bad = false;
+  if (!((dm >> lane) & 1ull)) {
+    for (int s = s0; s < s1; ++s) {
+      const int e0 = sload(a.rec, 2 * s), d = sload(a.rec, 2 * s + 1);
+      bool par = false;
+      for (int k = 0; k < d; ++k) par ^= a.P[(size_t)sload(a.cols, e0 + k) * ldb + col] < 0.f;
+      bad |= par;
+    }
+  }
+  const uint64_t m = __ballot(bad);
+  if (m != 0ull && lane == 0) atomicOr(reinterpret_cast<unsigned long long*>(a.unsat) + tile, (unsigned long long)m);
+}
+
+// Syndrome, packed form, step 1: bits[tile][v] = ballot(P[v][lane's codeword] < 0), finished lanes 0 (never
+// loaded). item = (run of 64 variables, tile); lane i keeps the word of variable v0 + i, one 512-byte store.
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_pack(const LayPassArgs a) {
+  if (sload(a.running, 0) == 0) return;
+  const int lane = (int)(threadIdx.x & 63u);
+  const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int nruns = (a.n_v + kLayTile - 1) / kLayTile;
+  if (item >= (int64_t)nruns * a.ntiles) return;
+  const int tile = (int)(item % a.ntiles);
+  const int run = (int)(item / a.ntiles);
+  const uint64_t dm = lay_mask(a.done, tile);
+  if (dm == ~0ull) return;
+  const bool live = !((dm >> lane) & 1ull);
+  const size_t ldb = (size_t)a.ntiles * kLayTile;
+  const size_t col = (size_t)tile * kLayTile + (size_t)lane;
+  const int v0 = run * kLayTile, n = a.n_v - v0 < kLayTile ? a.n_v - v0 : kLayTile;
+  uint64_t mine = 0ull;
+#pragma unroll 8
+  for (int i = 0; i < n; ++i) {
+    bool neg = false;
+    if (live) neg = a.P[(size_t)(v0 + i) * ldb + col] < 0.f;
+    const uint64_t w = __ballot(neg);
+    if (lane == i) mine = w;
+  }
+  if (lane < n) a.bits[(size_t)tile * (size_t)a.n_v + (size_t)(v0 + lane)] = mine;
+}
+
+// Step 2: item = (run of 64 consecutive slots, tile), lane = check: the XOR of the packed words of the check's
+// variables is the set of codewords that leave it unsatisfied; OR over the wave, one 64-bit atomic OR when
+// non-zero. (The variable indices are per-lane loads here: a lane owns a check, not a codeword.)
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_syndrome_packed(const LayPassArgs a) {
+  if (sload(a.running, 0) == 0) return;
+  const int lane = (int)(threadIdx.x & 63u);
+  const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int nruns = (a.n_c + kLayTile - 1) / kLayTile;
+  if (item >= (int64_t)nruns * a.ntiles) return;
+  const int tile = (int)(item % a.ntiles);
+  const int run = (int)(item / a.ntiles);
+  const uint64_t dm = lay_mask(a.done, tile);
+  if (dm == ~0ull) return;
+  const uint64_t* bits = a.bits + (size_t)tile * (size_t)a.n_v;
+  const int s = run * kLayTile + lane;
+  uint64_t w = 0ull;
+  if (s < a.n_c) {
+    const int e0 = a.rec[2 * s], d = a.rec[2 * s + 1];
+    for (int k = 0; k < d; ++k) w ^= bits[a.cols[e0 + k]];
+  }
+  w &= ~dm;
+#pragma unroll
+  for (int off = 32; off >= 1; off >>= 1) w |= (uint64_t)__shfl_xor((unsigned long long)w, off);
+  if (w != 0ull && lane == 0) atomicOr(reinterpret_cast<unsigned long long*>(a.unsat) + tile, (unsigned long long)w);
+}
+
+// One wave per tile: running codewords whose syndrome is zero are finished at iteration `it`.
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_finalise(const LayPassArgs a, int it) {
+  if (sload(a.running, 0) == 0) return;
+  const int lane = (int)(threadIdx.x & 63u);
+  const int tile = (int)blockIdx.x * kLayPassWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (tile >= a.ntiles) return;
+  const uint64_t dm = lay_mask(a.done, tile), um = lay_mask(a.unsat, tile);
+  const uint64_t now = ~dm & ~um;
+  if (a.iters && ((now >> lane) & 1ull)) a.iters[tile * kLayTile + lane] = it;
+  if (lane == 0) {
+    if (now != 0ull) {
+      a.done[tile] = dm | now;
+      atomicSub(a.running, (int)__popcll(now));
+    }
+    if (um != 0ull) a.unsat[tile] = 0ull;
+  }
+}
+
+// out[row][b] = P[row][b] for b < B (padding lanes never reach the caller); item = (row < n_v, tile)
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_stage_out(const LayPassArgs a, float* __restrict__ out) {
+  const int lane = (int)(threadIdx.x & 63u);
+  const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + (int64_t)(threadIdx.x >> 6);
+  if (item >= (int64_t)a.n_v * a.ntiles) return;
+  const int tile = (int)(item % a.ntiles);
+  const int64_t row = item / a.ntiles;
+  const int b = tile * kLayTile + lane;
+  if (b < a.B) out[(size_t)row * (size_t)a.B + (size_t)b] = a.P[(size_t)row * (size_t)a.ntiles * kLayTile + (size_t)b];
+}
+
+namespace {
+bool lay_pass_args_ok(const LayPassArgs& a) {
+  return a.P && a.M1 && a.M2 && a.PS && a.done && a.unsat && a.running && a.rec && a.cols && a.n_v >= 1 &&
+         a.n_c >= 1 && a.B >= 1 && a.ntiles == pass_tiles(a.B);
+}
+hipError_t lay_pass_launch(const void* f, int64_t items, void** p, hipStream_t s) {
+  const int64_t grid = (items + kLayPassWaves - 1) / kLayPassWaves;
+  if (grid < 1 || grid > 0x7fffffffll) return hipErrorInvalidValue;
+  return hipLaunchKernel(f, dim3((unsigned)grid), dim3(64 * kLayPassWaves), p, 0, s);
+}
+}  // namespace
+
+hipError_t launch_lay_stage_in(const LayPassArgs& a, const float* llr, int imax, hipStream_t s) {
+  if (!lay_pass_args_ok(a) || !llr) return hipErrorInvalidValue;
+  LayPassArgs args = a;
+  void* p[] = {&args, (void*)&llr, (void*)&imax};
+  return lay_pass_launch((const void*)lay_stage_in, (int64_t)std::max(a.n_v, a.n_c) * a.ntiles, p, s);
+}
+
+hipError_t launch_lay_layer(const LayPassArgs& a, int slot0, int n_checks, hipStream_t s) {
+  if (!lay_pass_args_ok(a) || slot0 < 0 || n_checks < 0 || (int64_t)slot0 + n_checks > a.n_c)
+    return hipErrorInvalidValue;
+  if (n_checks == 0) return hipSuccess;
+  LayPassArgs args = a;
+  void* p[] = {&args, (void*)&slot0, (void*)&n_checks};
+  return lay_pass_launch((const void*)lay_layer, pass_items(n_checks, a.B), p, s);
+}
+
+hipError_t launch_lay_syndrome(const LayPassArgs& a, int packed, hipStream_t s) {
+  if (!lay_pass_args_ok(a) || (packed && !a.bits)) return hipErrorInvalidValue;
+  LayPassArgs args = a;
+  void* p[] = {&args};
+  if (!packed) return lay_pass_launch((const void*)lay_syndrome, pass_items(pass_syn_runs(a.n_c), a.B), p, s);
+  const hipError_t e = lay_pass_launch((const void*)lay_pack, pass_items(pass_pack_runs(a.n_v), a.B), p, s);
+  if (e != hipSuccess) return e;
+  return lay_pass_launch((const void*)lay_syndrome_packed, pass_items(pass_pack_runs(a.n_c), a.B), p, s);
+}
+
+hipError_t launch_lay_finalise(const LayPassArgs& a, int it, hipStream_t s) {
+  if (!lay_pass_args_ok(a)) return hipErrorInvalidValue;
+  LayPassArgs args = a;
+  void* p[] = {&args, (void*)&it};
+  return lay_pass_launch((const void*)lay_finalise, a.ntiles, p, s);
+}
+
+hipError_t launch_lay_stage_out(const LayPassArgs& a, float* out, hipStream_t s) {
+  if (!lay_pass_args_ok(a) || !out) return hipErrorInvalidValue;
+  LayPassArgs args = a;
+  void* p[] = {&args, (void*)&out};
+  return lay_pass_launch((const void*)lay_stage_out, (int64_t)a.n_v * a.ntiles, p, s);
+}
+
+// the largest private (scratch) segment over the per-layer kernels: built to run without one
+hipError_t lay_pass_private_bytes(size_t* bytes) {
+  *bytes = 0;
+  for (const void* f : {(const void*)lay_stage_in, (const void*)lay_layer, (const void*)lay_syndrome,
+                        (const void*)lay_pack, (const void*)lay_syndrome_packed, (const void*)lay_finalise,
+                        (const void*)lay_stage_out}) {
+    hipFuncAttributes fa;
+    const hipError_t e = hipFuncGetAttributes(&fa, f);
+    if (e != hipSuccess) return e;
+    *bytes = std::max(*bytes, (size_t)fa.localSizeBytes);
+  }
+  return hipSuccess;
+}
+
 }  // namespace ibl

@@ -1,8 +1,8 @@
 // Host-side planning of the layered (row-serial) min-sum decoder: pure C++17, no HIP (like plan.h).
 //
-// Built twice: into libibldpc.so (capi.hip includes this header) and, with AddressSanitizer and
-// UndefinedBehaviorSanitizer, into the CPU-only checker tests/asan/layered_plan_check.cpp
-// (tests/test_cpu_layered.py).
+// Built into libibldpc.so (capi.hip includes this header) and, with AddressSanitizer and
+// UndefinedBehaviorSanitizer, into the CPU-only checkers tests/asan/layered_plan_check.cpp
+// (tests/test_cpu_layered.py) and tests/asan/layered_pass_plan_check.cpp (tests/test_cpu_layered_passes.py).
 //
 // A layer is a set of checks no two of which share a variable; the layers are disjoint, cover every check and
 // are decoded in order (include/ibldpc.h "Layered min-sum"). The device plan cuts every layer into tasks of up
@@ -127,6 +127,78 @@ inline void plan_layered(int32_t n_v, int32_t n_c, const int32_t* indptr, const 
   pl->n_tasks = (int32_t)(pl->task.size() / 4);
   pl->cw_bytes = layered_cw_bytes(n_v, n_c);
   pl->cw_per_group = layered_cw_per_group(n_v, n_c);
+}
+
+// ---- per-layer path over HBM (codes of any length; checked by tests/asan/layered_pass_plan_check.cpp) --------
+// lane = codeword: P[n_v][ldb] and, per check, the three state rows M1 / M2 / PS [n_c][ldb], the checks in layer
+// order (slot = position in layer_checks). One launch per layer; a wave item is (check of the layer, tile of
+// kLayTile codewords), tile fastest, kLayPassWaves items per workgroup. The syndrome's item is (run of kLaySynRun
+// consecutive slots, tile) in its gather form; its packed form first packs the hard decisions into one 64-bit word
+// per (variable, tile), item (run of kLayTile variables, tile), then XORs them per check, item (run of kLayTile
+// slots, tile). One 64-bit mask of finished and one of unsatisfied codewords per tile.
+constexpr int kLayTile = 64;        // codewords per wave item (one dword per lane and row)
+constexpr int kLayPassWaves = 4;    // wave items per workgroup (256 threads)
+constexpr int kLaySynRun = 16;      // checks per syndrome item
+
+inline int32_t pass_tiles(int32_t B, int32_t tile = kLayTile) { return (int32_t)(((int64_t)B + tile - 1) / tile); }
+// padded row stride (codewords) of a batch of B
+inline int64_t pass_ldb(int32_t B, int32_t tile = kLayTile) { return (int64_t)pass_tiles(B, tile) * tile; }
+// wave items and workgroups of a launch over n_checks checks (a layer, or the syndrome's runs) for a batch of B
+inline int64_t pass_items(int32_t n_checks, int32_t B, int32_t tile = kLayTile) {
+  return (int64_t)n_checks * (int64_t)pass_tiles(B, tile);
+}
+inline int64_t pass_grid(int32_t n_checks, int32_t B, int32_t tile = kLayTile) {
+  return (pass_items(n_checks, B, tile) + kLayPassWaves - 1) / kLayPassWaves;
+}
+inline int32_t pass_syn_runs(int32_t n_c) { return (int32_t)(((int64_t)n_c + kLaySynRun - 1) / kLaySynRun); }
+// packed syndrome: runs of kLayTile variables (packing, a lane keeps a variable's word) or checks (lane = check)
+inline int32_t pass_pack_runs(int32_t n) { return (int32_t)(((int64_t)n + kLayTile - 1) / kLayTile); }
+
+// byte sizes of the device scratch a per-layer handle of max_batch owns
+struct LayeredPassBytes {
+  size_t P = 0;       // [n_v][ldb] fp32
+  size_t state = 0;   // each of M1, M2, PS: [n_c][ldb] 4-byte words
+  size_t mask = 0;    // each of finished, unsatisfied: one 64-bit word per tile
+  size_t counter = 0; // codewords still running
+  size_t bits = 0;    // packed hard decisions: one 64-bit word per variable and tile
+  size_t total = 0;   // P + 3 state + 2 mask + counter + bits
+};
+inline LayeredPassBytes pass_bytes(int32_t n_v, int32_t n_c, int32_t max_batch) {
+  LayeredPassBytes b;
+  const size_t ldb = (size_t)pass_ldb(max_batch);
+  b.P = (size_t)4 * (size_t)n_v * ldb;
+  b.state = (size_t)4 * (size_t)n_c * ldb;
+  b.mask = (size_t)8 * (size_t)pass_tiles(max_batch);
+  b.counter = 4;
+  b.bits = (size_t)8 * (size_t)n_v * (size_t)pass_tiles(max_batch);
+  b.total = b.P + 3 * b.state + 2 * b.mask + b.counter + b.bits;
+  return b;
+}
+
+struct LayeredPassPlan {
+  std::vector<int32_t> rec;         // per slot {CSR offset of the check's first edge, degree}
+  std::vector<int32_t> check_of;    // slot -> check
+  std::vector<int32_t> layer_slot;  // n_layers + 1: first slot of each layer
+  int32_t max_layer = 0;            // checks of the largest layer
+};
+
+// Precondition: validate_layers(...) == 0.
+inline void plan_layered_passes(int32_t n_c, const int32_t* indptr, int32_t n_layers, const int32_t* layer_ptr,
+                                const int32_t* layer_checks, LayeredPassPlan* pl) {
+  pl->rec.clear(); pl->check_of.clear();
+  pl->layer_slot.assign(layer_ptr, layer_ptr + n_layers + 1);
+  pl->rec.reserve((size_t)2 * (size_t)n_c);
+  pl->check_of.reserve((size_t)n_c);
+  pl->max_layer = 0;
+  for (int32_t l = 0; l < n_layers; ++l) {
+    pl->max_layer = std::max(pl->max_layer, layer_ptr[l + 1] - layer_ptr[l]);
+    for (int32_t i = layer_ptr[l]; i < layer_ptr[l + 1]; ++i) {
+      const int32_t c = layer_checks[i];
+      pl->check_of.push_back(c);
+      pl->rec.push_back(indptr[c]);
+      pl->rec.push_back(indptr[c + 1] - indptr[c]);
+    }
+  }
 }
 
 }  // namespace ibl

@@ -291,11 +291,20 @@ class LayeredDecoder:
     include/ibldpc.h "Layered min-sum"). ``layers``: ordered sequences of check indices (``codes.qc_layers``,
     ``codes.greedy_layers``). ``alpha`` scales and ``beta`` offsets the check magnitudes (1, 0: plain layered
     min-sum). The early stop is per codeword; ``decode(..., iters=)`` receives each codeword's iteration count.
-    Raises :class:`_lib.IBLError` (``IBL_EUNSUPPORTED``) when a codeword does not fit in LDS or ``precision``
-    is not float32."""
+    ``path``: ``"fused"`` (default) the on-chip kernel, one wave per codeword in LDS; ``"passes"`` per-layer
+    kernels over HBM for codes of any length (``codes.dvbs2_layers`` for DVB-S2; they own about 4 N + 12 n_c
+    bytes per codeword of ``max_batch``); ``"auto"`` the fused kernel when the codeword fits, else the per-layer
+    kernels. The outputs are the same on every path.
+    Raises :class:`_lib.IBLError` (``IBL_EUNSUPPORTED``) when ``path="fused"`` and a codeword does not fit in
+    LDS, or ``precision`` is not float32."""
+
+    _PATHS = {"auto": _lib.IBL_PATH_AUTO, "passes": _lib.IBL_PATH_PASSES, "fused": _lib.IBL_PATH_FUSED}
 
     def __init__(self, graph: Graph, layers, imax: int, max_batch: int, alpha: float = 1.0, beta: float = 0.0,
-                 llr_max: float = 150.0, precision=torch.float32):
+                 llr_max: float = 150.0, precision=torch.float32, path: str = "fused"):
+        if path not in self._PATHS:
+            raise ValueError('path must be "fused", "passes" or "auto"')
+        self.path = path
         self.graph = graph
         self.imax = int(imax)
         self.max_batch = int(max_batch)
@@ -308,14 +317,23 @@ class LayeredDecoder:
             chk = np.zeros(1, np.int32)
         self.n_layers = nl
         h = ctypes.c_void_p()
-        _lib.check(_lib.load().ibl_layered_create(graph.handle, nl, ptr, chk, self.imax, self.alpha, self.beta,
-                                                  self.llr_max, _DT_FL[precision], self.max_batch, ctypes.byref(h)),
-                   "ibl_layered_create")
+        _lib.check(_lib.load().ibl_layered_create_path(graph.handle, nl, ptr, chk, self.imax, self.alpha, self.beta,
+                                                       self.llr_max, _DT_FL[precision], self.max_batch,
+                                                       self._PATHS[path], ctypes.byref(h)),
+                   "ibl_layered_create_path")
         self._h = h
+
+    @property
+    def path_in_use(self) -> str:
+        """``"fused"`` or ``"passes"``: the kernels decodes run (``ibl_layered_path_in_use``)."""
+        f = ctypes.c_int32()
+        _lib.check(_lib.load().ibl_layered_path_in_use(self._h, ctypes.byref(f)), "ibl_layered_path_in_use")
+        return "fused" if f.value else "passes"
 
     def geometry(self, B: int):
         """``(cw_per_group, ngroups, grid)`` a batch of ``B`` is decoded with (``ibl_layered_geometry``): a
-        workgroup decodes ``cw_per_group`` consecutive codewords at a time, workgroup w the groups w, w + grid, ..."""
+        workgroup decodes ``cw_per_group`` consecutive codewords at a time, workgroup w the groups w, w + grid, ...
+        ``(0, 0, 0)`` on a per-layer decoder."""
         c, n, g = ctypes.c_int32(), ctypes.c_int32(), ctypes.c_int32()
         _lib.check(_lib.load().ibl_layered_geometry(self._h, int(B), ctypes.byref(c), ctypes.byref(n),
                                                     ctypes.byref(g)), "ibl_layered_geometry")

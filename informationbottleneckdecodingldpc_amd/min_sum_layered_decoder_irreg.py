@@ -1,12 +1,14 @@
 """Layered normalised / offset min-sum LDPC decoder with the interface of the float min-sum class
-(:mod:`.min_sum_decoder_irreg`), running on the fused MI355X HIP kernel (``ibl_layered_*``).
+(:mod:`.min_sum_decoder_irreg`), running on the MI355X HIP kernels of ``ibl_layered_*``.
 
 The reference has no layered decoder; this class keeps ``Min_Sum_Decoder_class_irregular``'s constructor shape
 and method names so the same drivers (``ber.run_ber``) take it. Keyword-only extensions:
 
 * ``layers`` — ordered sequences of check indices; or ``Z`` — the lifting size of a quasi-cyclic code, whose
   block rows become the layers (``codes.qc_layers``); neither: ``codes.greedy_layers``;
-* ``alpha``, ``beta`` — normalisation factor and offset of the check magnitudes, max(alpha * m - beta, 0).
+* ``alpha``, ``beta`` — normalisation factor and offset of the check magnitudes, max(alpha * m - beta, 0);
+* ``path`` — ``"fused"`` (default), ``"passes"`` (per-layer kernels over HBM: long codes such as DVB-S2 with
+  ``layers=codes.dvbs2_layers(H)``) or ``"auto"`` (:class:`.engine.LayeredDecoder`).
 
 fp32 only. The early stop is per codeword; ``last_iterations`` holds the int32 device tensor of the last
 decode's iteration counts.
@@ -24,7 +26,10 @@ from .engine import LayeredDecoder, count_below
 class Min_Sum_Layered_Decoder_class_irregular(CodeMixin):
 
     def __init__(self, filename, imax_, cardinality_T_channel_, msg_at_time_, *, layers=None, Z=None,
-                 alpha: float = 1.0, beta: float = 0.0, llr_max: float = 150.0):
+                 alpha: float = 1.0, beta: float = 0.0, llr_max: float = 150.0, path: str = "fused"):
+        if path not in LayeredDecoder._PATHS:
+            raise ValueError('path must be "fused", "passes" or "auto"')
+        self.path = path
         self._init_code(filename)
         self.imax = int(imax_)
         self.cardinality_T_channel = int(cardinality_T_channel_)
@@ -50,7 +55,7 @@ class Min_Sum_Layered_Decoder_class_irregular(CodeMixin):
         self.context = dev
         self.msg_at_time = int(msg_at_time_)
         self._dec = LayeredDecoder(self._graph_on(dev), self.layers, self.imax, self.msg_at_time, alpha=self.alpha,
-                                   beta=self.beta, llr_max=self.llr_max)
+                                   beta=self.beta, llr_max=self.llr_max, path=self.path)
 
     def _decode(self, received_blocks, buffer_in, return_buffer, early_stop=True):
         if self._dec is None:
