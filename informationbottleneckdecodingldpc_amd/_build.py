@@ -12,7 +12,7 @@ CSRC = os.path.join(PKG, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 LIB = os.path.join(PKG, "libibldpc.so")
 SOURCES = ["ib_kernels.hip", "float_kernels.hip", "channel_kernels.hip", "encoder_kernels.hip", "layered_kernels.hip",
-           "capi.hip", "comm.hip"]
+           "capi_core.hip", "capi_ib.hip", "capi_float.hip", "capi_layered.hip", "capi_encoder.hip", "comm.hip"]
 ARCH = os.environ.get("IBLDPC_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", INCLUDE, "-I", CSRC,

@@ -1,0 +1,409 @@
+// C ABI (include/ibldpc.h): the float decoders (min-sum, belief propagation; float_kernels.hip).
+//
+// Schedules restate the reference's host loops without their per-iteration host sync:
+//   decode_OpenCL_min_sum            (Continous_LDPC_Decoding/min_sum_decoder_irreg.py:221-287)
+//   decode_OpenCL_belief_propagation (bp_decoder_irreg.py:221-286)
+// Early stop: each check-node pass ORs "some check unsatisfied" into 64 flag words of its
+// iteration; the launches of the next iteration read those words and exit at once when they
+// are all zero, and a one-wave kernel turns the flags into the iteration index the output
+// pass uses.  The host only enqueues.
+#include "host.h"
+
+using namespace ibl;
+
+struct ibl_float {
+  const ibl_graph* g = nullptr;
+  int32_t kind = 0, imax = 0, prec = kF32, max_batch = 0, ldb = 0;
+  double llr_max = 150.0;
+  DevBuf<uint8_t> cin, vbuf0, vbuf1, chf;   // inboxes and staged channel, fp32 or fp64 elements
+  DevBuf<int32_t> flags, dL;
+  int grid_cn = 0, grid_vn = 0;
+  // degree-2 variable fold of the per-pass path (fl_cn_item): per-check records, the variables the
+  // variable pass still updates, the second check inbox (the check passes alternate between cin / cin2)
+  DevBuf<uint8_t> cin2;
+  DevBuf<int32_t> fold, vn_nodes;
+  int32_t n_vn_nodes = 0, n_folded = 0;
+  std::vector<int32_t> fold_rec, fold_rest;   // the fold's host plan; uploaded with cin2 once a batch can use it
+  DevBuf<int32_t> bad;      // channel LLRs that violated the precondition since the last ibl_float_input_check
+  int32_t small_b = 0;      // small-batch kernels (fl_*_small) for B <= small_b (0: off)
+  bool s_ok = false;        // the small-batch kernels run without scratch (create's check)
+  ChainGraphs s_graphs;     // small-batch pass chains (IBL_SMALL_GRAPH=0 at create: launch them one by one)
+  KTimer timer;
+  // fused on-chip path (FlFusedArgs): task tables, LDS bytes per workgroup, grid
+  int32_t path = IBL_PATH_AUTO;
+  bool fused_ok = false;
+  FusedTaskBufs ft;
+  size_t f_lds = 0;
+  int f_grid = 0;
+};
+
+namespace {
+
+// Task tables of the fused float kernel (FlFusedArgs). Check nodes sorted by degree (heaviest first,
+// stable) and cut into tasks of up to 64 nodes of one degree; edge k of lane i of a check task gets
+// slot first + k*count + i. Variable nodes likewise; vn_slot maps each variable edge (task-major,
+// k*count + i) to the slot of the same edge. Leaves fused_ok false when the code does not fit.
+int fused_setup(ibl_float* h) {
+  const ibl_graph* g = h->g;
+  const int64_t E = g->n_e;
+  if (E >= 65536 || g->dc_min < 2 || E == 0 || (size_t)(E + g->n_v) * 16 > (size_t)kLdsBytes) return IBL_OK;
+  FusedTasks ft;
+  // 16-byte slots (ds_read_b128 / ds_write_b128): the natural order (stable by degree) keeps a quasi-cyclic
+  // code's lanes on runs of consecutive slots, which conflict less than the dword-bank greedy order;
+  // IBL_FUSED_VORDER=1 selects the greedy order (A/B)
+  const char* voe = getenv("IBL_FUSED_VORDER");
+  build_fused_tasks(*g, &ft, voe && voe[0] == '1', fused_vwin());
+  pad_vn_slots(&ft);
+  // messages and channel (16-byte slots), 4 counter words, the padded u16 indices (codes whose indices do
+  // not fit beside the messages take the per-pass path)
+  const size_t lds = (size_t)(E + g->n_v) * 16 + 16 + ft.vn_slot.size() * 2;
+  if (lds > (size_t)kLdsBytes) return IBL_OK;
+  int bpc = 0, block = 0;
+  if (fl_fused_occupancy(h->kind, h->prec, g->dcm, g->dvm, lds, &bpc, &block) != hipSuccess || bpc < 1) {
+    (void)hipGetLastError();
+    return IBL_OK;
+  }
+  if (int rc = h->ft.upload(ft)) return rc;
+  h->f_lds = lds;
+  h->f_grid = bpc * g->num_cus;
+  h->fused_ok = true;
+  return IBL_OK;
+}
+
+// Launch geometry of the fused float kernel for a batch of B: groups of 4 fp32 / 2 fp64 codewords, one per
+// workgroup round (fl_fused's group loop); the decode and ibl_float_fused_geometry both take it from here.
+void float_fused_geometry(const ibl_float* h, int B, int32_t* ngroups, int32_t* grid) {
+  const int cwl = h->prec == kF32 ? 4 : 2;
+  *ngroups = (B + cwl - 1) / cwl;
+  *grid = std::min(*ngroups, h->f_grid);
+}
+
+// The fold's device state (second check inbox, per-check records, unfolded variable list) once a batch can reach
+// the per-pass kernels (max_batch > small_b): decoders that only ever run the small-batch kernels — the
+// reference's DVB-S2 driver decodes msg_at_time = 2 — do not hold a fourth E x ldb inbox. cin2 is set last:
+// cin2 set <=> the fold's state is complete.
+int fold_alloc(ibl_float* h) {
+  if (h->n_folded == 0 || h->cin2 || h->max_batch <= h->small_b) return IBL_OK;
+  DevBuf<uint8_t> c2;
+  DevBuf<int32_t> fold, nodes;
+  int rc;
+  if ((rc = c2.alloc_zero((size_t)h->g->n_e * h->ldb * (h->prec == kF32 ? 4 : 8))) || (rc = fold.upload(h->fold_rec)) ||
+      (rc = nodes.upload(h->fold_rest)))
+    return rc;
+  h->fold = std::move(fold);
+  h->vn_nodes = std::move(nodes);
+  h->cin2 = std::move(c2);
+  return IBL_OK;
+}
+
+// the staging kernels count precondition violations (float_kernels.hip llr_bad): min-sum NaN; BP NaN and, for
+// the fp64 decoder, |x| > 709.089 (just under ln(DBL_MAX / 2)), for the fp32 decoder +-inf
+int stage_rule(const ibl_float* h) { return h->kind == IBL_BP ? (h->prec == kF64 ? 2 : 3) : 1; }
+
+int float_decode_fused(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out, int32_t out_dtype,
+                       bool early, int32_t* d_iters, hipStream_t s) {
+  const ibl_graph* g = h->g;
+  const int I = h->imax, cwl = h->prec == kF32 ? 4 : 2;
+  HIPCHK(launch_fl_stage_t(d_llr, llr_dtype, g->n_v, B, h->ft.vn_node, h->chf, h->prec, stage_rule(h), h->bad, s));
+  FlFusedArgs fa{};
+  fa.ch = h->chf; fa.cn_task = h->ft.cn_task; fa.vn_task = h->ft.vn_task; fa.vn_node = h->ft.vn_node;
+  fa.vn_slot = h->ft.vn_slot; fa.out = d_out; fa.unsat = flag_row(h->flags, early, 0); fa.dL = nullptr;
+  fa.llr_max = h->llr_max; fa.n_e = (int32_t)g->n_e; fa.n_v = g->n_v; fa.n_cn_tasks = h->ft.n_cn;
+  fa.n_vn_tasks = h->ft.n_vn; fa.n_vs = h->ft.n_vs; fa.ldb = h->ldb; fa.B = B; fa.imax = I; fa.out_dtype = out_dtype;
+  int grid = 0;
+  float_fused_geometry(h, B, &fa.ngroups, &grid);
+  fa.aligned = out_aligned(B, d_out, cwl, out_dtype == kF32 ? 4 : 8);
+  auto launch = [&] { return launch_fl_fused(fa, h->kind, h->prec, g->dcm, g->dvm, grid, h->f_lds, s); };
+#if IBL_DIAG
+  const char* ftrace = getenv("IBL_TRACE_FUSED");   // diagnostic builds: phase clocks of block 0's first group
+  TraceBuf tr;
+  int rc;
+  if (ftrace) {
+    if ((rc = tr.open((size_t)kFlTraceWords * (2 * I + 4), s))) return rc;
+    fa.trace = tr.d;
+  }
+#endif
+  HIPCHK(h->timer.timed(0, s, launch));
+#if IBL_DIAG
+  if (ftrace && (rc = tr.save(s, ftrace, 0, tr.n))) return rc;
+  fa.trace = nullptr;
+#endif
+  HIPCHK(launch_finalize(h->flags, I, early ? 1 : 0, h->dL, d_iters, s));
+  if (early) {   // batch-global stop before imax-1: re-run the batch to L (the kernel exits if L = imax-1)
+    fa.unsat = nullptr;
+    fa.dL = h->dL;
+    HIPCHK(h->timer.timed(0, s, launch));
+  }
+  return IBL_OK;
+}
+
+// small batch: (task, word) items, lane = node (fl_*_small); the per-pass schedule without the fold.
+// Rows packed to the batch (B rounded up to 4 codewords: fl_send's quads, 16-byte pieces) instead of
+// the per-pass path's ldb, so a pass touches E x ldbs elements of each inbox, not one line per edge
+int float_decode_small(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out, int32_t out_dtype,
+                       bool early, int32_t* d_iters, hipStream_t s) {
+  const ibl_graph* g = h->g;
+  const int I = h->imax, cwl = h->prec == kF32 ? 4 : 2;
+  const int nwords = (B + cwl - 1) / cwl, ldbs = (B + 3) / 4 * 4;
+  HIPCHK(launch_fl_stage(d_llr, llr_dtype, g->n_v, B, h->chf, h->prec, ldbs, stage_rule(h), h->bad, s));
+  auto grid_of = [&](int ntask) {
+    const int need = (ntask * nwords + kFlSmallBlock / 64 - 1) / (kFlSmallBlock / 64);
+    return std::max(1, std::min(need, 4 * g->num_cus));
+  };
+  FlArgs send{};
+  send.ch = h->chf; send.out = h->cin; send.start = g->vn_start; send.deg = g->vn_deg; send.tgt = g->tgt_vn;
+  send.n_nodes = g->n_v; send.ldb = ldbs; send.B = B;
+  FlArgs cn{}, vn{};
+  cn.in = h->cin; cn.start = g->cn_start; cn.deg = g->cn_deg; cn.tgt = g->tgt_cn; cn.ch = h->chf;
+  vn.out = h->cin; vn.ch = h->chf; vn.start = g->vn_start; vn.deg = g->vn_deg; vn.tgt = g->tgt_vn;
+  cn.info = g->cn_info; cn.task = g->cn_task; cn.n_tasks = g->n_cn_task;
+  vn.info = g->vn_info; vn.task = g->vn_task; vn.n_tasks = g->n_vn_task;
+  cn.llr_max = vn.llr_max = h->llr_max;
+  cn.n_nodes = g->n_c; vn.n_nodes = g->n_v;
+  cn.nwords = vn.nwords = nwords;
+  cn.ldb = vn.ldb = ldbs;
+  cn.B = vn.B = B;
+  const int gcn = grid_of(g->n_cn_task), gvn = grid_of(g->n_vn_task);
+  // the pass chain (decoder buffers only): send, then {CN j, VN j} — replayed from a captured graph (ChainGraphs)
+  auto chain = [&](hipStream_t st) -> hipError_t {
+    hipError_t e = launch_fl_send(send, h->prec, st);
+    if (e != hipSuccess) return e;
+    FlArgs c = cn, v = vn;
+    for (int j = 1; j < I; ++j) {
+      void* vb = (j & 1) ? h->vbuf1 : h->vbuf0;
+      c.out = vb;
+      c.gate = flag_row(h->flags, early && j >= 3, j - 2);
+      c.unsat = flag_row(h->flags, early, j - 1);
+      if ((e = h->timer.timed(0, st, [&] { return launch_fl_cn_small(c, h->kind, h->prec, g->dcm, gcn, st); })) != hipSuccess)
+        return e;
+      if (j == I - 1) break;   // the last variable pass feeds no output (as in float_decode_passes)
+      v.in = vb;
+      v.gate = flag_row(h->flags, early && j >= 2, j - 1);
+      if ((e = h->timer.timed(1, st, [&] { return launch_fl_vn_small(v, h->prec, g->dvm, gvn, st); })) != hipSuccess)
+        return e;
+    }
+    return hipSuccess;
+  };
+  if (h->s_graphs.on && !h->timer.on) HIPCHK(h->s_graphs.run(B, early ? 1 : 0, s, chain));
+  else HIPCHK(chain(s));
+  HIPCHK(launch_finalize(h->flags, I, early ? 1 : 0, h->dL, d_iters, s));
+  FlDecArgs dc{};
+  dc.vin0 = h->vbuf0; dc.vin1 = h->vbuf1; dc.ch = h->chf; dc.start = g->vn_start; dc.deg = g->vn_deg;
+  dc.iters = h->dL; dc.out = d_out; dc.out_dtype = out_dtype; dc.n_nodes = g->n_v; dc.ldb = ldbs; dc.B = B;
+  dc.info = g->vn_info; dc.task = g->vn_task; dc.n_tasks = g->n_vn_task; dc.nwords = nwords;
+  HIPCHK(launch_fl_dec_small(dc, h->prec, grid_of(g->n_vn_task), s));
+  return IBL_OK;
+}
+
+int float_decode_passes(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out, int32_t out_dtype,
+                        bool early, int32_t* d_iters, hipStream_t s) {
+  const ibl_graph* g = h->g;
+  const int I = h->imax, cwl = h->prec == kF32 ? 4 : 2;   // cwl: codewords per lane
+  const int nchunks = (B + 64 * cwl - 1) / (64 * cwl);
+  HIPCHK(launch_fl_stage(d_llr, llr_dtype, g->n_v, B, h->chf, h->prec, h->ldb, stage_rule(h), h->bad, s));
+  FlArgs send{};
+  send.ch = h->chf; send.out = h->cin;   // = cb[1] below
+  send.start = g->vn_start; send.deg = g->vn_deg; send.tgt = g->tgt_vn;
+  send.n_nodes = g->n_v; send.ldb = h->ldb; send.B = B;
+  HIPCHK(launch_fl_send(send, h->prec, s));
+  // Check pass j reads check inbox cb[j & 1] (send fills cb[1]) and writes the variable inbox vbuf[j & 1];
+  // variable pass j writes cb[(j + 1) & 1]. With the fold, check pass j also writes its folded variables'
+  // messages into cb[(j + 1) & 1], and the variable pass skips them; the last check pass writes every
+  // variable-inbox row (the decision reads them) and folds nothing. The last iteration's variable pass
+  // only feeds a syndrome the reference never reads (its loop ends at imax, bp_decoder_irreg.py:240-268),
+  // so it is not run.
+  if (h->n_folded > 0 && !h->cin2) return fail(IBL_EHIP, "fold inbox missing (fold_alloc)");
+  const bool fold = h->n_folded > 0;
+  void* cb[2] = {fold ? h->cin2 : h->cin, h->cin};
+  FlArgs cn{}, vn{};
+  cn.start = g->cn_start; cn.deg = g->cn_deg; cn.tgt = g->tgt_cn; cn.ch = h->chf; cn.fold = h->fold;
+  vn.ch = h->chf; vn.start = g->vn_start; vn.deg = g->vn_deg; vn.tgt = g->tgt_vn;
+  vn.nodes = fold ? h->vn_nodes.get() : nullptr;
+  cn.llr_max = vn.llr_max = h->llr_max;
+  cn.n_nodes = g->n_c; vn.n_nodes = fold ? h->n_vn_nodes : g->n_v;
+  cn.nchunks = nchunks;
+  vn.nchunks = (B + fl_vn_chunk(h->prec, g->dvm) - 1) / fl_vn_chunk(h->prec, g->dvm);
+  cn.ldb = vn.ldb = h->ldb;
+  cn.B = vn.B = B;
+  for (int j = 1; j < I; ++j) {
+    void* vb = (j & 1) ? h->vbuf1 : h->vbuf0;
+    const bool last = j == I - 1;
+    cn.in = cb[j & 1];
+    cn.out = vb;
+    cn.fout = cb[(j + 1) & 1];
+    cn.fold_mode = (fold && !last) ? (early ? 2 : 1) : 0;
+    cn.gate = flag_row(h->flags, early && j >= 3, j - 2);
+    cn.unsat = flag_row(h->flags, early, j - 1);
+    HIPCHK(h->timer.timed(0, s, [&] { return launch_fl_cn(cn, h->kind, h->prec, g->dcm, h->grid_cn, s); }));
+    if (last) break;
+    vn.in = vb;
+    vn.out = cb[(j + 1) & 1];
+    vn.gate = flag_row(h->flags, early && j >= 2, j - 1);
+    HIPCHK(h->timer.timed(1, s, [&] { return launch_fl_vn(vn, h->prec, g->dvm, h->grid_vn, s); }));
+  }
+  HIPCHK(launch_finalize(h->flags, I, early ? 1 : 0, h->dL, d_iters, s));
+  FlDecArgs dc{};
+  dc.vin0 = h->vbuf0; dc.vin1 = h->vbuf1; dc.ch = h->chf; dc.start = g->vn_start; dc.deg = g->vn_deg;
+  dc.iters = h->dL; dc.out = d_out; dc.out_dtype = out_dtype; dc.n_nodes = g->n_v; dc.nchunks = nchunks;
+  dc.ldb = h->ldb; dc.B = B;
+  dc.aligned = out_aligned(B, d_out, cwl, out_dtype == kF32 ? 4 : 8);
+  const size_t items = (size_t)g->n_v * nchunks;
+  HIPCHK(launch_fl_dec(dc, h->prec, (int)std::min<size_t>((items + 3) / 4, 65536), s));
+  return IBL_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int ibl_float_set_path(ibl_float* h, int32_t path) {
+  if (!h) return fail(IBL_EINVAL, "decoder is NULL");
+  if (int rc = check_path(path)) return rc;
+  if (path == IBL_PATH_FUSED && !h->fused_ok)
+    return fail(IBL_EUNSUPPORTED, "code does not fit the fused kernel ((E + N) * 16 B > 160 KiB or a check degree < 2)");
+  h->path = path;
+  return IBL_OK;
+}
+
+int ibl_float_set_small_batch(ibl_float* h, int32_t max_b) {
+  if (!h) return fail(IBL_EINVAL, "decoder is NULL");
+  if (max_b < 0) return fail(IBL_EINVAL, "max_b must be >= 0");
+  if (max_b > 0 && !h->s_ok)   // create turned them off: this build's small-batch kernels need scratch
+    return fail(IBL_EUNSUPPORTED, "the small-batch kernels of this build have a private segment: rebuild required");
+  HIPCHK(hipSetDevice(h->g->device));
+  const int32_t old = h->small_b;
+  h->small_b = max_b;
+  int rc = fold_alloc(h);   // batches above the new threshold take the per-pass kernels, which fold
+  if (rc) h->small_b = old;
+  return rc;
+}
+
+int ibl_float_small_batch(const ibl_float* h, int32_t* max_b) {
+  if (!h || !max_b) return fail(IBL_EINVAL, "NULL argument");
+  *max_b = h->small_b;
+  return IBL_OK;
+}
+
+int ibl_float_folded(const ibl_float* h, int32_t* n_folded) {
+  if (!h || !n_folded) return fail(IBL_EINVAL, "NULL argument");
+  *n_folded = h->n_folded;
+  return IBL_OK;
+}
+
+int ibl_float_input_check(ibl_float* h, int32_t* violations, void* stream) {
+  if (!h) return fail(IBL_EINVAL, "decoder is NULL");
+  // The counter belongs to the decoder and collects every decode's staging, on any stream: synchronise the whole
+  // device (not only `stream`) so no decode still in flight elsewhere adds to it between the read and the clear.
+  (void)stream;
+  HIPCHK(hipSetDevice(h->g->device));
+  HIPCHK(hipDeviceSynchronize());
+  int32_t n = 0;
+  HIPCHK(hipMemcpy(&n, h->bad, sizeof(int32_t), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemset(h->bad, 0, sizeof(int32_t)));
+  if (violations) *violations = n;
+  if (n > 0)
+    return fail(IBL_EINVAL, std::to_string(n) + (h->kind == IBL_BP
+                                                     ? (h->prec == kF64 ? " channel LLR(s) NaN or |x| > 709.089 (BP precondition)"
+                                                                          : " channel LLR(s) NaN or infinite (BP precondition)")
+                                                     : " channel LLR(s) NaN (min-sum precondition)") +
+                                ": those decodes' outputs are unspecified");
+  return IBL_OK;
+}
+
+int ibl_float_fused_geometry(const ibl_float* h, int32_t B, int32_t* ngroups, int32_t* grid) {
+  if (!h || !ngroups || !grid) return fail(IBL_EINVAL, "NULL argument");
+  if (B < 1 || B > h->max_batch) return fail(IBL_EINVAL, "B must lie in [1, max_batch]");
+  *ngroups = *grid = 0;
+  if (h->fused_ok && h->path != IBL_PATH_PASSES) float_fused_geometry(h, B, ngroups, grid);
+  return IBL_OK;
+}
+
+int ibl_float_path_in_use(const ibl_float* h, int32_t* fused) {
+  if (!h || !fused) return fail(IBL_EINVAL, "NULL argument");
+  *fused = (h->fused_ok && h->path != IBL_PATH_PASSES) ? 1 : 0;
+  return IBL_OK;
+}
+
+int ibl_float_timing(ibl_float* h, int32_t enable) { return timing_enable(h, enable); }
+int ibl_float_timing_read(ibl_float* h, double* cn_ms, int32_t* cn_n, double* vn_ms, int32_t* vn_n) {
+  return timing_read(h, cn_ms, cn_n, vn_ms, vn_n);
+}
+
+int ibl_float_create(const ibl_graph* g, int32_t kind, int32_t imax, double llr_max, int32_t precision,
+                     int32_t max_batch, ibl_float** out) {
+  if (!out) return fail(IBL_EINVAL, "out is NULL");
+  *out = nullptr;
+  if (!g) return fail(IBL_EINVAL, "graph is NULL");
+  if (kind != IBL_MINSUM && kind != IBL_BP) return fail(IBL_EINVAL, "kind must be IBL_MINSUM or IBL_BP");
+  if (precision != kF32 && precision != kF64) return fail(IBL_EINVAL, "precision must be IBL_F32 or IBL_F64");
+  if (imax < 1 || max_batch < 1) return fail(IBL_EINVAL, "imax and max_batch must be >= 1");
+  if (g->dcm > kMaxD || g->dvm > kMaxD) return fail(IBL_EUNSUPPORTED, "float decoders support node degrees <= 16");
+  HIPCHK(hipSetDevice(g->device));
+  std::unique_ptr<ibl_float> h(new ibl_float());
+  h->g = g; h->kind = kind; h->imax = imax; h->prec = precision; h->max_batch = max_batch; h->llr_max = llr_max;
+  // rows padded to the widest wave item of the per-pass kernels (fp32 256 / fp64 128 codewords; 512 with IBL_FL_VN2
+  // builds), not beyond: the reference's DVB-S2 driver decodes msg_at_time = 2 in fp64
+  const int pad = std::max(64 * (precision == kF32 ? 4 : 2), fl_vn_chunk(precision, g->dvm));
+  h->ldb = (max_batch + pad - 1) / pad * pad;
+  const size_t es = precision == kF32 ? 4 : 8;
+  const size_t inbox = (size_t)g->n_e * h->ldb * es;
+  int rc;
+  if ((rc = h->cin.alloc_zero(inbox)) || (rc = h->vbuf0.alloc_zero(inbox)) || (rc = h->vbuf1.alloc_zero(inbox)) ||
+      (rc = h->chf.alloc((size_t)g->n_v * h->ldb * es)) || (rc = h->flags.alloc((size_t)imax * kShards)) ||
+      (rc = h->dL.alloc(1)) || (rc = h->bad.alloc_zero(1)))
+    return rc;
+  int bpc = 0;
+  // at most 16 waves per CU: with a second block per CU its waves issue behind the first block's
+  // (oldest-first) and the per-block work counters cannot rebalance across blocks
+  if (fl_occupancy(0, kind, precision, g->dcm, &bpc) != hipSuccess || bpc < 1) bpc = 1;
+  // (A/B knob, read once here: IBL_FL_WAVES = waves per CU the per-pass grids may fill, default 16)
+  const char* fw = getenv("IBL_FL_WAVES");
+  const int wcap = std::max(16, fw ? atoi(fw) : 16) * 64;
+  h->grid_cn = std::min(bpc, wcap / fl_block(0, kind, precision, g->dcm)) * g->num_cus;
+  if (fl_occupancy(1, kind, precision, g->dvm, &bpc) != hipSuccess || bpc < 1) bpc = 1;
+  h->grid_vn = std::min(bpc, wcap / fl_block(1, kind, precision, g->dvm)) * g->num_cus;
+  if ((rc = fused_setup(h.get()))) return rc;
+  // degree-2 variable fold of the per-pass path (IBL_FL_FOLD=0 at create turns it off: A/B); its second check
+  // inbox is allocated only once some batch can reach the per-pass kernels (max_batch > small_b, fold_alloc)
+  if (env_on("IBL_FL_FOLD") && (h->n_folded = plan_fold(*g, &h->fold_rec, &h->fold_rest)) > 0)
+    h->n_vn_nodes = (int32_t)h->fold_rest.size();
+  else
+    h->n_folded = 0;
+  // same guard as the IB fast path: the float kernels are built to run without scratch
+  size_t priv = 0;
+  const char* kname = "";
+  HIPCHK(fl_private_bytes(kind, precision, g->dcm, g->dvm, h->fused_ok, &priv, &kname));
+  if ((rc = refuse_private(priv, std::string("float kernel ") + kname + " has a ",
+                           "-byte private segment (register spill): rebuild required")))
+    return rc;
+  // small-batch kernels (IBL_SMALL_B at create overrides the default; off if they would need scratch)
+  HIPCHK(fl_small_private_bytes(kind, precision, g->dcm, g->dvm, &priv, &kname));
+  h->s_ok = priv == 0;
+  small_batch_env(h->s_ok, kFlSmallBatchDefault, &h->small_b, &h->s_graphs);
+  if ((rc = fold_alloc(h.get()))) return rc;
+  *out = h.release();
+  return IBL_OK;
+}
+
+void ibl_float_destroy(ibl_float* h) {
+  if (h) (void)hipSetDevice(h->g->device);
+  delete h;
+}
+
+int ibl_float_decode(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out, int32_t out_dtype,
+                     int32_t early_stop, int32_t* d_iters, void* stream) {
+  if (!h) return fail(IBL_EINVAL, "decoder is NULL");
+  if (B < 1 || B > h->max_batch) return fail(IBL_EINVAL, "B must lie in [1, max_batch]");
+  if ((llr_dtype != kF32 && llr_dtype != kF64) || (out_dtype != kF32 && out_dtype != kF64))
+    return fail(IBL_EINVAL, "LLR dtypes must be IBL_F32 or IBL_F64");
+  if (!d_llr || !d_out) return fail(IBL_EINVAL, "NULL buffer");
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(hipSetDevice(h->g->device));
+  const bool early = early_stop != 0 && h->imax > 1;
+  if (early) HIPCHK(hipMemsetAsync(h->flags, 0, sizeof(int32_t) * (size_t)h->imax * kShards, s));
+  if (h->fused_ok && h->path != IBL_PATH_PASSES)
+    return float_decode_fused(h, d_llr, llr_dtype, B, d_out, out_dtype, early, d_iters, s);
+  if (B <= h->small_b) return float_decode_small(h, d_llr, llr_dtype, B, d_out, out_dtype, early, d_iters, s);
+  return float_decode_passes(h, d_llr, llr_dtype, B, d_out, out_dtype, early, d_iters, s);
+}
+
+}  // extern "C"

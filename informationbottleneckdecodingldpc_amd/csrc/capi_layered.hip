@@ -1,0 +1,220 @@
+// C ABI (include/ibldpc.h): the layered normalised / offset min-sum decoder (layered_plan.h, layered_kernels.hip):
+// the fused on-chip kernel for codes whose codeword state fits the LDS, the per-layer path over HBM otherwise.
+#include <cmath>
+#include <cstring>
+
+#include "host.h"
+#include "layered_plan.h"
+
+using namespace ibl;
+
+struct ibl_layered {
+  const ibl_graph* g = nullptr;
+  int32_t imax = 0, max_batch = 0, n_tasks = 0, cw_per_group = 0, bpc = 1;
+  float alpha = 1.f, beta = 0.f, llr_max = 150.f;
+  size_t cw_bytes = 0;
+  DevBuf<int32_t> task, idx;
+  DevBuf<float> buf;        // [max_batch][n_v] codeword rows
+  // per-layer path over HBM (fused = 0): the plan's records, the layers' first slots and the scratch of
+  // layered_plan.h pass_bytes(n_v, n_c, max_batch)
+  int32_t fused = 1;
+  std::vector<int32_t> layer_slot;
+  DevBuf<int32_t> rec;
+  DevBuf<float> P, M1, M2;
+  DevBuf<uint32_t> PS;
+  DevBuf<uint64_t> done, unsat, bits;
+  DevBuf<int32_t> running;
+  int32_t syn_packed = 1;   // syndrome form (IBL_LAY_SYNDROME=gather|packed at create; DESIGN.md for the numbers)
+};
+
+namespace {
+std::vector<int32_t> graph_indptr(const ibl_graph* g) {
+  std::vector<int32_t> ip((size_t)g->n_c + 1, 0);
+  for (int32_t c = 0; c < g->n_c; ++c) ip[(size_t)c + 1] = ip[c] + g->h_cn_deg[c];
+  return ip;
+}
+void layered_geometry(const ibl_layered* h, int B, int32_t* ngroups, int32_t* grid) {
+  *ngroups = (B + h->cw_per_group - 1) / h->cw_per_group;
+  *grid = std::min(*ngroups, h->bpc * h->g->num_cus);
+}
+
+// The per-layer handle (layers already validated): plan, records and all scratch for max_batch.
+int layered_create_passes(const ibl_graph* g, const std::vector<int32_t>& ip, int32_t n_layers,
+                          const int32_t* layer_ptr, const int32_t* layer_checks, int32_t imax, float alpha, float beta,
+                          float llr_max, int32_t max_batch, ibl_layered** out) {
+  LayeredPassPlan pl;
+  plan_layered_passes(g->n_c, ip.data(), n_layers, layer_ptr, layer_checks, &pl);
+  const int64_t rows = std::max(g->n_v, g->n_c);
+  if (pass_grid(pl.max_layer, max_batch) > 0x7fffffffll || pass_grid(pass_syn_runs(g->n_c), max_batch) > 0x7fffffffll ||
+      (rows * pass_tiles(max_batch) + kLayPassWaves - 1) / kLayPassWaves > 0x7fffffffll)
+    return fail(IBL_EINVAL, "max_batch is too large for the per-layer kernels' grids");
+  HIPCHK(hipSetDevice(g->device));
+  size_t priv = 0;
+  HIPCHK(lay_pass_private_bytes(&priv));
+  int rc = refuse_private(priv, "a per-layer layered kernel has a ", "-byte private segment (register spill): rebuild required");
+  if (rc) return rc;
+  std::unique_ptr<ibl_layered> h(new ibl_layered());
+  h->g = g; h->imax = imax; h->max_batch = max_batch; h->alpha = alpha; h->beta = beta; h->llr_max = llr_max;
+  h->fused = 0;
+  h->layer_slot = pl.layer_slot;
+  const LayeredPassBytes by = pass_bytes(g->n_v, g->n_c, max_batch);
+  if ((rc = h->rec.upload(pl.rec)) || (rc = h->P.alloc(by.P / 4)) || (rc = h->M1.alloc(by.state / 4)) ||
+      (rc = h->M2.alloc(by.state / 4)) || (rc = h->PS.alloc(by.state / 4)) || (rc = h->done.alloc(by.mask / 8)) ||
+      (rc = h->unsat.alloc(by.mask / 8)) || (rc = h->running.alloc(1)) || (rc = h->bits.alloc(by.bits / 8)))
+    return rc;
+  if (const char* v = getenv("IBL_LAY_SYNDROME")) {
+    if (!strcmp(v, "gather")) h->syn_packed = 0;
+    else if (strcmp(v, "packed")) return fail(IBL_EINVAL, "IBL_LAY_SYNDROME must be gather or packed");
+  }
+  *out = h.release();
+  return IBL_OK;
+}
+
+int layered_decode_passes(ibl_layered* h, const float* d_llr, int32_t B, float* d_out, int32_t early_stop,
+                          int32_t* d_iters, hipStream_t s) {
+  const ibl_graph* g = h->g;
+  LayPassArgs a{};
+  a.P = h->P; a.M1 = h->M1; a.M2 = h->M2; a.PS = h->PS; a.done = h->done; a.unsat = h->unsat;
+  a.running = h->running; a.bits = h->bits; a.rec = h->rec; a.cols = g->csr_cols; a.iters = d_iters;
+  a.alpha = h->alpha; a.beta = h->beta; a.llr_max = h->llr_max;
+  a.n_v = g->n_v; a.n_c = g->n_c; a.B = B; a.ntiles = pass_tiles(B);
+  HIPCHK(launch_lay_stage_in(a, d_llr, h->imax, s));
+  const int32_t n_layers = (int32_t)h->layer_slot.size() - 1;
+  for (int32_t it = 1; it <= h->imax; ++it) {
+    for (int32_t l = 0; l < n_layers; ++l)
+      HIPCHK(launch_lay_layer(a, h->layer_slot[l], h->layer_slot[l + 1] - h->layer_slot[l], s));
+    if (early_stop && it < h->imax) {
+      HIPCHK(launch_lay_syndrome(a, h->syn_packed, s));
+      HIPCHK(launch_lay_finalise(a, it, s));
+    }
+  }
+  HIPCHK(launch_lay_stage_out(a, d_out, s));
+  return IBL_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int ibl_layers_validate(int32_t n_v, int32_t n_c, const int32_t* indptr, const int32_t* cols, int32_t n_layers,
+                        const int32_t* layer_ptr, const int32_t* layer_checks) {
+  std::string err;
+  const int rc = validate_layers(n_v, n_c, indptr, cols, n_layers, layer_ptr, layer_checks, &err);
+  if (rc) return fail(rc == -2 ? IBL_EUNSUPPORTED : IBL_EINVAL, err);
+  return IBL_OK;
+}
+
+int ibl_layered_create(const ibl_graph* g, int32_t n_layers, const int32_t* layer_ptr, const int32_t* layer_checks,
+                       int32_t imax, float alpha, float beta, float llr_max, int32_t precision, int32_t max_batch,
+                       ibl_layered** out) {
+  return ibl_layered_create_path(g, n_layers, layer_ptr, layer_checks, imax, alpha, beta, llr_max, precision,
+                                 max_batch, IBL_PATH_FUSED, out);
+}
+
+int ibl_layered_create_path(const ibl_graph* g, int32_t n_layers, const int32_t* layer_ptr,
+                            const int32_t* layer_checks, int32_t imax, float alpha, float beta, float llr_max,
+                            int32_t precision, int32_t max_batch, int32_t path, ibl_layered** out) {
+  if (!out) return fail(IBL_EINVAL, "out is NULL");
+  *out = nullptr;
+  if (!g) return fail(IBL_EINVAL, "graph is NULL");
+  if (precision == kF64) return fail(IBL_EUNSUPPORTED, "the layered decoder is fp32 only (fp64 is not built)");
+  if (precision != kF32) return fail(IBL_EINVAL, "precision must be IBL_F32");
+  if (imax < 1 || max_batch < 1) return fail(IBL_EINVAL, "imax and max_batch must be >= 1");
+  if (!(alpha >= 0.f) || !(beta >= 0.f) || !(llr_max > 0.f) || std::isinf(alpha) || std::isinf(beta))
+    return fail(IBL_EINVAL, "alpha and beta must be finite and >= 0, llr_max > 0");
+  if (int rc = check_path(path)) return rc;
+  const std::vector<int32_t> ip = graph_indptr(g);
+  int rc = ibl_layers_validate(g->n_v, g->n_c, ip.data(), g->h_cols.data(), n_layers, layer_ptr, layer_checks);
+  if (rc) return rc;
+  if (path == IBL_PATH_PASSES || (path == IBL_PATH_AUTO && layered_cw_per_group(g->n_v, g->n_c) < 1))
+    return layered_create_passes(g, ip, n_layers, layer_ptr, layer_checks, imax, alpha, beta, llr_max, max_batch, out);
+  LayeredPlan pl;
+  plan_layered(g->n_v, g->n_c, ip.data(), g->h_cols.data(), n_layers, layer_ptr, layer_checks, &pl);
+  if (pl.cw_per_group < 1)
+    return fail(IBL_EUNSUPPORTED, "code does not fit the layered kernel: one codeword needs 4 N + 12 n_c = " +
+                                      std::to_string(pl.cw_bytes) + " bytes of LDS, a workgroup has " +
+                                      std::to_string(kLayLds));
+  HIPCHK(hipSetDevice(g->device));
+  std::unique_ptr<ibl_layered> h(new ibl_layered());
+  h->g = g; h->imax = imax; h->max_batch = max_batch; h->alpha = alpha; h->beta = beta; h->llr_max = llr_max;
+  h->n_tasks = pl.n_tasks; h->cw_per_group = pl.cw_per_group; h->cw_bytes = pl.cw_bytes;
+  if ((rc = h->task.upload(pl.task)) || (rc = h->idx.upload(pl.idx)) ||
+      (rc = h->buf.alloc((size_t)max_batch * (size_t)g->n_v)))
+    return rc;
+  int bpc = 0;
+  size_t priv = 0;
+  const hipError_t e = lay_fused_occupancy(h->cw_per_group, (size_t)h->cw_per_group * h->cw_bytes, &bpc, &priv);
+  if (e != hipSuccess) return fail(IBL_EHIP, std::string("layered kernel occupancy: ") + hipGetErrorString(e));
+  if (bpc < 1) return fail(IBL_EHIP, "no occupancy for the layered kernel");
+  // same guard as the other fused kernels: built to run without scratch
+  if ((rc = refuse_private(priv, "layered kernel has a ", "-byte private segment (register spill): rebuild required")))
+    return rc;
+  h->bpc = bpc;
+  *out = h.release();
+  return IBL_OK;
+}
+
+int ibl_layered_geometry(const ibl_layered* h, int32_t B, int32_t* cw_per_group, int32_t* ngroups, int32_t* grid) {
+  if (!h || !cw_per_group || !ngroups || !grid) return fail(IBL_EINVAL, "NULL argument");
+  if (B < 1 || B > h->max_batch) return fail(IBL_EINVAL, "B must lie in [1, max_batch]");
+  if (!h->fused) {
+    *cw_per_group = *ngroups = *grid = 0;
+    return IBL_OK;
+  }
+  *cw_per_group = h->cw_per_group;
+  layered_geometry(h, B, ngroups, grid);
+  return IBL_OK;
+}
+
+int ibl_layered_path_in_use(const ibl_layered* h, int32_t* fused) {
+  if (!h || !fused) return fail(IBL_EINVAL, "NULL argument");
+  *fused = h->fused;
+  return IBL_OK;
+}
+
+int ibl_layered_decode(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out,
+                       int32_t out_dtype, int32_t early_stop, int32_t* d_iters, void* stream) {
+  if (!h) return fail(IBL_EINVAL, "decoder is NULL");
+  if (B < 1 || B > h->max_batch) return fail(IBL_EINVAL, "B must lie in [1, max_batch]");
+  if (llr_dtype == kF64 || out_dtype == kF64) return fail(IBL_EUNSUPPORTED, "the layered decoder is fp32 only");
+  if (llr_dtype != kF32 || out_dtype != kF32) return fail(IBL_EINVAL, "LLR dtypes must be IBL_F32");
+  if (!d_llr || !d_out) return fail(IBL_EINVAL, "NULL buffer");
+  const ibl_graph* g = h->g;
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(hipSetDevice(g->device));
+  if (!h->fused)
+    return layered_decode_passes(h, static_cast<const float*>(d_llr), B, static_cast<float*>(d_out), early_stop,
+                                 d_iters, s);
+  HIPCHK(launch_lay_transpose(static_cast<const float*>(d_llr), h->buf, g->n_v, B, s));
+  LayeredArgs a{};
+  a.buf = h->buf; a.task = h->task; a.idx = h->idx; a.iters = d_iters;
+  a.alpha = h->alpha; a.beta = h->beta; a.llr_max = h->llr_max;
+  a.n_v = g->n_v; a.n_c = g->n_c; a.n_tasks = h->n_tasks; a.B = B; a.imax = h->imax;
+  a.early = early_stop ? 1 : 0;
+  a.cw_per_group = h->cw_per_group; a.cw_bytes = (int32_t)h->cw_bytes;
+  int32_t grid = 0;
+  layered_geometry(h, B, &a.ngroups, &grid);
+#if IBL_DIAG
+  // diagnostic builds only: IBL_TRACE_LAYERED=<file> records workgroup 0 / wave 0's clocks at every task of its
+  // first codeword's second iteration (with -DIBL_LAY_TRACE=1 kernels, tools/variants.py laytrace)
+  const char* ltrace = getenv("IBL_TRACE_LAYERED");
+  TraceBuf tr;
+  int rc;
+  if (ltrace) {
+    if ((rc = tr.open((size_t)3 * h->n_tasks, s))) return rc;
+    a.trace = tr.d;
+  }
+#endif
+  HIPCHK(launch_lay_fused(a, grid, (size_t)h->cw_per_group * h->cw_bytes, s));
+#if IBL_DIAG
+  if (ltrace && (rc = tr.save(s, ltrace, 0, tr.n))) return rc;
+#endif
+  HIPCHK(launch_lay_transpose(h->buf, static_cast<float*>(d_out), B, g->n_v, s));
+  return IBL_OK;
+}
+
+void ibl_layered_destroy(ibl_layered* h) {
+  if (h) (void)hipSetDevice(h->g->device);
+  delete h;
+}
+
+}  // extern "C"

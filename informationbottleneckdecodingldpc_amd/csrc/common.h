@@ -67,7 +67,7 @@ constexpr int kLdsBytes = 160 * 1024;
 
 enum Dtype : int32_t { kU8 = 1, kI32 = 2, kF32 = 3, kF64 = 4 };
 
-// the C ABI's per-thread last error (capi.hip; ibl_last_error): other translation units report through it
+// the C ABI's per-thread last error (capi_core.hip; ibl_last_error): other translation units report through it
 int set_error(int code, const char* msg);
 
 // Read-only graph arrays read through the constant address space: uniform indices become scalar
@@ -258,7 +258,7 @@ struct FlDecArgs {
   int32_t n_tasks, nwords;
 };
 
-// launchers (defined in the .hip translation units, called by capi.hip)
+// launchers (defined in the .hip translation units, called by capi_*.hip)
 hipError_t launch_ib_stage(const void* ch, int dtype, int n, int B, uint8_t* ch8, int ldb, hipStream_t s);
 // writes the first ceil(B / 8) words of every row (the rest of a row is padding no output reads)
 hipError_t launch_ib_stage4(const void* ch, int dtype, int n, int B, uint8_t* ch4, int ldb_bytes, hipStream_t s);

@@ -1052,7 +1052,7 @@ __device__ __forceinline__ void fused_cn_item(void* msg, int first, int cnt_, in
 }
 
 // Variable-edge slot indices: staged into LDS as 16-bit values beside the messages (the fused path
-// requires the room for them, capi.hip fused_setup), row k of a task at sfirst + 64k: the D loads share
+// requires the room for them, capi_float.hip fused_setup), row k of a task at sfirst + 64k: the D loads share
 // one address and take their row offsets as immediates.
 template <typename F, int D, int NC>
 __device__ __forceinline__ void fused_vn_item(void* msg, const void* chL, const uint16_t* vn_slot, int pos,

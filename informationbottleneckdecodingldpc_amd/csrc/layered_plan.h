@@ -1,6 +1,6 @@
 // Host-side planning of the layered (row-serial) min-sum decoder: pure C++17, no HIP (like plan.h).
 //
-// Built into libibldpc.so (capi.hip includes this header) and, with AddressSanitizer and
+// Built into libibldpc.so (capi_layered.hip includes this header) and, with AddressSanitizer and
 // UndefinedBehaviorSanitizer, into the CPU-only checkers tests/asan/layered_plan_check.cpp
 // (tests/test_cpu_layered.py) and tests/asan/layered_pass_plan_check.cpp (tests/test_cpu_layered_passes.py).
 //

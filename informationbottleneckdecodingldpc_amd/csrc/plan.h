@@ -3,7 +3,7 @@
 // Everything the C ABI derives on the host before a launch lives here — the edge index arrays
 // (map_node_connections), the fast path's work orders and small-batch tasks, the float and IB paths' degree-2
 // fold plans (the IB one under tests/asan/fold_plan_check.cpp), the fused kernels' task tables and the encoder's substitution / factorisation plan — so the
-// same code is built twice: into libibldpc.so (capi.hip includes this header) and, with AddressSanitizer
+// same code is built twice: into libibldpc.so (the capi_*.hip units include this header) and, with AddressSanitizer
 // and UndefinedBehaviorSanitizer, into the CPU-only checker tests/asan/plan_check.cpp
 // (tests/test_cpu_host.py::test_host_planning_under_sanitizers).
 #pragma once

@@ -40,24 +40,32 @@ def test_library_exports_every_header_symbol(lib):
 
 def test_product_library_has_no_diagnostic_hooks(lib):
     """The timing-only hooks (IBL_VN_PART runs part of the variable pass: its outputs are not decodes;
-    IBL_TRACE_WAVES / IBL_TRACE_FUSED allocate and sync per decode; IBL_DEBUG_SYNC syncs per launch) exist
-    only in diagnostic builds (-DIBL_DIAG=1, tools/variants.py diag / ftrace): the product library does not
-    even hold their names, so no environment variable can change what a decode computes or costs. The
-    create-time A/B knobs stay (read once per decoder)."""
+    IBL_TRACE_WAVES / IBL_TRACE_FUSED / IBL_TRACE_LAYERED allocate and sync per decode; IBL_DEBUG_SYNC syncs per
+    launch) exist only in diagnostic builds (-DIBL_DIAG=1, tools/variants.py diag / ftrace / laytrace): the product
+    library does not even hold their names, so no environment variable can change what a decode computes or costs.
+    The create-time A/B knobs stay (read once per decoder)."""
+    import glob
     from informationbottleneckdecodingldpc_amd import _build
     _build.build()
     blob = open(lib.LIB_PATH, "rb").read()
-    for name in (b"IBL_VN_PART", b"IBL_TRACE_WAVES", b"IBL_TRACE_FUSED", b"IBL_DEBUG_SYNC"):
+    for name in (b"IBL_VN_PART", b"IBL_TRACE_WAVES", b"IBL_TRACE_FUSED", b"IBL_TRACE_LAYERED", b"IBL_DEBUG_SYNC"):
         assert name not in blob, name
-    src = open(os.path.join(ROOT, "informationbottleneckdecodingldpc_amd", "csrc", "capi.hip")).read()
-    # every getenv outside the diagnostic blocks sits in a create-time function
+    files = sorted(glob.glob(os.path.join(ROOT, "informationbottleneckdecodingldpc_amd", "csrc", "capi_*.hip")))
+    assert [os.path.basename(f) for f in files] == ["capi_core.hip", "capi_encoder.hip", "capi_float.hip",
+                                                    "capi_ib.hip", "capi_layered.hip"]
+    src = "\n".join(open(f).read() for f in files)
+    # every read of the environment outside the diagnostic blocks sits in a create-time function: none in the
+    # decode entries, in any per-path decode function, or in the fused IB kernel's group-size rule
     body = re.sub(r"#if IBL_DIAG.*?#endif", "", src, flags=re.S)
-    decode_fns = re.findall(r"\nint (ibl_(?:ib|float)_decode)\(.*?\n}\n", body, flags=re.S)
-    assert len(decode_fns) == 2
-    for m in re.finditer(r"\nint (ibl_(?:ib|float)_decode)\(.*?\n}\n", body, flags=re.S):
-        assert "getenv" not in m.group(0), m.group(1)
-    ncw = re.search(r"int ib_fused_ncw\(.*?\n}\n", body, flags=re.S).group(0)
-    assert "getenv" not in ncw
+    decode_fns = ["ibl_ib_decode", "ib_decode_fused", "ib_decode_small", "ib_decode_fast", "ib_decode_generic",
+                  "ibl_float_decode", "float_decode_fused", "float_decode_small", "float_decode_passes",
+                  "ibl_layered_decode", "layered_decode_passes"]
+    assert sorted(set(re.findall(r"\nint (\w*_decode\w*)\(", body))) == sorted(decode_fns)
+    for fn in decode_fns + ["ib_fused_ncw"]:
+        found = re.findall(r"\nint %s\(.*?\n}\n" % fn, body, flags=re.S)
+        assert len(found) == 1, fn
+        for reader in ("getenv", "env_on", "small_batch_env", "fused_vwin"):   # host.h's readers of the environment
+            assert reader not in found[0], (fn, reader)
 
 
 def test_library_device_count_without_gpu(lib):
