@@ -30,7 +30,7 @@ extern "C" {
 #define IBL_VERSION 3
 
 enum { IBL_OK = 0, IBL_EINVAL = -1, IBL_EHIP = -2, IBL_ENOMEM = -3, IBL_EUNSUPPORTED = -4 };
-enum { IBL_U8 = 1, IBL_I32 = 2, IBL_F32 = 3, IBL_F64 = 4 };
+enum { IBL_U8 = 1, IBL_I32 = 2, IBL_F32 = 3, IBL_F64 = 4, IBL_I8 = 5 };   /* IBL_I8: fixed-point layered only */
 enum { IBL_MINSUM = 0, IBL_BP = 1 };
 enum { IBL_PATH_AUTO = 0, IBL_PATH_PASSES = 1, IBL_PATH_FUSED = 2 };
 enum { IBL_FLAG_FORCE_GENERIC = 1 };
@@ -334,6 +334,61 @@ int ibl_layered_decode(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int
                        int32_t out_dtype, int32_t early_stop, int32_t* d_iters, void* stream);
 int ibl_layered_geometry(const ibl_layered* h, int32_t B, int32_t* cw_per_group, int32_t* ngroups, int32_t* grid);
 void ibl_layered_destroy(ibl_layered* h);
+
+/*
+ * Layered min-sum, fixed point: a second arithmetic of the layered decoder above, integer throughout — 8-bit APP
+ * values, messages saturated at q_max (6 bits at most) — on the per-layer path over HBM.  Layers, the per-codeword
+ * early stop, the handle type and ibl_layered_decode / _path_in_use / _geometry / _destroy are those above.
+ *
+ * Parameters:  alpha16  int 0..16   normalisation in sixteenths (13 is the project's 0.8125)
+ *              beta_q   int 0..63   offset in integer units
+ *              q_max    int 1..63   message saturation (31: 6-bit messages)
+ *              scale    float, finite, > 0   integer units per LLR unit (2.0)
+ * The APP saturation is fixed at 127.
+ *
+ * Semantics, per codeword; all arithmetic in integers:
+ *   P[v] = clamp(rint(f32(llr[v]) * f32(scale)), -127, +127)
+ *           one rounded fp32 product, rint ties-to-even, clamped as a float before conversion
+ *           IBL_I8 input: P[v] = max(x, -127)
+ *   R[e] = 0
+ *   for it = 1..imax:
+ *     for each layer in order, each check c of the layer, its edges e = (c, v) in ascending column order:
+ *         T_e = P[v] - R[e]                        (not clamped)
+ *         Q_e = clamp(T_e, -q_max, +q_max);  neg_e = (T_e < 0)
+ *       m1 = min |Q_e| at the FIRST position attaining it;  m2 = min over the other positions;  s = XOR neg_e
+ *       for each e:  mag = (e is that first position) ? m2 : m1
+ *                    mag = max(((alpha16 * mag + 8) >> 4) - beta_q, 0)
+ *                    R[e] = (s ^ neg_e) ? -mag : mag
+ *                    P[v] = clamp(T_e + R[e], -127, +127)
+ *     early stop, per codeword: as the fp32 decoder (x = P < 0; the first zero syndrome freezes out and iters)
+ *   out:  IBL_I8 -> P;   IBL_F32 -> f32(P) / f32(scale)   (one correctly rounded fp32 division)
+ * Precondition: no channel LLR is NaN.  P is updated from the unclamped T, not from Q as in the fp32 semantics:
+ * the usual hardware form, which keeps the 8-bit APP range useful when q_max is small.
+ *
+ * ibl_layered_create_fixed  validates as ibl_layered_create_path does.  Out-of-range parameters, imax or max_batch
+ *   < 1 and an unknown path are IBL_EINVAL; IBL_PATH_FUSED is IBL_EUNSUPPORTED (the fixed-point fused kernel is not
+ *   built); IBL_PATH_PASSES and IBL_PATH_AUTO give the per-layer kernels.  The parameters are judged before the
+ *   graph, so these refusals need no device.
+ *   Layout: a lane owns 4 consecutive codewords and a wave updates one check for 256.  The handle owns, allocated at
+ *   create for ldb = max_batch rounded up to 256 codewords, the APP values [N][ldb] int8 and ONE 32-bit state word
+ *   per check and codeword [n_c][ldb] (corrected m2 << 26 | corrected m1 << 20 | first argmin position << 16 | the
+ *   sign bits of R, edge k at bit k), and, per 64 codewords as on the fp32 per-layer path, the packed hard decisions
+ *   (one bit per variable and codeword), a 64-bit mask of finished and one of unsatisfied codewords, and a counter:
+ *   memory  N ldb + 4 n_c ldb + 8 N ceil(max_batch / 64) + 64 ldb / 256 + 4  bytes, about N + 4 n_c + N / 8 per
+ *   codeword (DVB-S2 N = 64800 rate 1/2: 202.5 KB per codeword, 1.66 GB at 8192, against 5.3 GB in fp32).  An
+ *   iteration moves 2 E + 8 n_c bytes per codeword (fp32: 8 E + 24 n_c).
+ *   ibl_layered_decode on such a handle takes llr_dtype and out_dtype in {IBL_F32, IBL_I8} in any combination
+ *   (anything else is IBL_EINVAL); d_out may be d_llr when the dtypes match.  It enqueues the launch chain of the
+ *   fp32 per-layer path (staging, n_layers launches per iteration, pack / syndrome / finalise after every iteration
+ *   but the last when early_stop is set, output) with the same guarantees: no allocation, no host synchronisation,
+ *   no read-back; finished and padding codewords store nothing that reaches the caller; a finished codeword's values
+ *   are frozen at its stop iteration.
+ * ibl_layered_is_fixed  *fixed = 1 for a handle of ibl_layered_create_fixed, 0 otherwise.
+ */
+int ibl_layered_create_fixed(const ibl_graph* g, int32_t n_layers, const int32_t* layer_ptr,
+                             const int32_t* layer_checks, int32_t imax, int32_t alpha16, int32_t beta_q, int32_t q_max,
+                             float scale, int32_t max_batch, int32_t path, ibl_layered** out);
+int ibl_layered_is_fixed(const ibl_layered* h, int32_t* fixed);
 
 /*
  * Error counter.  Replaces return_errors_all_zero (discrete_LDPC_decoder_irreg.py:343-349,

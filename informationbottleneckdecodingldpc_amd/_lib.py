@@ -17,7 +17,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IBLDPC_LIB") or os.path.join(_HERE, "libibldpc.so")
 
 IBL_OK, IBL_EINVAL, IBL_EHIP, IBL_ENOMEM, IBL_EUNSUPPORTED = 0, -1, -2, -3, -4
-IBL_U8, IBL_I32, IBL_F32, IBL_F64 = 1, 2, 3, 4
+IBL_U8, IBL_I32, IBL_F32, IBL_F64, IBL_I8 = 1, 2, 3, 4, 5
 IBL_MINSUM, IBL_BP = 0, 1
 IBL_FLAG_FORCE_GENERIC = 1
 IBL_PATH_AUTO, IBL_PATH_PASSES, IBL_PATH_FUSED = 0, 1, 2
@@ -44,7 +44,7 @@ EXPORTS = [
     "ibl_shard_range", "ibl_comm_unique_id", "ibl_comm_create", "ibl_comm_broadcast", "ibl_comm_allreduce_sum_i64",
     "ibl_comm_destroy",
     "ibl_layers_validate", "ibl_layered_create", "ibl_layered_decode", "ibl_layered_geometry", "ibl_layered_destroy",
-    "ibl_layered_create_path", "ibl_layered_path_in_use",
+    "ibl_layered_create_path", "ibl_layered_path_in_use", "ibl_layered_create_fixed", "ibl_layered_is_fixed",
 ]
 IBL_COMM_ID_BYTES = 128
 
@@ -131,6 +131,9 @@ def load():
     L.ibl_layered_create_path.argtypes = [_vp, _i32, _i32p, _i32p, _i32, _f32, _f32, _f32, _i32, _i32, _i32,
                                           ctypes.POINTER(_vp)]
     L.ibl_layered_path_in_use.argtypes = [_vp, ctypes.POINTER(_i32)]
+    L.ibl_layered_create_fixed.argtypes = [_vp, _i32, _i32p, _i32p, _i32, _i32, _i32, _i32, _f32, _i32, _i32,
+                                           ctypes.POINTER(_vp)]
+    L.ibl_layered_is_fixed.argtypes = [_vp, ctypes.POINTER(_i32)]
     L.ibl_layered_decode.argtypes =[_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]
     L.ibl_layered_geometry.argtypes = [_vp, _i32, ctypes.POINTER(_i32), ctypes.POINTER(_i32), ctypes.POINTER(_i32)]
     L.ibl_layered_destroy.argtypes = [_vp]

@@ -1,5 +1,6 @@
 // C ABI (include/ibldpc.h): the layered normalised / offset min-sum decoder (layered_plan.h, layered_kernels.hip):
-// the fused on-chip kernel for codes whose codeword state fits the LDS, the per-layer path over HBM otherwise.
+// the fused on-chip kernel for codes whose codeword state fits the LDS, the per-layer path over HBM otherwise, and
+// the fixed-point arithmetic on the per-layer path (ibl_layered_create_fixed).
 #include <cmath>
 #include <cstring>
 
@@ -25,6 +26,12 @@ struct ibl_layered {
   DevBuf<uint64_t> done, unsat, bits;
   DevBuf<int32_t> running;
   int32_t syn_packed = 1;   // syndrome form (IBL_LAY_SYNDROME=gather|packed at create; DESIGN.md for the numbers)
+  // fixed point (ibl_layered_create_fixed; fused = 0): rec, layer_slot, the masks, the counter and bits as above,
+  // the int8 APP rows and the state words of layered_plan.h fix_bytes(n_v, n_c, max_batch)
+  int32_t fixed = 0, alpha16 = 16, beta_q = 0, q_max = 31;
+  float scale = 2.f;
+  DevBuf<int8_t> P8;
+  DevBuf<uint32_t> S;
 };
 
 namespace {
@@ -91,6 +98,25 @@ int layered_decode_passes(ibl_layered* h, const float* d_llr, int32_t B, float* 
   HIPCHK(launch_lay_stage_out(a, d_out, s));
   return IBL_OK;
 }
+
+int layered_run_fixed(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out, int32_t out_dtype,
+                      int32_t early_stop, int32_t* d_iters, hipStream_t s) {
+  const ibl_graph* g = h->g;
+  LayFixArgs a{};
+  a.P = h->P8; a.S = h->S; a.done = h->done; a.unsat = h->unsat; a.running = h->running; a.bits = h->bits;
+  a.rec = h->rec; a.cols = g->csr_cols; a.iters = d_iters;
+  a.alpha16 = h->alpha16; a.beta_q = h->beta_q; a.q_max = h->q_max; a.scale = h->scale;
+  a.n_v = g->n_v; a.n_c = g->n_c; a.B = B; a.ntiles = pass_tiles(B); a.ntiles4 = fix_tiles(B);
+  HIPCHK(launch_layfix_stage_in(a, d_llr, llr_dtype, h->imax, s));
+  const int32_t n_layers = (int32_t)h->layer_slot.size() - 1;
+  for (int32_t it = 1; it <= h->imax; ++it) {
+    for (int32_t l = 0; l < n_layers; ++l)
+      HIPCHK(launch_layfix_layer(a, h->layer_slot[l], h->layer_slot[l + 1] - h->layer_slot[l], s));
+    if (early_stop && it < h->imax) HIPCHK(launch_layfix_stop(a, it, s));
+  }
+  HIPCHK(launch_layfix_stage_out(a, d_out, out_dtype, s));
+  return IBL_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -153,6 +179,56 @@ int ibl_layered_create_path(const ibl_graph* g, int32_t n_layers, const int32_t*
   return IBL_OK;
 }
 
+int ibl_layered_create_fixed(const ibl_graph* g, int32_t n_layers, const int32_t* layer_ptr,
+                             const int32_t* layer_checks, int32_t imax, int32_t alpha16, int32_t beta_q, int32_t q_max,
+                             float scale, int32_t max_batch, int32_t path, ibl_layered** out) {
+  if (!out) return fail(IBL_EINVAL, "out is NULL");
+  *out = nullptr;
+  if (imax < 1 || max_batch < 1) return fail(IBL_EINVAL, "imax and max_batch must be >= 1");
+  if (!fix_params_ok(alpha16, beta_q, q_max))
+    return fail(IBL_EINVAL, "alpha16 must lie in [0, 16], beta_q in [0, 63], q_max in [1, 63]");
+  if (!(scale > 0.f) || std::isinf(scale)) return fail(IBL_EINVAL, "scale must be finite and > 0");
+  if (int rc = check_path(path)) return rc;
+  if (path == IBL_PATH_FUSED)
+    return fail(IBL_EUNSUPPORTED, "the fixed-point fused kernel is not built: use IBL_PATH_PASSES or IBL_PATH_AUTO");
+  if (!g) return fail(IBL_EINVAL, "graph is NULL");
+  const std::vector<int32_t> ip = graph_indptr(g);
+  int rc = ibl_layers_validate(g->n_v, g->n_c, ip.data(), g->h_cols.data(), n_layers, layer_ptr, layer_checks);
+  if (rc) return rc;
+  LayeredPassPlan pl;
+  plan_layered_passes(g->n_c, ip.data(), n_layers, layer_ptr, layer_checks, &pl);
+  const int64_t rows = std::max(g->n_v, g->n_c);
+  if (fix_grid(pl.max_layer, max_batch) > 0x7fffffffll ||
+      pass_grid(pass_pack_runs((int32_t)rows), max_batch) > 0x7fffffffll ||
+      (rows * fix_tiles(max_batch) + kLayPassWaves - 1) / kLayPassWaves > 0x7fffffffll)
+    return fail(IBL_EINVAL, "max_batch is too large for the per-layer kernels' grids");
+  HIPCHK(hipSetDevice(g->device));
+  size_t priv = 0, priv_stop = 0;
+  HIPCHK(layfix_private_bytes(&priv));
+  HIPCHK(lay_pass_private_bytes(&priv_stop));   // the shared syndrome and finalise kernels
+  if ((rc = refuse_private(std::max(priv, priv_stop), "a fixed-point layered kernel has a ",
+                           "-byte private segment (register spill): rebuild required")))
+    return rc;
+  std::unique_ptr<ibl_layered> h(new ibl_layered());
+  h->g = g; h->imax = imax; h->max_batch = max_batch;
+  h->fused = 0; h->fixed = 1;
+  h->alpha16 = alpha16; h->beta_q = beta_q; h->q_max = q_max; h->scale = scale;
+  h->layer_slot = pl.layer_slot;
+  const LayeredFixBytes by = fix_bytes(g->n_v, g->n_c, max_batch);
+  if ((rc = h->rec.upload(pl.rec)) || (rc = h->P8.alloc(by.P)) || (rc = h->S.alloc(by.state / 4)) ||
+      (rc = h->done.alloc(by.mask / 8)) || (rc = h->unsat.alloc(by.mask / 8)) || (rc = h->running.alloc(1)) ||
+      (rc = h->bits.alloc(by.bits / 8)))
+    return rc;
+  *out = h.release();
+  return IBL_OK;
+}
+
+int ibl_layered_is_fixed(const ibl_layered* h, int32_t* fixed) {
+  if (!h || !fixed) return fail(IBL_EINVAL, "NULL argument");
+  *fixed = h->fixed;
+  return IBL_OK;
+}
+
 int ibl_layered_geometry(const ibl_layered* h, int32_t B, int32_t* cw_per_group, int32_t* ngroups, int32_t* grid) {
   if (!h || !cw_per_group || !ngroups || !grid) return fail(IBL_EINVAL, "NULL argument");
   if (B < 1 || B > h->max_batch) return fail(IBL_EINVAL, "B must lie in [1, max_batch]");
@@ -175,6 +251,13 @@ int ibl_layered_decode(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int
                        int32_t out_dtype, int32_t early_stop, int32_t* d_iters, void* stream) {
   if (!h) return fail(IBL_EINVAL, "decoder is NULL");
   if (B < 1 || B > h->max_batch) return fail(IBL_EINVAL, "B must lie in [1, max_batch]");
+  if (h->fixed) {
+    if ((llr_dtype != kF32 && llr_dtype != kI8) || (out_dtype != kF32 && out_dtype != kI8))
+      return fail(IBL_EINVAL, "LLR dtypes of a fixed-point decoder must be IBL_F32 or IBL_I8");
+    if (!d_llr || !d_out) return fail(IBL_EINVAL, "NULL buffer");
+    HIPCHK(hipSetDevice(h->g->device));
+    return layered_run_fixed(h, d_llr, llr_dtype, B, d_out, out_dtype, early_stop, d_iters, (hipStream_t)stream);
+  }
   if (llr_dtype == kF64 || out_dtype == kF64) return fail(IBL_EUNSUPPORTED, "the layered decoder is fp32 only");
   if (llr_dtype != kF32 || out_dtype != kF32) return fail(IBL_EINVAL, "LLR dtypes must be IBL_F32");
   if (!d_llr || !d_out) return fail(IBL_EINVAL, "NULL buffer");

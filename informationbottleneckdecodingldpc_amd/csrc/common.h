@@ -65,7 +65,7 @@ constexpr int kTP = 16;           // IB fast path: alphabet padded to 16 (entry 
 constexpr int kShards = 64;       // early-stop flag words per iteration (one wave load)
 constexpr int kLdsBytes = 160 * 1024;
 
-enum Dtype : int32_t { kU8 = 1, kI32 = 2, kF32 = 3, kF64 = 4 };
+enum Dtype : int32_t { kU8 = 1, kI32 = 2, kF32 = 3, kF64 = 4, kI8 = 5 };
 
 // the C ABI's per-thread last error (capi_core.hip; ibl_last_error): other translation units report through it
 int set_error(int code, const char* msg);
@@ -393,5 +393,31 @@ hipError_t launch_lay_syndrome(const LayPassArgs& a, int packed, hipStream_t s);
 hipError_t launch_lay_finalise(const LayPassArgs& a, int it, hipStream_t s);
 hipError_t launch_lay_stage_out(const LayPassArgs& a, float* out, hipStream_t s);
 hipError_t lay_pass_private_bytes(size_t* bytes);
+
+// Fixed-point per-layer path (include/ibldpc.h "Layered min-sum, fixed point"): a lane owns 4 consecutive
+// codewords, rows [row][ldb] with ldb = ntiles4 * 256 (layered_plan.h "fixed point"). The masks, the packed hard
+// decisions, `running`, `rec` and `cols` are those of LayPassArgs, per 64 codewords, so the packed syndrome and the
+// finalise kernel of the fp32 path serve both.
+struct LayFixArgs {
+  int8_t* P;                // [n_v][ldb] APP values, one byte per codeword
+  uint32_t* S;              // [n_c][ldb] per slot: m2' << 26 | m1' << 20 | argmin position << 16 | sign bits of R
+  uint64_t* done;           // [4 ntiles4] as LayPassArgs::done; the words past ntiles are all ones
+  uint64_t* unsat;          // [4 ntiles4]
+  int32_t* running;
+  uint64_t* bits;           // [ntiles][n_v]
+  const int32_t* rec;
+  const int32_t* cols;
+  int32_t* iters;           // [B] or nullptr
+  int32_t alpha16, beta_q, q_max;
+  float scale;
+  int32_t n_v, n_c, B, ntiles, ntiles4;   // tiles of 64 (masks, bits) and of 256 (rows) codewords of B
+};
+// llr / out: [N][B] of dtype kF32 (quantised on the way in, divided by scale on the way out) or kI8
+hipError_t launch_layfix_stage_in(const LayFixArgs& a, const void* llr, int32_t dtype, int imax, hipStream_t s);
+hipError_t launch_layfix_layer(const LayFixArgs& a, int slot0, int n_checks, hipStream_t s);
+// pack the hard decisions of the int8 rows, XOR the packed words per check, finish the satisfied codewords (three)
+hipError_t launch_layfix_stop(const LayFixArgs& a, int it, hipStream_t s);
+hipError_t launch_layfix_stage_out(const LayFixArgs& a, void* out, int32_t dtype, hipStream_t s);
+hipError_t layfix_private_bytes(size_t* bytes);
 
 }  // namespace ibl

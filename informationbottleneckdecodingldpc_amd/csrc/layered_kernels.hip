@@ -524,4 +524,269 @@ hipError_t lay_pass_private_bytes(size_t* bytes) {
   return hipSuccess;
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Fixed point, per-layer path over HBM (include/ibldpc.h "Layered min-sum, fixed point").
+//
+// Integer arithmetic throughout, plain C++ per codeword. A lane owns 4 consecutive codewords: P[n_v][ldb] int8 is
+// one dword per row and lane, the check state S[n_c][ldb] one 32-bit word per codeword (fix_state_word: two 6-bit
+// corrected magnitudes, the first argmin position, the sign bits of R with edge k at bit k), a lane's four words one
+// 16-byte access; ldb = 256 ntiles4. One launch per layer, a wave item (check of the layer, tile of 256
+// codewords); the check's record and variable indices are wave-uniform scalar loads as in lay_layer.
+//
+// The stop is the fp32 path's: done / unsat masks and packed hard decisions per 64 codewords (layfix_pack makes the
+// latter from the int8 rows, lay_syndrome_packed and lay_finalise are launched unchanged). The mask words of a
+// tile of 256 past the batch are all ones. A lane whose four codewords are finished leaves before its first vector
+// load; a lane with some finished stores their bytes and state words back unchanged.
+namespace {
+
+__device__ __forceinline__ uint32_t layfix_sign_nibble(uint32_t w) {   // bit i = sign of byte i
+  return (((w >> 7) & 0x01010101u) * 0x01020408u) >> 24;
+}
+
+// finished bits of the lane's 4 codewords (bit j: codeword 4 lane + j of the tile); *all: the whole tile is finished
+__device__ __forceinline__ uint32_t layfix_finished(const uint64_t* done, int tile4, int lane, bool* all) {
+  const uint64_t d0 = lay_mask(done, 4 * tile4), d1 = lay_mask(done, 4 * tile4 + 1),
+                 d2 = lay_mask(done, 4 * tile4 + 2), d3 = lay_mask(done, 4 * tile4 + 3);
+  *all = (d0 & d1 & d2 & d3) == ~0ull;
+  const int sub = lane >> 4;
+  const uint64_t dm = sub == 0 ? d0 : sub == 1 ? d1 : sub == 2 ? d2 : d3;
+  return (uint32_t)(dm >> ((lane & 15) * 4)) & 0xFu;
+}
+
+// One check of degree D for the lane's 4 codewords (bytes at `col` of every P row, words at srow of S).
+template <int D>
+__device__ __forceinline__ void layfix_cn_rows(const LayFixArgs& a, int e0, size_t srow, size_t col, size_t ldb,
+                                               uint32_t fin) {
+  size_t v[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) v[k] = (size_t)sload(a.cols, e0 + k) * ldb + col;
+  uint32_t p[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) p[k] = *reinterpret_cast<const uint32_t*>(a.P + v[k]);
+  const uint4 st = *reinterpret_cast<const uint4*>(a.S + srow);
+  uint32_t w[kLayFixCw] = {st.x, st.y, st.z, st.w};
+  const int alpha16 = a.alpha16, beta = a.beta_q, qm = a.q_max;
+#pragma unroll
+  for (int j = 0; j < kLayFixCw; ++j) {
+    if ((fin >> j) & 1u) continue;   // frozen at its stop iteration
+    const uint32_t ws = w[j];
+    const int m1o = (int)((ws >> 20) & 63u), m2o = (int)(ws >> 26);
+    const uint32_t poso = (ws >> 16) & 15u;
+    int t[D];
+    int m1 = kLayFixQMax + 1, m2 = kLayFixQMax + 1;
+    uint32_t pos = 0, neg = 0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      const int mag = (uint32_t)k == poso ? m2o : m1o;
+      const int r = ((ws >> k) & 1u) ? -mag : mag;
+      const int x = (int)(int8_t)(p[k] >> (8 * j)) - r;
+      t[k] = x;
+      neg |= ((uint32_t)x >> 31) << k;
+      const int m = min(abs(x), qm);
+      pos = m < m1 ? (uint32_t)k : pos;   // moves only on m < m1: the first position attaining the minimum
+      m2 = min(m2, max(m1, m));
+      m1 = min(m1, m);
+    }
+    const int m1n = max(((alpha16 * m1 + 8) >> 4) - beta, 0), m2n = max(((alpha16 * m2 + 8) >> 4) - beta, 0);
+    const uint32_t sg = ((__popc(neg) & 1) ? ~neg : neg) & ((1u << D) - 1u);   // s ^ neg_e: R[e] is negated
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      const int mag = (uint32_t)k == pos ? m2n : m1n;
+      const int r = ((sg >> k) & 1u) ? -mag : mag;
+      const int pn = min(max(t[k] + r, -kLayFixApp), kLayFixApp);
+      p[k] = (p[k] & ~(0xFFu << (8 * j))) | ((uint32_t)(pn & 0xFF) << (8 * j));
+    }
+    w[j] = fix_state_word((uint32_t)m1n, (uint32_t)m2n, pos, sg);
+  }
+#pragma unroll
+  for (int k = 0; k < D; ++k) *reinterpret_cast<uint32_t*>(a.P + v[k]) = p[k];
+  *reinterpret_cast<uint4*>(a.S + srow) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+}  // namespace
+
+// P = the quantised (IBL_F32) or copied (IBL_I8, -128 -> -127) channel values, padding codewords 0; state words 0;
+// masks, counter and iters reset. item = (row < max(n_v, n_c), tile of 256)
+__global__ __launch_bounds__(64 * kLayPassWaves) void layfix_stage_in(const LayFixArgs a, const void* __restrict__ llr,
+                                                                      int dtype, int imax) {
+  const int lane = (int)(threadIdx.x & 63u);
+  const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + (int64_t)(threadIdx.x >> 6);
+  const int64_t rows = a.n_v > a.n_c ? a.n_v : a.n_c;
+  if (item >= rows * a.ntiles4) return;
+  const int tile = (int)(item % a.ntiles4);
+  const int64_t row = item / a.ntiles4;
+  const size_t ldb = (size_t)a.ntiles4 * kLayFixTile;
+  const int b0 = tile * kLayFixTile + kLayFixCw * lane;
+  const size_t at = (size_t)row * ldb + (size_t)b0;
+  if (row < a.n_v) {
+    uint32_t w = 0;
+#pragma unroll
+    for (int j = 0; j < kLayFixCw; ++j) {
+      int x = 0;
+      if (b0 + j < a.B) {
+        const size_t src = (size_t)row * (size_t)a.B + (size_t)(b0 + j);
+        if (dtype == kF32) {
+          // one rounded product, rint to even, clamped as a float, then converted
+          const float f = __builtin_rintf(static_cast<const float*>(llr)[src] * a.scale);
+          x = (int)fminf(fmaxf(f, -(float)kLayFixApp), (float)kLayFixApp);
+        } else {
+          x = max((int)static_cast<const int8_t*>(llr)[src], -kLayFixApp);
+        }
+      }
+      w |= (uint32_t)(x & 0xFF) << (8 * j);
+    }
+    *reinterpret_cast<uint32_t*>(a.P + at) = w;
+  }
+  if (row < a.n_c) *reinterpret_cast<uint4*>(a.S + at) = make_uint4(0u, 0u, 0u, 0u);
+  if (row == 0) {
+    if (a.iters) {
+#pragma unroll
+      for (int j = 0; j < kLayFixCw; ++j)
+        if (b0 + j < a.B) a.iters[b0 + j] = imax;
+    }
+    if (lane < kLayFixCw) {
+      const int t64 = kLayFixCw * tile + lane;
+      const int left = a.B - t64 * kLayTile;   // <= 0: a mask word past the batch
+      a.done[t64] = left >= kLayTile ? 0ull : left <= 0 ? ~0ull : ~0ull << left;
+      a.unsat[t64] = 0ull;
+    }
+    if (lane == 0 && tile == 0) *a.running = a.B;
+  }
+}
+
+// item = (check slot0 + c of the layer, tile of 256), tile fastest
+__global__ __launch_bounds__(64 * kLayPassWaves) void layfix_layer(const LayFixArgs a, int slot0, int n_checks) {
+  if (sload(a.running, 0) == 0) return;
+  const int lane = (int)(threadIdx.x & 63u);
+  const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (item >= (int64_t)n_checks * a.ntiles4) return;
+  const int tile = (int)(item % a.ntiles4);
+  const int slot = slot0 + (int)(item / a.ntiles4);
+  bool all;
+  const uint32_t fin = layfix_finished(a.done, tile, lane, &all);
+  if (all) return;             // wave-uniform: the whole tile is finished
+  if (fin == 0xFu) return;     // the lane's four codewords are finished (or padding)
+  const int e0 = sload(a.rec, 2 * slot), d = sload(a.rec, 2 * slot + 1);
+  const size_t ldb = (size_t)a.ntiles4 * kLayFixTile;
+  const size_t col = (size_t)tile * kLayFixTile + (size_t)(kLayFixCw * lane);
+  const size_t srow = (size_t)slot * ldb + col;
+  switch (d) {
+#define LAY_CASE(D) case D: layfix_cn_rows<D>(a, e0, srow, col, ldb, fin); break;
+    LAY_CASE(2) LAY_CASE(3) LAY_CASE(4) LAY_CASE(5) LAY_CASE(6) LAY_CASE(7) LAY_CASE(8) LAY_CASE(9)
+    LAY_CASE(10) LAY_CASE(11) LAY_CASE(12) LAY_CASE(13) LAY_CASE(14) LAY_CASE(15) LAY_CASE(16)
+#undef LAY_CASE
+    default: break;
+  }
+}
+
+// Hard decisions of the int8 rows in lay_pack's form: bits[tile][v] bit b = (P[v][64 tile + b] < 0), finished
+// codewords 0. item = (run of 64 variables, tile of 64); lane i reads the 64 bytes of variable v0 + i.
+__global__ __launch_bounds__(64 * kLayPassWaves) void layfix_pack(const LayFixArgs a) {
+  if (sload(a.running, 0) == 0) return;
+  const int lane = (int)(threadIdx.x & 63u);
+  const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int nruns = (a.n_v + kLayTile - 1) / kLayTile;
+  if (item >= (int64_t)nruns * a.ntiles) return;
+  const int tile = (int)(item % a.ntiles);
+  const int run = (int)(item / a.ntiles);
+  const uint64_t dm = lay_mask(a.done, tile);
+  if (dm == ~0ull) return;
+  const int v = run * kLayTile + lane;
+  if (v >= a.n_v) return;
+  const size_t ldb = (size_t)a.ntiles4 * kLayFixTile;
+  const uint4* src = reinterpret_cast<const uint4*>(a.P + (size_t)v * ldb + (size_t)tile * kLayTile);
+  uint64_t word = 0ull;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const uint4 x = src[q];
+    const uint32_t n = layfix_sign_nibble(x.x) | (layfix_sign_nibble(x.y) << 4) | (layfix_sign_nibble(x.z) << 8) |
+                       (layfix_sign_nibble(x.w) << 12);
+    word |= (uint64_t)n << (16 * q);
+  }
+  a.bits[(size_t)tile * (size_t)a.n_v + (size_t)v] = word & ~dm;
+}
+
+// out[row][b] = P[row][b] (IBL_I8) or f32(P) / scale (IBL_F32) for b < B; item = (row < n_v, tile of 256)
+__global__ __launch_bounds__(64 * kLayPassWaves) void layfix_stage_out(const LayFixArgs a, void* __restrict__ out,
+                                                                       int dtype) {
+  const int lane = (int)(threadIdx.x & 63u);
+  const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + (int64_t)(threadIdx.x >> 6);
+  if (item >= (int64_t)a.n_v * a.ntiles4) return;
+  const int tile = (int)(item % a.ntiles4);
+  const int64_t row = item / a.ntiles4;
+  const int b0 = tile * kLayFixTile + kLayFixCw * lane;
+  if (b0 >= a.B) return;
+  const uint32_t w = *reinterpret_cast<const uint32_t*>(a.P + (size_t)row * (size_t)a.ntiles4 * kLayFixTile + (size_t)b0);
+#pragma unroll
+  for (int j = 0; j < kLayFixCw; ++j) {
+    if (b0 + j >= a.B) break;
+    const int x = (int)(int8_t)(w >> (8 * j));
+    const size_t dst = (size_t)row * (size_t)a.B + (size_t)(b0 + j);
+    if (dtype == kF32) static_cast<float*>(out)[dst] = (float)x / a.scale;
+    else static_cast<int8_t*>(out)[dst] = (int8_t)x;
+  }
+}
+
+namespace {
+bool layfix_args_ok(const LayFixArgs& a) {
+  return a.P && a.S && a.done && a.unsat && a.running && a.bits && a.rec && a.cols && a.n_v >= 1 && a.n_c >= 1 &&
+         a.B >= 1 && a.ntiles == pass_tiles(a.B) && a.ntiles4 == fix_tiles(a.B) &&
+         fix_params_ok(a.alpha16, a.beta_q, a.q_max) && a.scale > 0.f;
+}
+bool layfix_dtype_ok(int32_t dtype) { return dtype == kF32 || dtype == kI8; }
+}  // namespace
+
+hipError_t launch_layfix_stage_in(const LayFixArgs& a, const void* llr, int32_t dtype, int imax, hipStream_t s) {
+  if (!layfix_args_ok(a) || !llr || !layfix_dtype_ok(dtype)) return hipErrorInvalidValue;
+  LayFixArgs args = a;
+  void* p[] = {&args, (void*)&llr, (void*)&dtype, (void*)&imax};
+  return lay_pass_launch((const void*)layfix_stage_in, (int64_t)std::max(a.n_v, a.n_c) * a.ntiles4, p, s);
+}
+
+hipError_t launch_layfix_layer(const LayFixArgs& a, int slot0, int n_checks, hipStream_t s) {
+  if (!layfix_args_ok(a) || slot0 < 0 || n_checks < 0 || (int64_t)slot0 + n_checks > a.n_c)
+    return hipErrorInvalidValue;
+  if (n_checks == 0) return hipSuccess;
+  LayFixArgs args = a;
+  void* p[] = {&args, (void*)&slot0, (void*)&n_checks};
+  return lay_pass_launch((const void*)layfix_layer, fix_items(n_checks, a.B), p, s);
+}
+
+hipError_t launch_layfix_stop(const LayFixArgs& a, int it, hipStream_t s) {
+  if (!layfix_args_ok(a)) return hipErrorInvalidValue;
+  LayFixArgs args = a;
+  void* p[] = {&args};
+  hipError_t e = lay_pass_launch((const void*)layfix_pack, pass_items(pass_pack_runs(a.n_v), a.B), p, s);
+  if (e != hipSuccess) return e;
+  // the fp32 path's kernels read only what the two paths share
+  LayPassArgs f{};
+  f.done = a.done; f.unsat = a.unsat; f.running = a.running; f.bits = a.bits; f.rec = a.rec; f.cols = a.cols;
+  f.iters = a.iters; f.n_v = a.n_v; f.n_c = a.n_c; f.B = a.B; f.ntiles = a.ntiles;
+  void* ps[] = {&f};
+  e = lay_pass_launch((const void*)lay_syndrome_packed, pass_items(pass_pack_runs(a.n_c), a.B), ps, s);
+  if (e != hipSuccess) return e;
+  void* pf[] = {&f, (void*)&it};
+  return lay_pass_launch((const void*)lay_finalise, a.ntiles, pf, s);
+}
+
+hipError_t launch_layfix_stage_out(const LayFixArgs& a, void* out, int32_t dtype, hipStream_t s) {
+  if (!layfix_args_ok(a) || !out || !layfix_dtype_ok(dtype)) return hipErrorInvalidValue;
+  LayFixArgs args = a;
+  void* p[] = {&args, (void*)&out, (void*)&dtype};
+  return lay_pass_launch((const void*)layfix_stage_out, (int64_t)a.n_v * a.ntiles4, p, s);
+}
+
+// the largest private (scratch) segment over the fixed-point kernels: built to run without one
+hipError_t layfix_private_bytes(size_t* bytes) {
+  *bytes = 0;
+  for (const void* f : {(const void*)layfix_stage_in, (const void*)layfix_layer, (const void*)layfix_pack,
+                        (const void*)layfix_stage_out}) {
+    hipFuncAttributes fa;
+    const hipError_t e = hipFuncGetAttributes(&fa, f);
+    if (e != hipSuccess) return e;
+    *bytes = std::max(*bytes, (size_t)fa.localSizeBytes);
+  }
+  return hipSuccess;
+}
+
 }  // namespace ibl

@@ -2,7 +2,8 @@
 //
 // Built into libibldpc.so (capi_layered.hip includes this header) and, with AddressSanitizer and
 // UndefinedBehaviorSanitizer, into the CPU-only checkers tests/asan/layered_plan_check.cpp
-// (tests/test_cpu_layered.py) and tests/asan/layered_pass_plan_check.cpp (tests/test_cpu_layered_passes.py).
+// (tests/test_cpu_layered.py), tests/asan/layered_pass_plan_check.cpp (tests/test_cpu_layered_passes.py) and
+// tests/asan/layered_fixed_plan_check.cpp (tests/test_cpu_layered_fixed.py).
 //
 // A layer is a set of checks no two of which share a variable; the layers are disjoint, cover every check and
 // are decoded in order (include/ibldpc.h "Layered min-sum"). The device plan cuts every layer into tasks of up
@@ -199,6 +200,53 @@ inline void plan_layered_passes(int32_t n_c, const int32_t* indptr, int32_t n_la
       pl->rec.push_back(indptr[c + 1] - indptr[c]);
     }
   }
+}
+
+// ---- fixed point, per-layer path (include/ibldpc.h "Layered min-sum, fixed point"; checked by
+// tests/asan/layered_fixed_plan_check.cpp) ------------------------------------------------------------------------
+// A lane owns 4 consecutive codewords: P[n_v][ldb] int8 (one dword per row and lane) and one 32-bit state word per
+// check and codeword S[n_c][ldb] (a lane's four words one 16-byte load), ldb a multiple of kLayFixTile. A wave
+// item is (check of the layer, tile of kLayFixTile codewords); the plan (LayeredPassPlan), the masks of finished
+// and unsatisfied codewords and the packed hard decisions stay per kLayTile codewords, the mask arrays padded to
+// whole tiles of kLayFixTile (the padding words all ones: finished).
+constexpr int kLayFixCw = 4;                              // codewords per lane
+constexpr int kLayFixTile = kLayFixCw * kLayTile;         // codewords per wave item
+constexpr int kLayFixApp = 127, kLayFixQMax = 63, kLayFixAlphaOne = 16;
+
+inline int32_t fix_tiles(int32_t B) { return pass_tiles(B, kLayFixTile); }
+inline int64_t fix_ldb(int32_t B) { return pass_ldb(B, kLayFixTile); }
+// words of each mask array: the kLayTile tiles of whole tiles of kLayFixTile
+inline int64_t fix_mask_words(int32_t B) { return (int64_t)fix_tiles(B) * kLayFixCw; }
+inline int64_t fix_items(int32_t n_checks, int32_t B) { return pass_items(n_checks, B, kLayFixTile); }
+inline int64_t fix_grid(int32_t n_checks, int32_t B) { return pass_grid(n_checks, B, kLayFixTile); }
+
+struct LayeredFixBytes {
+  size_t P = 0;       // [n_v][ldb] int8
+  size_t state = 0;   // [n_c][ldb] 32-bit words
+  size_t mask = 0;    // each of finished, unsatisfied
+  size_t counter = 0;
+  size_t bits = 0;    // one 64-bit word per variable and tile of kLayTile
+  size_t total = 0;   // P + state + 2 mask + counter + bits
+};
+inline LayeredFixBytes fix_bytes(int32_t n_v, int32_t n_c, int32_t max_batch) {
+  LayeredFixBytes b;
+  const size_t ldb = (size_t)fix_ldb(max_batch);
+  b.P = (size_t)n_v * ldb;
+  b.state = (size_t)4 * (size_t)n_c * ldb;
+  b.mask = (size_t)8 * (size_t)fix_mask_words(max_batch);
+  b.counter = 4;
+  b.bits = (size_t)8 * (size_t)n_v * (size_t)pass_tiles(max_batch);
+  b.total = b.P + b.state + 2 * b.mask + b.counter + b.bits;
+  return b;
+}
+// ibl_layered_create_fixed's ranges: alpha16 in [0, 16], beta_q in [0, 63], q_max in [1, 63]
+constexpr bool fix_params_ok(int32_t alpha16, int32_t beta_q, int32_t q_max) {
+  return alpha16 >= 0 && alpha16 <= kLayFixAlphaOne && beta_q >= 0 && beta_q <= kLayFixQMax && q_max >= 1 &&
+         q_max <= kLayFixQMax;
+}
+// the state word of a check: corrected magnitudes (6 bits each), first argmin position, sign bits of R (edge k at bit k)
+constexpr uint32_t fix_state_word(uint32_t m1, uint32_t m2, uint32_t pos, uint32_t signs) {
+  return (m2 << 26) | (m1 << 20) | (pos << 16) | signs;
 }
 
 }  // namespace ibl

@@ -374,6 +374,73 @@ class LayeredDecoder:
             self._h = None
 
 
+class LayeredFixedDecoder:
+    """Layered min-sum in fixed point (``ibl_layered_create_fixed``; semantics in include/ibldpc.h "Layered
+    min-sum, fixed point"): 8-bit APP values, messages saturated at ``q_max``, magnitudes corrected as
+    ``max(((alpha16 * m + 8) >> 4) - beta_q, 0)``, float LLRs quantised as ``rint(llr * scale)``. It runs the
+    per-layer kernels over HBM (``path`` ``"auto"`` or ``"passes"``; ``"fused"`` raises :class:`_lib.IBLError`,
+    ``IBL_EUNSUPPORTED``: that kernel is not built) and owns about N + 4 n_c + N / 8 bytes per codeword of
+    ``max_batch``. ``decode`` takes and gives float32 or int8 tensors in any combination."""
+
+    _PATHS = LayeredDecoder._PATHS
+    _DT = {torch.float32: _lib.IBL_F32, torch.int8: _lib.IBL_I8}
+
+    def __init__(self, graph: Graph, layers, imax: int, max_batch: int, alpha16: int = 16, beta_q: int = 0,
+                 q_max: int = 31, scale: float = 2.0, path: str = "auto"):
+        if path not in self._PATHS:
+            raise ValueError('path must be "fused", "passes" or "auto"')
+        self.path = path
+        self.graph = graph
+        self.imax = int(imax)
+        self.max_batch = int(max_batch)
+        self.alpha16, self.beta_q, self.q_max, self.scale = int(alpha16), int(beta_q), int(q_max), float(scale)
+        self.device = graph.device
+        nl, ptr, chk = _lib.pack_layers(layers)
+        if chk.size == 0:
+            chk = np.zeros(1, np.int32)
+        self.n_layers = nl
+        h = ctypes.c_void_p()
+        _lib.check(_lib.load().ibl_layered_create_fixed(graph.handle, nl, ptr, chk, self.imax, self.alpha16,
+                                                        self.beta_q, self.q_max, self.scale, self.max_batch,
+                                                        self._PATHS[path], ctypes.byref(h)),
+                   "ibl_layered_create_fixed")
+        self._h = h
+
+    path_in_use = LayeredDecoder.path_in_use
+    geometry = LayeredDecoder.geometry
+    __del__ = LayeredDecoder.__del__
+
+    def decode(self, llr: torch.Tensor, out: Optional[torch.Tensor] = None, out_dtype=None,
+               early_stop: bool = True, iters: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``llr`` [N][B] float32 (quantised with ``scale``) or int8 (integer units) on the decoder's device -> APP
+        values [N][B] of ``out_dtype`` (default: ``out``'s, else ``llr``'s): int8 integer units, or float32 divided
+        by ``scale``. ``out`` may be ``llr`` when the dtypes match. ``iters`` as :meth:`LayeredDecoder.decode`."""
+        n = self.graph.edges.n_v
+        _check_tensor(llr, self.device, n, "channel LLRs")
+        if llr.dtype not in self._DT:
+            raise ValueError("channel LLRs must be float32 or int8")
+        B = llr.shape[1]
+        if out_dtype is None:
+            out_dtype = llr.dtype if out is None else out.dtype
+        if out_dtype not in self._DT:
+            raise ValueError("out_dtype must be torch.float32 or torch.int8")
+        if out is None:
+            out = torch.empty((n, B), dtype=out_dtype, device=self.device)
+        _check_tensor(out, self.device, n, "output")
+        if out.dtype != out_dtype or out.shape[1] != B:
+            raise ValueError("output must be [N][B] of out_dtype")
+        it_ptr = None
+        if iters is not None:
+            if iters.dtype != torch.int32 or iters.device != self.device or iters.numel() < B \
+                    or not iters.is_contiguous():
+                raise ValueError("iters must be a contiguous int32 device tensor of at least B entries")
+            it_ptr = iters.data_ptr()
+        _lib.check(_lib.load().ibl_layered_decode(self._h, llr.data_ptr(), self._DT[llr.dtype], B, out.data_ptr(),
+                                                  self._DT[out_dtype], int(bool(early_stop)), it_ptr,
+                                                  _stream_ptr(self.device)), "ibl_layered_decode")
+        return out
+
+
 def count_below(x: torch.Tensor, rows: int, threshold: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Device count of ``x[:rows] < threshold`` (the reference's error counters) -> int64 tensor."""
     if x.dim() != 2 or not x.is_contiguous() or x.device.type != "cuda":

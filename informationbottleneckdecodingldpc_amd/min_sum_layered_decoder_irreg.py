@@ -8,9 +8,14 @@ and method names so the same drivers (``ber.run_ber``) take it. Keyword-only ext
   block rows become the layers (``codes.qc_layers``); neither: ``codes.greedy_layers``;
 * ``alpha``, ``beta`` — normalisation factor and offset of the check magnitudes, max(alpha * m - beta, 0);
 * ``path`` — ``"fused"`` (default), ``"passes"`` (per-layer kernels over HBM: long codes such as DVB-S2 with
-  ``layers=codes.dvbs2_layers(H)``) or ``"auto"`` (:class:`.engine.LayeredDecoder`).
+  ``layers=codes.dvbs2_layers(H)``) or ``"auto"`` (:class:`.engine.LayeredDecoder`);
+* ``fixed`` — ``True`` decodes in fixed point (:class:`.engine.LayeredFixedDecoder`, include/ibldpc.h "Layered
+  min-sum, fixed point") with ``scale`` integer units per LLR unit and messages saturated at ``q_max``: ``alpha``
+  must be a multiple of 1/16 in [0, 1] and ``beta * scale`` an integer in [0, 63]; ``llr_max`` is not used (the
+  APP values saturate at 127 units); ``path`` ``"passes"`` or ``"auto"`` (``"fused"`` raises ``ValueError``).
+  Input and output stay float32.
 
-fp32 only. The early stop is per codeword; ``last_iterations`` holds the int32 device tensor of the last
+fp32 only unless ``fixed``. The early stop is per codeword; ``last_iterations`` holds the int32 device tensor of the last
 decode's iteration counts.
 """
 from __future__ import annotations
@@ -20,16 +25,27 @@ import torch
 
 from . import codes
 from ._dropin import CodeMixin, resolve_device, to_device_input
-from .engine import LayeredDecoder, count_below
+from .engine import LayeredDecoder, LayeredFixedDecoder, count_below
 
 
 class Min_Sum_Layered_Decoder_class_irregular(CodeMixin):
 
     def __init__(self, filename, imax_, cardinality_T_channel_, msg_at_time_, *, layers=None, Z=None,
-                 alpha: float = 1.0, beta: float = 0.0, llr_max: float = 150.0, path: str = "fused"):
+                 alpha: float = 1.0, beta: float = 0.0, llr_max: float = 150.0, path: str = "fused",
+                 fixed: bool = False, scale: float = 2.0, q_max: int = 31):
         if path not in LayeredDecoder._PATHS:
             raise ValueError('path must be "fused", "passes" or "auto"')
         self.path = path
+        self.fixed = bool(fixed)
+        if self.fixed:
+            if path == "fused":
+                raise ValueError('fixed=True runs the per-layer kernels: path must be "passes" or "auto"')
+            a16, bq = float(alpha) * 16.0, float(beta) * float(scale)
+            if not (0.0 <= a16 <= 16.0 and a16 == int(a16)):
+                raise ValueError("fixed=True: alpha must be a multiple of 1/16 in [0, 1]")
+            if not (0.0 <= bq <= 63.0 and bq == int(bq)):
+                raise ValueError("fixed=True: beta * scale must be an integer in [0, 63]")
+            self.alpha16, self.beta_q, self.q_max, self.scale = int(a16), int(bq), int(q_max), float(scale)
         self._init_code(filename)
         self.imax = int(imax_)
         self.cardinality_T_channel = int(cardinality_T_channel_)
@@ -54,6 +70,11 @@ class Min_Sum_Layered_Decoder_class_irregular(CodeMixin):
         self.device = dev
         self.context = dev
         self.msg_at_time = int(msg_at_time_)
+        if self.fixed:
+            self._dec = LayeredFixedDecoder(self._graph_on(dev), self.layers, self.imax, self.msg_at_time,
+                                            alpha16=self.alpha16, beta_q=self.beta_q, q_max=self.q_max,
+                                            scale=self.scale, path=self.path)
+            return
         self._dec = LayeredDecoder(self._graph_on(dev), self.layers, self.imax, self.msg_at_time, alpha=self.alpha,
                                    beta=self.beta, llr_max=self.llr_max, path=self.path)
 
