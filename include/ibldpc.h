@@ -319,6 +319,27 @@ int ibl_float_timing_read(ibl_float* h, double* cn_ms, int32_t* cn_launches, dou
  *   *ngroups = ceil(B / cw_per_group) groups of consecutive codewords, *grid = workgroups launched,
  *   min(ngroups, blocks per CU x CUs) — workgroup w decodes groups w, w + grid, w + 2 grid, ...  All three
  *   are 0 on a per-layer handle (the convention of ibl_float_fused_geometry).
+ *
+ * Compaction of the running codewords (fp32 per-layer handles; off unless switched on).  The per-layer kernels
+ *   skip finished codewords per whole tile of 64 only, so near the waterfall a few running codewords scattered over
+ *   the batch keep most tiles alive.  With compaction on, after the stop check of every iteration `it` with
+ *   it % every == 0 the device moves the columns of the running codewords to the lowest columns of P and of the
+ *   check state, in their order, and writes the finished codewords it drops to d_out at that moment.  Policy, with
+ *   R running codewords in an extent of E columns (E = B at the start), tE = ceil(E / 64), tR = ceil(R / 64):
+ *       compact  iff  R > 0  and  tE - tR >= max(1, ceil(min_free_pct * tE / 100));   afterwards E = R.
+ *   The decision is taken on the device: ibl_layered_decode still enqueues every launch up front (three more per
+ *   attempt: plan, row move, commit; the last two leave at once when the plan declined), allocates nothing and reads
+ *   nothing back, and no kernel waits for another workgroup.  Every value of d_out and d_iters is what the decode
+ *   without compaction gives, bit for bit.  d_out may be written before the decode's last kernel, and d_out may
+ *   still be d_llr: d_llr is read by the first launch only.
+ * ibl_layered_set_compaction  every = 0 switches it off (min_free_pct is not looked at); every >= 1 with
+ *   1 <= min_free_pct <= 100 switches it on for the decodes that follow, allocating on first use 8 bytes per
+ *   codeword of max_batch rounded up to 64, and 16 more.  Other numbers, judged first, and h == NULL are
+ *   IBL_EINVAL; a handle of the fused kernel is IBL_EUNSUPPORTED ("compaction needs the per-layer path"), a
+ *   fixed-point handle too ("compaction is not built for the fixed-point decoder").
+ * ibl_layered_compaction_stats  a diagnostic read-back: waits for `stream` (the stream of the last decode; no other
+ *   stream is waited for) and gives the compactions that decode made and its final extent; 0 and B after a decode
+ *   without compaction.  Refusals as ibl_layered_set_compaction.
  */
 typedef struct ibl_layered ibl_layered;
 int ibl_layers_validate(int32_t n_v, int32_t n_c, const int32_t* csr_indptr, const int32_t* csr_cols,
@@ -333,6 +354,8 @@ int ibl_layered_path_in_use(const ibl_layered* h, int32_t* fused);
 int ibl_layered_decode(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out,
                        int32_t out_dtype, int32_t early_stop, int32_t* d_iters, void* stream);
 int ibl_layered_geometry(const ibl_layered* h, int32_t B, int32_t* cw_per_group, int32_t* ngroups, int32_t* grid);
+int ibl_layered_set_compaction(ibl_layered* h, int32_t every, int32_t min_free_pct);
+int ibl_layered_compaction_stats(const ibl_layered* h, void* stream, int32_t* compactions, int32_t* extent);
 void ibl_layered_destroy(ibl_layered* h);
 
 /*

@@ -32,6 +32,11 @@ struct ibl_layered {
   float scale = 2.f;
   DevBuf<int8_t> P8;
   DevBuf<uint32_t> S;
+  // compaction of the running codewords (ibl_layered_set_compaction; fp32 per-layer path): every = 0 is off; the
+  // state of layered_plan.h pass_compact_bytes(max_batch), allocated when first switched on
+  int32_t compact_every = 0, compact_pct = 0;
+  DevBuf<int32_t> orig, dest, ctl;
+  int32_t last_B = 0, last_compact = 0;   // the last decode: its batch, and whether it ran with compaction
 };
 
 namespace {
@@ -85,17 +90,27 @@ int layered_decode_passes(ibl_layered* h, const float* d_llr, int32_t B, float* 
   a.running = h->running; a.bits = h->bits; a.rec = h->rec; a.cols = g->csr_cols; a.iters = d_iters;
   a.alpha = h->alpha; a.beta = h->beta; a.llr_max = h->llr_max;
   a.n_v = g->n_v; a.n_c = g->n_c; a.B = B; a.ntiles = pass_tiles(B);
-  HIPCHK(launch_lay_stage_in(a, d_llr, h->imax, s));
+  const int32_t every = h->compact_every;
+  LayCompactArgs c{};
+  c.orig = h->orig; c.dest = h->dest; c.ctl = h->ctl; c.out = d_out; c.min_free_pct = h->compact_pct;
+  h->last_B = B;
+  h->last_compact = every > 0;
+  if (every) HIPCHK(launch_lay_stage_in_c(a, c, d_llr, h->imax, s));
+  else HIPCHK(launch_lay_stage_in(a, d_llr, h->imax, s));
   const int32_t n_layers = (int32_t)h->layer_slot.size() - 1;
   for (int32_t it = 1; it <= h->imax; ++it) {
     for (int32_t l = 0; l < n_layers; ++l)
       HIPCHK(launch_lay_layer(a, h->layer_slot[l], h->layer_slot[l + 1] - h->layer_slot[l], s));
     if (early_stop && it < h->imax) {
       HIPCHK(launch_lay_syndrome(a, h->syn_packed, s));
-      HIPCHK(launch_lay_finalise(a, it, s));
+      if (every) HIPCHK(launch_lay_finalise_c(a, c, it, s));
+      else HIPCHK(launch_lay_finalise(a, it, s));
+      // the device decides whether the attempt moves anything (layered_plan.h compact_wanted)
+      if (every && it % every == 0) HIPCHK(launch_lay_compact(a, c, s));
     }
   }
-  HIPCHK(launch_lay_stage_out(a, d_out, s));
+  if (every) HIPCHK(launch_lay_stage_out_c(a, c, s));
+  else HIPCHK(launch_lay_stage_out(a, d_out, s));
   return IBL_OK;
 }
 
@@ -226,6 +241,52 @@ int ibl_layered_create_fixed(const ibl_graph* g, int32_t n_layers, const int32_t
 int ibl_layered_is_fixed(const ibl_layered* h, int32_t* fixed) {
   if (!h || !fixed) return fail(IBL_EINVAL, "NULL argument");
   *fixed = h->fixed;
+  return IBL_OK;
+}
+
+int ibl_layered_set_compaction(ibl_layered* h, int32_t every, int32_t min_free_pct) {
+  // the numbers are judged before the handle, so these refusals need no device
+  if (every < 0 || (every > 0 && (min_free_pct < 1 || min_free_pct > 100)))
+    return fail(IBL_EINVAL, "every must be >= 0 (0: off) and min_free_pct lie in [1, 100]");
+  if (!h) return fail(IBL_EINVAL, "decoder is NULL");
+  if (h->fixed) return fail(IBL_EUNSUPPORTED, "compaction is not built for the fixed-point decoder");
+  if (h->fused) return fail(IBL_EUNSUPPORTED, "compaction needs the per-layer path");
+  if (every == 0) {
+    h->compact_every = h->compact_pct = 0;
+    return IBL_OK;
+  }
+  if (!h->ctl) {
+    if ((pass_compact_rows(h->g->n_v, h->g->n_c) + kLayPassWaves - 1) / kLayPassWaves > 0x7fffffffll)
+      return fail(IBL_EINVAL, "the code is too large for the compaction kernels' grid");
+    HIPCHK(hipSetDevice(h->g->device));
+    size_t priv = 0;
+    HIPCHK(lay_compact_private_bytes(&priv));
+    int rc = refuse_private(priv, "a compaction kernel has a ", "-byte private segment (register spill): rebuild required");
+    if (rc) return rc;
+    const LayeredCompactBytes by = pass_compact_bytes(h->max_batch);
+    DevBuf<int32_t> orig, dest, ctl;
+    if ((rc = orig.alloc(by.orig / 4)) || (rc = dest.alloc(by.dest / 4)) || (rc = ctl.alloc_zero(by.ctl / 4))) return rc;
+    h->orig = std::move(orig); h->dest = std::move(dest); h->ctl = std::move(ctl);
+  }
+  h->compact_every = every;
+  h->compact_pct = min_free_pct;
+  return IBL_OK;
+}
+
+int ibl_layered_compaction_stats(const ibl_layered* h, void* stream, int32_t* compactions, int32_t* extent) {
+  if (!h || !compactions || !extent) return fail(IBL_EINVAL, "NULL argument");
+  if (h->fixed) return fail(IBL_EUNSUPPORTED, "compaction is not built for the fixed-point decoder");
+  if (h->fused) return fail(IBL_EUNSUPPORTED, "compaction needs the per-layer path");
+  *compactions = 0;
+  *extent = h->last_B;   // a decode without compaction keeps all its columns
+  if (!h->last_compact) return IBL_OK;
+  int32_t w[kLayCompactCtl] = {0, 0, 0, 0};
+  hipStream_t s = (hipStream_t)stream;
+  HIPCHK(hipSetDevice(h->g->device));
+  HIPCHK(hipMemcpyAsync(w, h->ctl.get(), sizeof(w), hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  *compactions = w[kLayCtlCount];
+  *extent = w[kLayCtlExtent];
   return IBL_OK;
 }
 

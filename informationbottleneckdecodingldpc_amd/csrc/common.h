@@ -394,6 +394,23 @@ hipError_t launch_lay_finalise(const LayPassArgs& a, int it, hipStream_t s);
 hipError_t launch_lay_stage_out(const LayPassArgs& a, float* out, hipStream_t s);
 hipError_t lay_pass_private_bytes(size_t* bytes);
 
+// Compaction of the running codewords on the per-layer path (layered_plan.h "compaction"; opt-in, a second
+// argument of the kernels that know about it, so LayPassArgs and every launch without it stay as they are).
+struct LayCompactArgs {
+  int32_t* orig;            // [ldb] the caller's column of the codeword now in column c
+  int32_t* dest;            // [ldb] map of the compaction in progress: new column, or -1 (finished: flushed)
+  int32_t* ctl;             // [kLayCompactCtl] extent, do flag, compactions of this decode
+  float* out;               // the caller's [n_v][B] output: finished codewords are delivered when they are dropped
+  int32_t min_free_pct;
+};
+// the _c launchers are lay_stage_in / lay_finalise / lay_stage_out through `orig` and the extent
+hipError_t launch_lay_stage_in_c(const LayPassArgs& a, const LayCompactArgs& c, const float* llr, int imax, hipStream_t s);
+hipError_t launch_lay_finalise_c(const LayPassArgs& a, const LayCompactArgs& c, int it, hipStream_t s);
+hipError_t launch_lay_stage_out_c(const LayPassArgs& a, const LayCompactArgs& c, hipStream_t s);
+// one attempt: plan (decides on the device), row move, commit — three launches, the last two leave when `do` is 0
+hipError_t launch_lay_compact(const LayPassArgs& a, const LayCompactArgs& c, hipStream_t s);
+hipError_t lay_compact_private_bytes(size_t* bytes);
+
 // Fixed-point per-layer path (include/ibldpc.h "Layered min-sum, fixed point"): a lane owns 4 consecutive
 // codewords, rows [row][ldb] with ldb = ntiles4 * 256 (layered_plan.h "fixed point"). The masks, the packed hard
 // decisions, `running`, `rec` and `cols` are those of LayPassArgs, per 64 codewords, so the packed syndrome and the

@@ -294,9 +294,11 @@ __device__ __forceinline__ void lay_cn_rows(const LayPassArgs& a, int e0, size_t
 }  // namespace
 
 // P = llr + 0 (a -0 enters as +0), padding lanes 0; state rows 0; masks, counter and iters reset.
-// item = (row < max(n_v, n_c), tile)
-__global__ __launch_bounds__(64 * kLayPassWaves) void lay_stage_in(const LayPassArgs a, const float* __restrict__ llr,
-                                                                   int imax) {
+// item = (row < max(n_v, n_c), tile). kCompact: also orig = the identity, extent = B, no compaction yet.
+namespace {
+template <bool kCompact>
+__device__ __forceinline__ void lay_stage_in_body(const LayPassArgs& a, const float* __restrict__ llr, int imax,
+                                                  const LayCompactArgs* c) {
   const int lane = (int)(threadIdx.x & 63u);
   const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + (int64_t)(threadIdx.x >> 6);
   const int64_t rows = a.n_v > a.n_c ? a.n_v : a.n_c;
@@ -314,13 +316,31 @@ __global__ __launch_bounds__(64 * kLayPassWaves) void lay_stage_in(const LayPass
   }
   if (row == 0) {
     if (a.iters && b < a.B) a.iters[b] = imax;
+    if constexpr (kCompact) c->orig[b] = b;
     if (lane == 0) {
       const int left = a.B - tile * kLayTile;   // >= 1
       a.done[tile] = left >= kLayTile ? 0ull : ~0ull << left;
       a.unsat[tile] = 0ull;
-      if (tile == 0) *a.running = a.B;
+      if (tile == 0) {
+        *a.running = a.B;
+        if constexpr (kCompact) {
+          c->ctl[kLayCtlExtent] = a.B;
+          c->ctl[kLayCtlDo] = 0;
+          c->ctl[kLayCtlCount] = 0;
+        }
+      }
     }
   }
+}
+}  // namespace
+
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_stage_in(const LayPassArgs a, const float* __restrict__ llr,
+                                                                   int imax) {
+  lay_stage_in_body<false>(a, llr, imax, nullptr);
+}
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_stage_in_c(const LayPassArgs a, const LayCompactArgs c,
+                                                                     const float* __restrict__ llr, int imax) {
+  lay_stage_in_body<true>(a, llr, imax, &c);
 }
 
 // item = (check slot0 + c of the layer, tile), tile fastest
@@ -430,14 +450,20 @@ __global__ __launch_bounds__(64 * kLayPassWaves) void lay_syndrome_packed(const 
 }
 
 // One wave per tile: running codewords whose syndrome is zero are finished at iteration `it`.
-__global__ __launch_bounds__(64 * kLayPassWaves) void lay_finalise(const LayPassArgs a, int it) {
+// kCompact: the codeword in column col is the caller's orig[col].
+namespace {
+template <bool kCompact>
+__device__ __forceinline__ void lay_finalise_body(const LayPassArgs& a, int it, const LayCompactArgs* c) {
   if (sload(a.running, 0) == 0) return;
   const int lane = (int)(threadIdx.x & 63u);
   const int tile = (int)blockIdx.x * kLayPassWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
   if (tile >= a.ntiles) return;
   const uint64_t dm = lay_mask(a.done, tile), um = lay_mask(a.unsat, tile);
   const uint64_t now = ~dm & ~um;
-  if (a.iters && ((now >> lane) & 1ull)) a.iters[tile * kLayTile + lane] = it;
+  if (a.iters && ((now >> lane) & 1ull)) {
+    if constexpr (kCompact) a.iters[c->orig[tile * kLayTile + lane]] = it;
+    else a.iters[tile * kLayTile + lane] = it;
+  }
   if (lane == 0) {
     if (now != 0ull) {
       a.done[tile] = dm | now;
@@ -445,6 +471,15 @@ __global__ __launch_bounds__(64 * kLayPassWaves) void lay_finalise(const LayPass
     }
     if (um != 0ull) a.unsat[tile] = 0ull;
   }
+}
+}  // namespace
+
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_finalise(const LayPassArgs a, int it) {
+  lay_finalise_body<false>(a, it, nullptr);
+}
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_finalise_c(const LayPassArgs a, const LayCompactArgs c,
+                                                                     int it) {
+  lay_finalise_body<true>(a, it, &c);
 }
 
 // out[row][b] = P[row][b] for b < B (padding lanes never reach the caller); item = (row < n_v, tile)
@@ -456,6 +491,148 @@ __global__ __launch_bounds__(64 * kLayPassWaves) void lay_stage_out(const LayPas
   const int64_t row = item / a.ntiles;
   const int b = tile * kLayTile + lane;
   if (b < a.B) out[(size_t)row * (size_t)a.B + (size_t)b] = a.P[(size_t)row * (size_t)a.ntiles * kLayTile + (size_t)b];
+}
+// With compaction: out[row][orig[c]] = P[row][c] for the columns c < extent still in use, running or finished
+// since the last compaction; the codewords dropped by a compaction were delivered then.
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_stage_out_c(const LayPassArgs a, const LayCompactArgs c) {
+  const int lane = (int)(threadIdx.x & 63u);
+  const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + (int64_t)(threadIdx.x >> 6);
+  if (item >= (int64_t)a.n_v * a.ntiles) return;
+  const int tile = (int)(item % a.ntiles);
+  const int64_t row = item / a.ntiles;
+  const int extent = sload(c.ctl, kLayCtlExtent);   // <= B
+  const int b = tile * kLayTile + lane;
+  if (b < extent)
+    c.out[(size_t)row * (size_t)a.B + (size_t)c.orig[b]] = a.P[(size_t)row * (size_t)a.ntiles * kLayTile + (size_t)b];
+}
+
+// ---- compaction of the running codewords (layered_plan.h "compaction"; include/ibldpc.h) -------------------------
+// Attempted after lay_finalise of an iteration: three launches, plan / rows / commit. The plan decides on the device
+// (layered_plan.h compact_wanted) and says so in the `do` word; the other two leave at once when it is 0. Nothing
+// waits for another workgroup: the three are ordered by the stream, and inside the row move a row belongs to one
+// wave. After the commit the running codewords are columns 0 .. R - 1 in their former order, extent = R, the
+// finished masks say "finished" for every column >= R, and every tile past ceil(R / 64) is skipped by the kernels
+// above as a finished tile always was. orig[c] names the caller's column of the codeword in column c.
+
+// One workgroup: dest[c] for c < extent (layered_plan.h compact_rank). Each wave scans the 64 tile counts of a
+// chunk of tiles itself (no LDS, no barrier) and writes every fourth tile of the chunk.
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_compact_plan(const LayPassArgs a, const LayCompactArgs c) {
+  const int R = sload(a.running, 0);
+  if (R == 0) return;   // `do` is 0: stage-in and every commit leave it so
+  const int E = sload(c.ctl, kLayCtlExtent);
+  if (!compact_wanted(R, E, c.min_free_pct)) {
+    if (threadIdx.x == 0) c.ctl[kLayCtlDo] = 0;
+    return;
+  }
+  const int lane = (int)(threadIdx.x & 63u);
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int tE = (E + kLayTile - 1) / kLayTile;   // <= ntiles: the masks and dest hold them
+  int below = 0;                                  // running columns of the tiles before the chunk
+  for (int t0 = 0; t0 < tE; t0 += 64) {
+    const int t = t0 + lane;
+    const uint64_t dm = t < tE ? a.done[t] : ~0ull;
+    const int cnt = compact_tile_count(dm);
+    int inc = cnt;   // inclusive scan over the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+      const int v = __shfl_up(inc, off);
+      if (lane >= off) inc += v;
+    }
+    const int excl = below + inc - cnt;
+    for (int j = wave; j < 64 && t0 + j < tE; j += kLayPassWaves) {
+      const uint64_t dj = (uint64_t)__shfl((unsigned long long)dm, j);
+      const int bj = __shfl(excl, j);
+      const int col = (t0 + j) * kLayTile + lane;
+      if (col < E) c.dest[col] = compact_rank(dj, lane, bj);
+    }
+    below += __shfl(inc, 63);
+  }
+  if (threadIdx.x == 0) c.ctl[kLayCtlDo] = 1;
+}
+
+// The row move, in place. item = row of P (n_v), then of M1, M2, PS (n_c each); one wave owns the row and walks its
+// source columns c < extent in ascending chunks of kLayCompactChunk x 64: it loads the chunk, waits for the loads,
+// then stores — a running element to row[dest[c]], a finished element of a P row to out[row][orig[c]] (the
+// codeword leaves the decoder here), finished state elements nowhere.
+// Why in place is safe: the map is stable, dest[c] <= c, so every destination of a chunk lies at or below the
+// chunk's last source, and the sources of every later chunk lie above it. A store can therefore only hit a source
+// of its own chunk or of an earlier one, and all of those were loaded before the chunk's first store: load, wait,
+// store per chunk in ascending order is the whole argument. Destinations are distinct, so stores do not collide.
+constexpr int kLayCompactChunk = 4;
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_compact_rows(const LayPassArgs a, const LayCompactArgs c) {
+  if (sload(c.ctl, kLayCtlDo) == 0) return;
+  const int lane = (int)(threadIdx.x & 63u);
+  const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (item >= (int64_t)a.n_v + 3 * (int64_t)a.n_c) return;
+  const int E = sload(c.ctl, kLayCtlExtent);
+  const size_t ldb = (size_t)a.ntiles * kLayTile;
+  const bool is_p = item < a.n_v;
+  // rows move as 32-bit words whatever they hold; no __restrict__: sources and destinations share the row
+  uint32_t* row;
+  uint32_t* orow = nullptr;
+  if (is_p) {
+    row = reinterpret_cast<uint32_t*>(a.P) + (size_t)item * ldb;
+    orow = reinterpret_cast<uint32_t*>(c.out) + (size_t)item * (size_t)a.B;
+  } else {
+    const int64_t r = item - a.n_v;
+    const int which = (int)(r / a.n_c);
+    uint32_t* base = which == 0 ? reinterpret_cast<uint32_t*>(a.M1) : which == 1 ? reinterpret_cast<uint32_t*>(a.M2) : a.PS;
+    row = base + (size_t)(r % a.n_c) * ldb;
+  }
+  for (int c0 = 0; c0 < E; c0 += kLayCompactChunk * kLayTile) {
+    uint32_t x[kLayCompactChunk];
+    int d[kLayCompactChunk];
+    bool move[kLayCompactChunk];
+#pragma unroll
+    for (int j = 0; j < kLayCompactChunk; ++j) {
+      const int col = c0 + j * kLayTile + lane;
+      d[j] = -1;
+      x[j] = 0u;
+      move[j] = false;
+      if (col < E) {
+        d[j] = c.dest[col];
+        move[j] = d[j] >= 0 ? d[j] != col : is_p;   // a running element already in place stays
+        if (move[j]) x[j] = row[col];
+      }
+    }
+    __builtin_amdgcn_s_waitcnt(0);   // every load of the chunk has returned before its first store
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < kLayCompactChunk; ++j) {
+      if (!move[j]) continue;
+      if (d[j] >= 0) row[d[j]] = x[j];
+      else orow[c.orig[c0 + j * kLayTile + lane]] = x[j];
+    }
+  }
+}
+
+// One workgroup: orig follows the move (orig[dest[c]] = orig[c], by the row move's ascending chunk rule with a
+// workgroup barrier between a chunk's loads and its stores), the finished masks of the new extent, and the words.
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_compact_commit(const LayPassArgs a, const LayCompactArgs c) {
+  if (sload(c.ctl, kLayCtlDo) == 0) return;
+  const int E = sload(c.ctl, kLayCtlExtent), R = sload(a.running, 0), n = sload(c.ctl, kLayCtlCount);
+  const int tid = (int)threadIdx.x;
+  for (int c0 = 0; c0 < E; c0 += 64 * kLayPassWaves) {   // E is uniform: every thread meets every barrier
+    const int col = c0 + tid;
+    int d = -1, o = 0;
+    if (col < E) {
+      d = c.dest[col];
+      if (d >= 0) o = c.orig[col];
+    }
+    __syncthreads();
+    if (d >= 0 && d != col) c.orig[d] = o;
+  }
+  const int tE = (E + kLayTile - 1) / kLayTile;
+  for (int t = tid; t < tE; t += 64 * kLayPassWaves) {
+    a.done[t] = compact_done_word(t, R);
+    a.unsat[t] = 0ull;
+  }
+  __syncthreads();   // every wave has read the words before they change
+  if (tid == 0) {
+    c.ctl[kLayCtlExtent] = R;
+    c.ctl[kLayCtlCount] = n + 1;
+    c.ctl[kLayCtlDo] = 0;
+  }
 }
 
 namespace {
@@ -508,6 +685,60 @@ hipError_t launch_lay_stage_out(const LayPassArgs& a, float* out, hipStream_t s)
   LayPassArgs args = a;
   void* p[] = {&args, (void*)&out};
   return lay_pass_launch((const void*)lay_stage_out, (int64_t)a.n_v * a.ntiles, p, s);
+}
+
+namespace {
+bool lay_compact_args_ok(const LayCompactArgs& c) {
+  return c.orig && c.dest && c.ctl && c.out && c.min_free_pct >= 1 && c.min_free_pct <= 100;
+}
+}  // namespace
+
+hipError_t launch_lay_stage_in_c(const LayPassArgs& a, const LayCompactArgs& c, const float* llr, int imax,
+                                 hipStream_t s) {
+  if (!lay_pass_args_ok(a) || !lay_compact_args_ok(c) || !llr) return hipErrorInvalidValue;
+  LayPassArgs args = a;
+  LayCompactArgs ca = c;
+  void* p[] = {&args, &ca, (void*)&llr, (void*)&imax};
+  return lay_pass_launch((const void*)lay_stage_in_c, (int64_t)std::max(a.n_v, a.n_c) * a.ntiles, p, s);
+}
+
+hipError_t launch_lay_finalise_c(const LayPassArgs& a, const LayCompactArgs& c, int it, hipStream_t s) {
+  if (!lay_pass_args_ok(a) || !lay_compact_args_ok(c)) return hipErrorInvalidValue;
+  LayPassArgs args = a;
+  LayCompactArgs ca = c;
+  void* p[] = {&args, &ca, (void*)&it};
+  return lay_pass_launch((const void*)lay_finalise_c, a.ntiles, p, s);
+}
+
+hipError_t launch_lay_stage_out_c(const LayPassArgs& a, const LayCompactArgs& c, hipStream_t s) {
+  if (!lay_pass_args_ok(a) || !lay_compact_args_ok(c)) return hipErrorInvalidValue;
+  LayPassArgs args = a;
+  LayCompactArgs ca = c;
+  void* p[] = {&args, &ca};
+  return lay_pass_launch((const void*)lay_stage_out_c, (int64_t)a.n_v * a.ntiles, p, s);
+}
+
+hipError_t launch_lay_compact(const LayPassArgs& a, const LayCompactArgs& c, hipStream_t s) {
+  if (!lay_pass_args_ok(a) || !lay_compact_args_ok(c)) return hipErrorInvalidValue;
+  LayPassArgs args = a;
+  LayCompactArgs ca = c;
+  void* p[] = {&args, &ca};
+  hipError_t e = hipLaunchKernel((const void*)lay_compact_plan, dim3(1), dim3(64 * kLayPassWaves), p, 0, s);
+  if (e != hipSuccess) return e;
+  if ((e = lay_pass_launch((const void*)lay_compact_rows, pass_compact_rows(a.n_v, a.n_c), p, s)) != hipSuccess) return e;
+  return hipLaunchKernel((const void*)lay_compact_commit, dim3(1), dim3(64 * kLayPassWaves), p, 0, s);
+}
+
+hipError_t lay_compact_private_bytes(size_t* bytes) {
+  *bytes = 0;
+  for (const void* f : {(const void*)lay_stage_in_c, (const void*)lay_finalise_c, (const void*)lay_stage_out_c,
+                        (const void*)lay_compact_plan, (const void*)lay_compact_rows, (const void*)lay_compact_commit}) {
+    hipFuncAttributes fa;
+    const hipError_t e = hipFuncGetAttributes(&fa, f);
+    if (e != hipSuccess) return e;
+    *bytes = std::max(*bytes, (size_t)fa.localSizeBytes);
+  }
+  return hipSuccess;
 }
 
 // the largest private (scratch) segment over the per-layer kernels: built to run without one

@@ -2,8 +2,9 @@
 //
 // Built into libibldpc.so (capi_layered.hip includes this header) and, with AddressSanitizer and
 // UndefinedBehaviorSanitizer, into the CPU-only checkers tests/asan/layered_plan_check.cpp
-// (tests/test_cpu_layered.py), tests/asan/layered_pass_plan_check.cpp (tests/test_cpu_layered_passes.py) and
-// tests/asan/layered_fixed_plan_check.cpp (tests/test_cpu_layered_fixed.py).
+// (tests/test_cpu_layered.py), tests/asan/layered_pass_plan_check.cpp (tests/test_cpu_layered_passes.py),
+// tests/asan/layered_fixed_plan_check.cpp (tests/test_cpu_layered_fixed.py) and
+// tests/asan/layered_compact_plan_check.cpp (tests/test_cpu_layered_compact.py).
 //
 // A layer is a set of checks no two of which share a variable; the layers are disjoint, cover every check and
 // are decoded in order (include/ibldpc.h "Layered min-sum"). The device plan cuts every layer into tasks of up
@@ -201,6 +202,54 @@ inline void plan_layered_passes(int32_t n_c, const int32_t* indptr, int32_t n_la
     }
   }
 }
+
+// ---- compaction of the running codewords, fp32 per-layer path (include/ibldpc.h "Layered min-sum", compaction;
+// checked by tests/asan/layered_compact_plan_check.cpp) --------------------------------------------------------------
+// Between iterations the columns of the running codewords move to the lowest columns of P, M1, M2 and PS, so that
+// whole tiles past them are finished and skipped. The two functions below are the policy and the map, shared by the
+// device plan kernel (lay_compact_plan) and the host-side checker; constexpr, so the kernels call them as they stand.
+constexpr int kLayCompactCtl = 4;   // control words: the three below and one of padding
+enum { kLayCtlExtent = 0, kLayCtlDo = 1, kLayCtlCount = 2 };   // columns in use; compaction in progress; count
+
+// Whether the R running codewords of an extent of E columns are compacted: never when none runs, else when the
+// move frees at least max(1, ceil(min_free_pct tE / 100)) of the extent's tE tiles.
+constexpr bool compact_wanted(int32_t R, int32_t E, int32_t min_free_pct) {
+  if (R <= 0 || E <= 0 || R > E) return false;
+  const int64_t tE = ((int64_t)E + kLayTile - 1) / kLayTile, tR = ((int64_t)R + kLayTile - 1) / kLayTile;
+  const int64_t pct = ((int64_t)min_free_pct * tE + 99) / 100;
+  return tE - tR >= (pct > 1 ? pct : 1);
+}
+// The rank map of one column: `done` is the finished mask of the column's tile, `lane` the column's bit, `below`
+// the running columns of the tiles before it. A running column goes to the number of running columns below it
+// (stable: never above its own place), a finished one is flushed (-1).
+constexpr int32_t compact_rank(uint64_t done, int lane, int32_t below) {
+  if ((done >> lane) & 1ull) return -1;
+  return below + (int32_t)__builtin_popcountll(~done & ((1ull << lane) - 1ull));
+}
+// running columns of a tile
+constexpr int32_t compact_tile_count(uint64_t done) { return (int32_t)__builtin_popcountll(~done); }
+// the finished mask of tile `tile` once R columns are in use: bit set for every column >= R
+constexpr uint64_t compact_done_word(int32_t tile, int32_t R) {
+  const int64_t left = (int64_t)R - (int64_t)tile * kLayTile;
+  return left >= kLayTile ? 0ull : left <= 0 ? ~0ull : ~0ull << left;
+}
+
+// byte sizes of the device state compaction adds to a per-layer handle of max_batch (allocated when first enabled)
+struct LayeredCompactBytes {
+  size_t orig = 0;    // [ldb] int32: the caller's column of the codeword now in column c
+  size_t dest = 0;    // [ldb] int32: the map of the compaction in progress
+  size_t ctl = 0;     // kLayCompactCtl int32 words
+  size_t total = 0;
+};
+inline LayeredCompactBytes pass_compact_bytes(int32_t max_batch) {
+  LayeredCompactBytes b;
+  b.orig = b.dest = (size_t)4 * (size_t)pass_ldb(max_batch);
+  b.ctl = (size_t)4 * kLayCompactCtl;
+  b.total = b.orig + b.dest + b.ctl;
+  return b;
+}
+// wave items of the row move: the n_v rows of P and the n_c rows of each of M1, M2, PS
+inline int64_t pass_compact_rows(int32_t n_v, int32_t n_c) { return (int64_t)n_v + 3 * (int64_t)n_c; }
 
 // ---- fixed point, per-layer path (include/ibldpc.h "Layered min-sum, fixed point"; checked by
 // tests/asan/layered_fixed_plan_check.cpp) ------------------------------------------------------------------------

@@ -295,13 +295,18 @@ class LayeredDecoder:
     kernels over HBM for codes of any length (``codes.dvbs2_layers`` for DVB-S2; they own about 4 N + 12 n_c
     bytes per codeword of ``max_batch``); ``"auto"`` the fused kernel when the codeword fits, else the per-layer
     kernels. The outputs are the same on every path.
+    ``compact`` (per-layer kernels only): ``True`` or ``(every, min_free_pct)`` moves the running codewords together
+    between iterations so that whole tiles of finished ones are skipped (``ibl_layered_set_compaction``; the policy
+    is in include/ibldpc.h). Values and iteration counts do not change; ``out`` may be written before the decode's
+    last kernel. ``True`` means ``COMPACT_DEFAULT``.
     Raises :class:`_lib.IBLError` (``IBL_EUNSUPPORTED``) when ``path="fused"`` and a codeword does not fit in
-    LDS, or ``precision`` is not float32."""
+    LDS, ``precision`` is not float32, or ``compact`` is given and the fused kernel is in use."""
 
     _PATHS = {"auto": _lib.IBL_PATH_AUTO, "passes": _lib.IBL_PATH_PASSES, "fused": _lib.IBL_PATH_FUSED}
+    COMPACT_DEFAULT = (2, 25)   # the best measured pair: DESIGN.md "Layered min-sum: compaction"
 
     def __init__(self, graph: Graph, layers, imax: int, max_batch: int, alpha: float = 1.0, beta: float = 0.0,
-                 llr_max: float = 150.0, precision=torch.float32, path: str = "fused"):
+                 llr_max: float = 150.0, precision=torch.float32, path: str = "fused", compact=None):
         if path not in self._PATHS:
             raise ValueError('path must be "fused", "passes" or "auto"')
         self.path = path
@@ -322,6 +327,42 @@ class LayeredDecoder:
                                                        self._PATHS[path], ctypes.byref(h)),
                    "ibl_layered_create_path")
         self._h = h
+        self._compaction = None
+        if compact is not None and compact is not False:
+            self.compaction = compact
+
+    @property
+    def compaction(self):
+        """``None`` (off) or ``(every, min_free_pct)``. Assigning ``True``, a pair, or ``None`` / ``False``
+        switches it for the decodes that follow (``ibl_layered_set_compaction``)."""
+        return self._compaction
+
+    @compaction.setter
+    def compaction(self, value):
+        if value is None or value is False:
+            pair = None
+        elif value is True:
+            pair = self.COMPACT_DEFAULT
+        else:
+            every, pct = value
+            pair = (int(every), int(pct))
+            if pair != (every, pct):
+                raise ValueError("compact must be True or a pair of integers (every, min_free_pct)")
+            if pair[0] < 1:
+                raise ValueError("compact: every must be >= 1 (None switches compaction off)")
+        every, pct = pair if pair else (0, 0)
+        _lib.check(_lib.load().ibl_layered_set_compaction(self._h, every, pct), "ibl_layered_set_compaction")
+        self._compaction = pair
+
+    def compaction_stats(self, stream=None):
+        """``(compactions, extent)`` of the last decode: how often the running codewords were moved together and
+        the columns in use at its end (``(0, B)`` without compaction). A diagnostic read-back: it waits for
+        ``stream`` (default: the current stream of the decoder's device), which must be the decode's."""
+        ptr = _stream_ptr(self.device) if stream is None else stream.cuda_stream
+        n, e = ctypes.c_int32(), ctypes.c_int32()
+        _lib.check(_lib.load().ibl_layered_compaction_stats(self._h, ptr, ctypes.byref(n), ctypes.byref(e)),
+                   "ibl_layered_compaction_stats")
+        return int(n.value), int(e.value)
 
     @property
     def path_in_use(self) -> str:

@@ -13,7 +13,10 @@ and method names so the same drivers (``ber.run_ber``) take it. Keyword-only ext
   min-sum, fixed point") with ``scale`` integer units per LLR unit and messages saturated at ``q_max``: ``alpha``
   must be a multiple of 1/16 in [0, 1] and ``beta * scale`` an integer in [0, 63]; ``llr_max`` is not used (the
   APP values saturate at 127 units); ``path`` ``"passes"`` or ``"auto"`` (``"fused"`` raises ``ValueError``).
-  Input and output stay float32.
+  Input and output stay float32;
+* ``compact`` — ``True`` or ``(every, min_free_pct)``: the per-layer kernels move the running codewords together
+  between iterations (:class:`.engine.LayeredDecoder`); same results. ``ValueError`` with ``fixed=True`` or
+  ``path="fused"``.
 
 fp32 only unless ``fixed``. The early stop is per codeword; ``last_iterations`` holds the int32 device tensor of the last
 decode's iteration counts.
@@ -32,11 +35,14 @@ class Min_Sum_Layered_Decoder_class_irregular(CodeMixin):
 
     def __init__(self, filename, imax_, cardinality_T_channel_, msg_at_time_, *, layers=None, Z=None,
                  alpha: float = 1.0, beta: float = 0.0, llr_max: float = 150.0, path: str = "fused",
-                 fixed: bool = False, scale: float = 2.0, q_max: int = 31):
+                 fixed: bool = False, scale: float = 2.0, q_max: int = 31, compact=None):
         if path not in LayeredDecoder._PATHS:
             raise ValueError('path must be "fused", "passes" or "auto"')
         self.path = path
         self.fixed = bool(fixed)
+        self.compact = None if compact is False else compact
+        if self.compact is not None and (self.fixed or path == "fused"):
+            raise ValueError('compact runs on the fp32 per-layer kernels: not with fixed=True or path="fused"')
         if self.fixed:
             if path == "fused":
                 raise ValueError('fixed=True runs the per-layer kernels: path must be "passes" or "auto"')
@@ -76,7 +82,8 @@ class Min_Sum_Layered_Decoder_class_irregular(CodeMixin):
                                             scale=self.scale, path=self.path)
             return
         self._dec = LayeredDecoder(self._graph_on(dev), self.layers, self.imax, self.msg_at_time, alpha=self.alpha,
-                                   beta=self.beta, llr_max=self.llr_max, path=self.path)
+                                   beta=self.beta, llr_max=self.llr_max, path=self.path,
+                                   compact=self.compact)
 
     def _decode(self, received_blocks, buffer_in, return_buffer, early_stop=True):
         if self._dec is None:
