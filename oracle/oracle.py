@@ -40,7 +40,7 @@ def lib():
         i32, i64 = ctypes.c_int32, ctypes.c_int64
         L.ibo_ib_decode.restype = ctypes.c_int
         L.ibo_ib_decode.argtypes = [i32, i32, i64, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p,
-                                    i32, i32, i32, i32, i32, _i32p, _i32p, _i32p, _i32p, i32,
+                                    i32, i32, i32, i32, i32, _i32p, i64, _i32p, i64, _i32p, i64, _i32p, i64, i32,
                                     _i32p, i32, i32, _i32p, ctypes.POINTER(i32), i32]
         L.ibo_float_decode.restype = ctypes.c_int
         L.ibo_float_decode.argtypes = [i32, i32, i64, _i32p, _i32p, _i32p, _i32p, _i32p, _i32p,
@@ -72,7 +72,10 @@ def _c(a, dt):
 
 def ib_decode(g, tb, ch: np.ndarray, match: bool, early_stop: bool = False,
               nthreads: int = 0, return_iters: bool = False):
-    """Oracle IB decode of ``ch`` ([N][B] cluster ids) -> [N][B] int32 cluster ids."""
+    """Oracle IB decode of ``ch`` ([N][B] cluster ids) -> [N][B] int32 cluster ids.
+
+    A table index past the end of its vector reads the vector's last entry (``lut_at``, ib_oracle.c): the
+    reference reads out of bounds there (a degree-1 variable's channel cluster with ``T_ch > T_dec``)."""
     ch = _c(ch, np.int32)
     if ch.ndim == 1:
         ch = ch[:, None]
@@ -80,12 +83,13 @@ def ib_decode(g, tb, ch: np.ndarray, match: bool, early_stop: bool = False,
     assert N == g.n_v
     out = np.zeros((N, B), dtype=np.int32)
     iters = ctypes.c_int32(0)
+    cn, vn = _c(tb.cn, np.int32).ravel(), _c(tb.vn, np.int32).ravel()
+    mc, mv = _c(tb.match_cn, np.int32).ravel(), _c(tb.match_vn, np.int32).ravel()
     rc = lib().ibo_ib_decode(g.n_v, g.n_c, g.n_e, _c(g.cn_start, np.int32), _c(g.cn_deg, np.int32),
                              _c(g.tgt_cn, np.int32), _c(g.vn_start, np.int32), _c(g.vn_deg, np.int32),
                              _c(g.tgt_vn, np.int32), tb.Tc, tb.T, tb.imax, tb.CM, tb.VM,
-                             _c(tb.cn, np.int32), _c(tb.vn, np.int32), _c(tb.match_cn, np.int32),
-                             _c(tb.match_vn, np.int32), int(bool(match)), ch, B, int(bool(early_stop)),
-                             out, ctypes.byref(iters), int(nthreads))
+                             cn, cn.size, vn, vn.size, mc, mc.size, mv, mv.size, int(bool(match)), ch, B,
+                             int(bool(early_stop)), out, ctypes.byref(iters), int(nthreads))
     if rc != 0:
         raise RuntimeError(f"oracle ib_decode failed rc={rc}")
     return (out, iters.value) if return_iters else out

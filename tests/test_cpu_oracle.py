@@ -77,6 +77,28 @@ def test_oracle_columns_are_independent(wlan_H):
         np.testing.assert_array_equal(oracle.ib_decode(g, tb, ch[:, b], match=True)[:, 0], full[:, b])
 
 
+@pytest.mark.parametrize("Tc,T", [(16, 8), (8, 4)])
+def test_oracle_index_past_the_vector_reads_its_last_entry(Tc, T):
+    """A degree-1 variable forwards its channel cluster unchanged; with T_ch > T_dec that value indexes the check
+    tables past their block, and in the last pass past the vector (the reference reads out of bounds; the oracle
+    used to, and crashed). The read is defined as the vector's last entry: the decode equals the decode with every
+    vector padded by copies of its last entry, where the same indices stay inside."""
+    g = graph.build_graph(codes.dvbs2_structured(seed=3, n=7200, k=3600, groups_hi=4))
+    assert (g.vn_deg == 1).sum() == 1
+    imax, B = 4, 37
+    tb = tables.random_tables(Tc, T, g.d_c_max, g.d_v_max, imax, seed=Tc + T + imax)
+    ch = np.random.default_rng(B).integers(0, Tc, (g.n_v, B))
+    ch[np.flatnonzero(g.vn_deg == 1), ::2] = Tc - 1          # the largest overshoot in every other codeword
+    pad = lambda v: np.concatenate([v, np.full(Tc * T, v[-1], v.dtype)])
+    padded = tables.IBTables(Tc, T, tb.CM, tb.VM, imax, pad(tb.cn), pad(tb.vn), pad(tb.match_cn), pad(tb.match_vn))
+    for early in (False, True):
+        out, it = oracle.ib_decode(g, tb, ch, match=True, early_stop=early, return_iters=True)
+        ref, ref_it = oracle.ib_decode(g, padded, ch, match=True, early_stop=early, return_iters=True)
+        assert it == ref_it == imax - 1
+        assert out.min() >= 0 and out.max() < T
+        np.testing.assert_array_equal(out, ref)
+
+
 def test_oracle_minsum_node_ops_equal_reference(golden):
     """min-sum CN fold and VN sum == the reference's host operations
     (min_sum_decoder_irreg.py:298-320), including zero inputs."""
