@@ -281,7 +281,21 @@ int ibl_float_timing_read(ibl_float* h, double* cn_ms, int32_t* cn_launches, dou
  *   early_stop = 0: no syndrome, every codeword runs imax iterations, iters[b] = imax
  * alpha = 1, beta = 0 is plain layered min-sum.  The early stop is PER CODEWORD (the flooding decoders above
  * stop the whole batch together, as the reference does).
- * Preconditions: channel LLRs finite; check degrees in [2, 16] (else IBL_EUNSUPPORTED).
+ * Preconditions: channel LLRs finite; check degrees in [2, 32] (else IBL_EUNSUPPORTED).
+ *
+ * Narrow and wide handles.  A handle is WIDE when its code has a check of degree above 16 (DVB-S2 normal frames of
+ *   rates 4/5 .. 9/10: degrees 18, 22, 27, 30; 5G NR base graph 1: 19); every other handle is narrow, and for it
+ *   every statement below holds as written.  A wide handle keeps, for EVERY check of its code, the sign bits of R
+ *   in a whole 32-bit word and the argmin position in a word of its own — four 4-byte words per check and codeword
+ *   (corrected m1, corrected m2, sign bits, position) where a narrow handle keeps three — and runs kernels of its
+ *   own for the steps that touch that state (the fused kernel, the staging launch, the layer launches and the row
+ *   move of the compaction).  Read for a wide handle:  12 n_c -> 16 n_c  in the fit rule
+ *   cw_per_group = min(8, floor(160 KiB / (4 N + 16 n_c))) (IBL_PATH_AUTO judges a wide code by it, and the "does
+ *   not fit" message names it) and in the per-layer memory (about 4 N + 16 n_c bytes per codeword of max_batch: a
+ *   fourth [n_c][ldb] array; an iteration moves 8 E + 32 n_c bytes per codeword);  n_v + 3 n_c -> n_v + 4 n_c  rows
+ *   in the compaction's row move.  The semantics, the launch chain and its count per decode, the stop masks, the
+ *   packed hard decisions, the syndrome and finalise kernels and the "no allocation, no host synchronisation,
+ *   capturable" guarantee are the same.  ibl_layered_is_wide tells which kind a handle is.
  *
  * ibl_layers_validate  (host only, no device) checks cover, disjointness, no variable shared within a layer
  *   (IBL_EINVAL) and the degree range (IBL_EUNSUPPORTED); ibl_last_error names the first offending check.
@@ -313,6 +327,8 @@ int ibl_float_timing_read(ibl_float* h, double* cn_ms, int32_t* cn_launches, dou
  *   environment at create selects the syndrome's other form (one launch that gathers the sign bits per check;
  *   same results, measured slower: DESIGN.md); any value but gather / packed is IBL_EINVAL.
  * ibl_layered_path_in_use  *fused = 1 when decodes run the fused kernel, 0 for the per-layer kernels.
+ * ibl_layered_is_wide  *wide = 1 for a handle (fp32 or fixed point) whose code has a check of degree above 16, else
+ *   0; NULL arguments are IBL_EINVAL.
  * ibl_layered_decode  d_llr [N][B] IBL_F32 in, d_out [N][B] IBL_F32 APP LLRs out, d_iters [B] int32 (or NULL):
  *   iterations run per codeword.  Asynchronous on `stream`, no host synchronisation.
  * ibl_layered_geometry the launch geometry ibl_layered_decode uses for a batch of B: codewords per workgroup,
@@ -351,6 +367,7 @@ int ibl_layered_create_path(const ibl_graph* g, int32_t n_layers, const int32_t*
                             const int32_t* layer_checks, int32_t imax, float alpha, float beta, float llr_max,
                             int32_t precision, int32_t max_batch, int32_t path, ibl_layered** out);
 int ibl_layered_path_in_use(const ibl_layered* h, int32_t* fused);
+int ibl_layered_is_wide(const ibl_layered* h, int32_t* wide);
 int ibl_layered_decode(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out,
                        int32_t out_dtype, int32_t early_stop, int32_t* d_iters, void* stream);
 int ibl_layered_geometry(const ibl_layered* h, int32_t B, int32_t* cw_per_group, int32_t* ngroups, int32_t* grid);
@@ -400,6 +417,12 @@ void ibl_layered_destroy(ibl_layered* h);
  *   memory  N ldb + 4 n_c ldb + 8 N ceil(max_batch / 64) + 64 ldb / 256 + 4  bytes, about N + 4 n_c + N / 8 per
  *   codeword (DVB-S2 N = 64800 rate 1/2: 202.5 KB per codeword, 1.66 GB at 8192, against 5.3 GB in fp32).  An
  *   iteration moves 2 E + 8 n_c bytes per codeword (fp32: 8 E + 24 n_c).
+ *   A WIDE handle (a check of degree above 16; ibl_layered_is_wide) keeps TWO 32-bit words per check and codeword,
+ *   for every check of its code, in two arrays [n_c][ldb] — word 0 = corrected m2 << 11 | corrected m1 << 5 | first
+ *   argmin position (5 bits), word 1 = the sign bits of R, edge k at bit k — a lane's four codewords one 16-byte
+ *   access per array:  memory  N ldb + 8 n_c ldb + ...  as above, about N + 8 n_c + N / 8 bytes per codeword; an
+ *   iteration moves 2 E + 16 n_c bytes per codeword.  Its staging and layer launches are kernels of their own;
+ *   everything else, the launch chain included, is as for a narrow handle.
  *   ibl_layered_decode on such a handle takes llr_dtype and out_dtype in {IBL_F32, IBL_I8} in any combination
  *   (anything else is IBL_EINVAL); d_out may be d_llr when the dtypes match.  It enqueues the launch chain of the
  *   fp32 per-layer path (staging, n_layers launches per iteration, pack / syndrome / finalise after every iteration

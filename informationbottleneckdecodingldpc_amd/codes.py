@@ -329,8 +329,8 @@ def greedy_layers(H):
 
 def validate_layers(H, layers) -> None:
     """Raise ``ValueError`` unless ``layers`` (sequences of check indices) are disjoint, cover every check of H,
-    hold no two checks sharing a variable within one layer, and every check has degree 2..16 (what the layered
-    decoder supports). The message names the first offending check."""
+    hold no two checks sharing a variable within one layer, and every check has degree 2..32 (what the layered
+    decoder supports; a code with a check above 16 gets the decoder's wide kernels). The message names the first offending check."""
     A = canonical_csr(H)
     n_c, n_v = A.shape
     layer_of = np.full(n_c, -1, dtype=np.int64)
@@ -350,10 +350,10 @@ def validate_layers(H, layers) -> None:
     if missing.size:
         raise ValueError(f"check {int(missing[0])} is in no layer")
     deg = np.diff(A.indptr)
-    bad = np.nonzero((deg < 2) | (deg > 16))[0]
+    bad = np.nonzero((deg < 2) | (deg > 32))[0]
     if bad.size:
         raise ValueError(f"check {int(bad[0])} has degree {int(deg[bad[0]])}: layered decoding supports check "
-                         "degrees 2..16")
+                         "degrees 2..32")
 
 
 def code_rate(H) -> float:

@@ -37,6 +37,10 @@ struct ibl_layered {
   int32_t compact_every = 0, compact_pct = 0;
   DevBuf<int32_t> orig, dest, ctl;
   int32_t last_B = 0, last_compact = 0;   // the last decode: its batch, and whether it ran with compaction
+  // wide (a check of degree 17..32; layered_plan.h layered_is_wide): the *_wide kernels and one more state array,
+  // PO [n_c][ldb] on the fp32 per-layer path, S1 [n_c][ldb] in fixed point (the fused kernel's PO is in LDS)
+  int32_t wide = 0;
+  DevBuf<uint32_t> PO, S1;
 };
 
 namespace {
@@ -61,15 +65,20 @@ int layered_create_passes(const ibl_graph* g, const std::vector<int32_t>& ip, in
       (rows * pass_tiles(max_batch) + kLayPassWaves - 1) / kLayPassWaves > 0x7fffffffll)
     return fail(IBL_EINVAL, "max_batch is too large for the per-layer kernels' grids");
   HIPCHK(hipSetDevice(g->device));
-  size_t priv = 0;
+  const bool wide = layered_is_wide(g->n_c, ip.data());
+  size_t priv = 0, priv_wide = 0;
   HIPCHK(lay_pass_private_bytes(&priv));
-  int rc = refuse_private(priv, "a per-layer layered kernel has a ", "-byte private segment (register spill): rebuild required");
+  if (wide) HIPCHK(lay_wide_private_bytes(&priv_wide));
+  int rc = refuse_private(std::max(priv, priv_wide), "a per-layer layered kernel has a ",
+                          "-byte private segment (register spill): rebuild required");
   if (rc) return rc;
   std::unique_ptr<ibl_layered> h(new ibl_layered());
   h->g = g; h->imax = imax; h->max_batch = max_batch; h->alpha = alpha; h->beta = beta; h->llr_max = llr_max;
   h->fused = 0;
+  h->wide = wide;
   h->layer_slot = pl.layer_slot;
-  const LayeredPassBytes by = pass_bytes(g->n_v, g->n_c, max_batch);
+  const LayeredPassBytes by = pass_bytes(g->n_v, g->n_c, max_batch, wide);
+  if (wide && (rc = h->PO.alloc(by.state / 4))) return rc;
   if ((rc = h->rec.upload(pl.rec)) || (rc = h->P.alloc(by.P / 4)) || (rc = h->M1.alloc(by.state / 4)) ||
       (rc = h->M2.alloc(by.state / 4)) || (rc = h->PS.alloc(by.state / 4)) || (rc = h->done.alloc(by.mask / 8)) ||
       (rc = h->unsat.alloc(by.mask / 8)) || (rc = h->running.alloc(1)) || (rc = h->bits.alloc(by.bits / 8)))
@@ -95,18 +104,27 @@ int layered_decode_passes(ibl_layered* h, const float* d_llr, int32_t B, float* 
   c.orig = h->orig; c.dest = h->dest; c.ctl = h->ctl; c.out = d_out; c.min_free_pct = h->compact_pct;
   h->last_B = B;
   h->last_compact = every > 0;
-  if (every) HIPCHK(launch_lay_stage_in_c(a, c, d_llr, h->imax, s));
+  // a wide handle: the same chain, the stage-in, the layers and the row move in their wide forms
+  const bool wide = h->wide != 0;
+  if (wide) HIPCHK(launch_lay_stage_in_wide(a, every ? &c : nullptr, h->PO, d_llr, h->imax, s));
+  else if (every) HIPCHK(launch_lay_stage_in_c(a, c, d_llr, h->imax, s));
   else HIPCHK(launch_lay_stage_in(a, d_llr, h->imax, s));
   const int32_t n_layers = (int32_t)h->layer_slot.size() - 1;
   for (int32_t it = 1; it <= h->imax; ++it) {
-    for (int32_t l = 0; l < n_layers; ++l)
-      HIPCHK(launch_lay_layer(a, h->layer_slot[l], h->layer_slot[l + 1] - h->layer_slot[l], s));
+    for (int32_t l = 0; l < n_layers; ++l) {
+      const int32_t s0 = h->layer_slot[l], n = h->layer_slot[l + 1] - s0;
+      if (wide) HIPCHK(launch_lay_layer_wide(a, h->PO, s0, n, s));
+      else HIPCHK(launch_lay_layer(a, s0, n, s));
+    }
     if (early_stop && it < h->imax) {
       HIPCHK(launch_lay_syndrome(a, h->syn_packed, s));
       if (every) HIPCHK(launch_lay_finalise_c(a, c, it, s));
       else HIPCHK(launch_lay_finalise(a, it, s));
       // the device decides whether the attempt moves anything (layered_plan.h compact_wanted)
-      if (every && it % every == 0) HIPCHK(launch_lay_compact(a, c, s));
+      if (every && it % every == 0) {
+        if (wide) HIPCHK(launch_lay_compact_wide(a, c, h->PO, s));
+        else HIPCHK(launch_lay_compact(a, c, s));
+      }
     }
   }
   if (every) HIPCHK(launch_lay_stage_out_c(a, c, s));
@@ -122,11 +140,16 @@ int layered_run_fixed(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int3
   a.rec = h->rec; a.cols = g->csr_cols; a.iters = d_iters;
   a.alpha16 = h->alpha16; a.beta_q = h->beta_q; a.q_max = h->q_max; a.scale = h->scale;
   a.n_v = g->n_v; a.n_c = g->n_c; a.B = B; a.ntiles = pass_tiles(B); a.ntiles4 = fix_tiles(B);
-  HIPCHK(launch_layfix_stage_in(a, d_llr, llr_dtype, h->imax, s));
+  const bool wide = h->wide != 0;
+  if (wide) HIPCHK(launch_layfix_stage_in_wide(a, h->S1, d_llr, llr_dtype, h->imax, s));
+  else HIPCHK(launch_layfix_stage_in(a, d_llr, llr_dtype, h->imax, s));
   const int32_t n_layers = (int32_t)h->layer_slot.size() - 1;
   for (int32_t it = 1; it <= h->imax; ++it) {
-    for (int32_t l = 0; l < n_layers; ++l)
-      HIPCHK(launch_layfix_layer(a, h->layer_slot[l], h->layer_slot[l + 1] - h->layer_slot[l], s));
+    for (int32_t l = 0; l < n_layers; ++l) {
+      const int32_t s0 = h->layer_slot[l], n = h->layer_slot[l + 1] - s0;
+      if (wide) HIPCHK(launch_layfix_layer_wide(a, h->S1, s0, n, s));
+      else HIPCHK(launch_layfix_layer(a, s0, n, s));
+    }
     if (early_stop && it < h->imax) HIPCHK(launch_layfix_stop(a, it, s));
   }
   HIPCHK(launch_layfix_stage_out(a, d_out, out_dtype, s));
@@ -166,24 +189,28 @@ int ibl_layered_create_path(const ibl_graph* g, int32_t n_layers, const int32_t*
   const std::vector<int32_t> ip = graph_indptr(g);
   int rc = ibl_layers_validate(g->n_v, g->n_c, ip.data(), g->h_cols.data(), n_layers, layer_ptr, layer_checks);
   if (rc) return rc;
-  if (path == IBL_PATH_PASSES || (path == IBL_PATH_AUTO && layered_cw_per_group(g->n_v, g->n_c) < 1))
+  const bool wide = layered_is_wide(g->n_c, ip.data());
+  if (path == IBL_PATH_PASSES || (path == IBL_PATH_AUTO && layered_cw_per_group(g->n_v, g->n_c, wide) < 1))
     return layered_create_passes(g, ip, n_layers, layer_ptr, layer_checks, imax, alpha, beta, llr_max, max_batch, out);
   LayeredPlan pl;
   plan_layered(g->n_v, g->n_c, ip.data(), g->h_cols.data(), n_layers, layer_ptr, layer_checks, &pl);
   if (pl.cw_per_group < 1)
-    return fail(IBL_EUNSUPPORTED, "code does not fit the layered kernel: one codeword needs 4 N + 12 n_c = " +
-                                      std::to_string(pl.cw_bytes) + " bytes of LDS, a workgroup has " +
-                                      std::to_string(kLayLds));
+    return fail(IBL_EUNSUPPORTED, std::string("code does not fit the layered kernel: one codeword needs ") +
+                                      (wide ? "4 N + 16 n_c = " : "4 N + 12 n_c = ") + std::to_string(pl.cw_bytes) +
+                                      " bytes of LDS, a workgroup has " + std::to_string(kLayLds));
   HIPCHK(hipSetDevice(g->device));
   std::unique_ptr<ibl_layered> h(new ibl_layered());
   h->g = g; h->imax = imax; h->max_batch = max_batch; h->alpha = alpha; h->beta = beta; h->llr_max = llr_max;
   h->n_tasks = pl.n_tasks; h->cw_per_group = pl.cw_per_group; h->cw_bytes = pl.cw_bytes;
+  h->wide = wide;
   if ((rc = h->task.upload(pl.task)) || (rc = h->idx.upload(pl.idx)) ||
       (rc = h->buf.alloc((size_t)max_batch * (size_t)g->n_v)))
     return rc;
   int bpc = 0;
   size_t priv = 0;
-  const hipError_t e = lay_fused_occupancy(h->cw_per_group, (size_t)h->cw_per_group * h->cw_bytes, &bpc, &priv);
+  const size_t lds = (size_t)h->cw_per_group * h->cw_bytes;
+  const hipError_t e = wide ? lay_fused_wide_occupancy(h->cw_per_group, lds, &bpc, &priv)
+                            : lay_fused_occupancy(h->cw_per_group, lds, &bpc, &priv);
   if (e != hipSuccess) return fail(IBL_EHIP, std::string("layered kernel occupancy: ") + hipGetErrorString(e));
   if (bpc < 1) return fail(IBL_EHIP, "no occupancy for the layered kernel");
   // same guard as the other fused kernels: built to run without scratch
@@ -218,19 +245,24 @@ int ibl_layered_create_fixed(const ibl_graph* g, int32_t n_layers, const int32_t
       (rows * fix_tiles(max_batch) + kLayPassWaves - 1) / kLayPassWaves > 0x7fffffffll)
     return fail(IBL_EINVAL, "max_batch is too large for the per-layer kernels' grids");
   HIPCHK(hipSetDevice(g->device));
-  size_t priv = 0, priv_stop = 0;
+  const bool wide = layered_is_wide(g->n_c, ip.data());
+  size_t priv = 0, priv_stop = 0, priv_wide = 0;
   HIPCHK(layfix_private_bytes(&priv));
   HIPCHK(lay_pass_private_bytes(&priv_stop));   // the shared syndrome and finalise kernels
-  if ((rc = refuse_private(std::max(priv, priv_stop), "a fixed-point layered kernel has a ",
+  if (wide) HIPCHK(lay_wide_private_bytes(&priv_wide));
+  if ((rc = refuse_private(std::max({priv, priv_stop, priv_wide}), "a fixed-point layered kernel has a ",
                            "-byte private segment (register spill): rebuild required")))
     return rc;
   std::unique_ptr<ibl_layered> h(new ibl_layered());
   h->g = g; h->imax = imax; h->max_batch = max_batch;
-  h->fused = 0; h->fixed = 1;
+  h->fused = 0; h->fixed = 1; h->wide = wide;
   h->alpha16 = alpha16; h->beta_q = beta_q; h->q_max = q_max; h->scale = scale;
   h->layer_slot = pl.layer_slot;
-  const LayeredFixBytes by = fix_bytes(g->n_v, g->n_c, max_batch);
-  if ((rc = h->rec.upload(pl.rec)) || (rc = h->P8.alloc(by.P)) || (rc = h->S.alloc(by.state / 4)) ||
+  // a wide handle's two state arrays are allocations of their own, by.state bytes together
+  const LayeredFixBytes by = fix_bytes(g->n_v, g->n_c, max_batch, wide);
+  const size_t s_words = by.state / (wide ? 8 : 4);
+  if (wide && (rc = h->S1.alloc(s_words))) return rc;
+  if ((rc = h->rec.upload(pl.rec)) || (rc = h->P8.alloc(by.P)) || (rc = h->S.alloc(s_words)) ||
       (rc = h->done.alloc(by.mask / 8)) || (rc = h->unsat.alloc(by.mask / 8)) || (rc = h->running.alloc(1)) ||
       (rc = h->bits.alloc(by.bits / 8)))
     return rc;
@@ -241,6 +273,12 @@ int ibl_layered_create_fixed(const ibl_graph* g, int32_t n_layers, const int32_t
 int ibl_layered_is_fixed(const ibl_layered* h, int32_t* fixed) {
   if (!h || !fixed) return fail(IBL_EINVAL, "NULL argument");
   *fixed = h->fixed;
+  return IBL_OK;
+}
+
+int ibl_layered_is_wide(const ibl_layered* h, int32_t* wide) {
+  if (!h || !wide) return fail(IBL_EINVAL, "NULL argument");
+  *wide = h->wide;
   return IBL_OK;
 }
 
@@ -256,7 +294,7 @@ int ibl_layered_set_compaction(ibl_layered* h, int32_t every, int32_t min_free_p
     return IBL_OK;
   }
   if (!h->ctl) {
-    if ((pass_compact_rows(h->g->n_v, h->g->n_c) + kLayPassWaves - 1) / kLayPassWaves > 0x7fffffffll)
+    if ((pass_compact_rows(h->g->n_v, h->g->n_c, h->wide != 0) + kLayPassWaves - 1) / kLayPassWaves > 0x7fffffffll)
       return fail(IBL_EINVAL, "the code is too large for the compaction kernels' grid");
     HIPCHK(hipSetDevice(h->g->device));
     size_t priv = 0;
@@ -348,7 +386,8 @@ int ibl_layered_decode(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int
     a.trace = tr.d;
   }
 #endif
-  HIPCHK(launch_lay_fused(a, grid, (size_t)h->cw_per_group * h->cw_bytes, s));
+  if (h->wide) HIPCHK(launch_lay_fused_wide(a, grid, (size_t)h->cw_per_group * h->cw_bytes, s));
+  else HIPCHK(launch_lay_fused(a, grid, (size_t)h->cw_per_group * h->cw_bytes, s));
 #if IBL_DIAG
   if (ltrace && (rc = tr.save(s, ltrace, 0, tr.n))) return rc;
 #endif

@@ -437,4 +437,21 @@ hipError_t launch_layfix_stop(const LayFixArgs& a, int it, hipStream_t s);
 hipError_t launch_layfix_stage_out(const LayFixArgs& a, void* out, int32_t dtype, hipStream_t s);
 hipError_t layfix_private_bytes(size_t* bytes);
 
+// Wide handles (a check of degree 17..32; layered_plan.h layered_is_wide): the kernels that touch the check state
+// have wide forms, which take the added state array as an argument of their own — PO [n_c][ldb], the fp32 argmin
+// positions (PS is then all sign bits), or S1 [n_c][ldb], the fixed-point sign words (S is then word 0 of
+// fix_state_words_wide) — so the argument structs and every narrow launch stay as they are. The fused kernel's PO
+// follows PS in the wave's LDS slice (cw_bytes = 4 N + 16 n_c). Every other launcher above serves both.
+hipError_t lay_fused_wide_occupancy(int cw_per_group, size_t lds, int* blocks_per_cu, size_t* private_bytes);
+hipError_t launch_lay_fused_wide(const LayeredArgs& a, int grid, size_t lds, hipStream_t s);
+// c: nullptr without compaction
+hipError_t launch_lay_stage_in_wide(const LayPassArgs& a, const LayCompactArgs* c, uint32_t* PO, const float* llr,
+                                    int imax, hipStream_t s);
+hipError_t launch_lay_layer_wide(const LayPassArgs& a, uint32_t* PO, int slot0, int n_checks, hipStream_t s);
+hipError_t launch_lay_compact_wide(const LayPassArgs& a, const LayCompactArgs& c, uint32_t* PO, hipStream_t s);
+hipError_t launch_layfix_stage_in_wide(const LayFixArgs& a, uint32_t* S1, const void* llr, int32_t dtype, int imax,
+                                       hipStream_t s);
+hipError_t launch_layfix_layer_wide(const LayFixArgs& a, uint32_t* S1, int slot0, int n_checks, hipStream_t s);
+hipError_t lay_wide_private_bytes(size_t* bytes);
+
 }  // namespace ibl

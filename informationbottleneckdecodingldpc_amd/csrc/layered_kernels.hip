@@ -295,10 +295,11 @@ __device__ __forceinline__ void lay_cn_rows(const LayPassArgs& a, int e0, size_t
 
 // P = llr + 0 (a -0 enters as +0), padding lanes 0; state rows 0; masks, counter and iters reset.
 // item = (row < max(n_v, n_c), tile). kCompact: also orig = the identity, extent = B, no compaction yet.
+// kWide: also the rows of PO, the wide handle's fourth state array.
 namespace {
-template <bool kCompact>
+template <bool kCompact, bool kWide = false>
 __device__ __forceinline__ void lay_stage_in_body(const LayPassArgs& a, const float* __restrict__ llr, int imax,
-                                                  const LayCompactArgs* c) {
+                                                  const LayCompactArgs* c, uint32_t* PO = nullptr) {
   const int lane = (int)(threadIdx.x & 63u);
   const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + (int64_t)(threadIdx.x >> 6);
   const int64_t rows = a.n_v > a.n_c ? a.n_v : a.n_c;
@@ -313,6 +314,7 @@ __device__ __forceinline__ void lay_stage_in_body(const LayPassArgs& a, const fl
     a.M1[at] = 0.f;
     a.M2[at] = 0.f;
     a.PS[at] = 0u;
+    if constexpr (kWide) PO[at] = 0u;
   }
   if (row == 0) {
     if (a.iters && b < a.B) a.iters[b] = imax;
@@ -341,6 +343,15 @@ __global__ __launch_bounds__(64 * kLayPassWaves) void lay_stage_in(const LayPass
 __global__ __launch_bounds__(64 * kLayPassWaves) void lay_stage_in_c(const LayPassArgs a, const LayCompactArgs c,
                                                                      const float* __restrict__ llr, int imax) {
   lay_stage_in_body<true>(a, llr, imax, &c);
+}
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_stage_in_wide(const LayPassArgs a, uint32_t* PO,
+                                                                        const float* __restrict__ llr, int imax) {
+  lay_stage_in_body<false, true>(a, llr, imax, nullptr, PO);
+}
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_stage_in_c_wide(const LayPassArgs a, const LayCompactArgs c,
+                                                                          uint32_t* PO, const float* __restrict__ llr,
+                                                                          int imax) {
+  lay_stage_in_body<true, true>(a, llr, imax, &c, PO);
 }
 
 // item = (check slot0 + c of the layer, tile), tile fastest
@@ -558,12 +569,16 @@ __global__ __launch_bounds__(64 * kLayPassWaves) void lay_compact_plan(const Lay
 // chunk's last source, and the sources of every later chunk lie above it. A store can therefore only hit a source
 // of its own chunk or of an earlier one, and all of those were loaded before the chunk's first store: load, wait,
 // store per chunk in ascending order is the whole argument. Destinations are distinct, so stores do not collide.
+// kWide: the rows of PO, the wide handle's fourth state array, move too.
 constexpr int kLayCompactChunk = 4;
-__global__ __launch_bounds__(64 * kLayPassWaves) void lay_compact_rows(const LayPassArgs a, const LayCompactArgs c) {
+namespace {
+template <bool kWide>
+// (the arguments by value, as the kernels have them: by reference the narrow kernel's scalar allocation changes)
+__device__ __forceinline__ void lay_compact_rows_body(const LayPassArgs a, const LayCompactArgs c, uint32_t* PO) {
   if (sload(c.ctl, kLayCtlDo) == 0) return;
   const int lane = (int)(threadIdx.x & 63u);
   const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (item >= (int64_t)a.n_v + 3 * (int64_t)a.n_c) return;
+  if (item >= (int64_t)a.n_v + (kWide ? 4 : 3) * (int64_t)a.n_c) return;
   const int E = sload(c.ctl, kLayCtlExtent);
   const size_t ldb = (size_t)a.ntiles * kLayTile;
   const bool is_p = item < a.n_v;
@@ -577,6 +592,7 @@ __global__ __launch_bounds__(64 * kLayPassWaves) void lay_compact_rows(const Lay
     const int64_t r = item - a.n_v;
     const int which = (int)(r / a.n_c);
     uint32_t* base = which == 0 ? reinterpret_cast<uint32_t*>(a.M1) : which == 1 ? reinterpret_cast<uint32_t*>(a.M2) : a.PS;
+    if constexpr (kWide) base = which == 3 ? PO : base;
     row = base + (size_t)(r % a.n_c) * ldb;
   }
   for (int c0 = 0; c0 < E; c0 += kLayCompactChunk * kLayTile) {
@@ -604,6 +620,15 @@ __global__ __launch_bounds__(64 * kLayPassWaves) void lay_compact_rows(const Lay
       else orow[c.orig[c0 + j * kLayTile + lane]] = x[j];
     }
   }
+}
+}  // namespace
+
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_compact_rows(const LayPassArgs a, const LayCompactArgs c) {
+  lay_compact_rows_body<false>(a, c, nullptr);
+}
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_compact_rows_wide(const LayPassArgs a, const LayCompactArgs c,
+                                                                            uint32_t* PO) {
+  lay_compact_rows_body<true>(a, c, PO);
 }
 
 // One workgroup: orig follows the move (orig[dest[c]] = orig[c], by the row move's ascending chunk rule with a
@@ -837,9 +862,12 @@ __device__ __forceinline__ void layfix_cn_rows(const LayFixArgs& a, int e0, size
 }  // namespace
 
 // P = the quantised (IBL_F32) or copied (IBL_I8, -128 -> -127) channel values, padding codewords 0; state words 0;
-// masks, counter and iters reset. item = (row < max(n_v, n_c), tile of 256)
-__global__ __launch_bounds__(64 * kLayPassWaves) void layfix_stage_in(const LayFixArgs a, const void* __restrict__ llr,
-                                                                      int dtype, int imax) {
+// masks, counter and iters reset. item = (row < max(n_v, n_c), tile of 256). kWide: also the words of S1, the wide
+// handle's second state array.
+namespace {
+template <bool kWide>
+__device__ __forceinline__ void layfix_stage_in_body(const LayFixArgs& a, uint32_t* S1, const void* __restrict__ llr,
+                                                     int dtype, int imax) {
   const int lane = (int)(threadIdx.x & 63u);
   const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + (int64_t)(threadIdx.x >> 6);
   const int64_t rows = a.n_v > a.n_c ? a.n_v : a.n_c;
@@ -868,7 +896,10 @@ __global__ __launch_bounds__(64 * kLayPassWaves) void layfix_stage_in(const LayF
     }
     *reinterpret_cast<uint32_t*>(a.P + at) = w;
   }
-  if (row < a.n_c) *reinterpret_cast<uint4*>(a.S + at) = make_uint4(0u, 0u, 0u, 0u);
+  if (row < a.n_c) {
+    *reinterpret_cast<uint4*>(a.S + at) = make_uint4(0u, 0u, 0u, 0u);
+    if constexpr (kWide) *reinterpret_cast<uint4*>(S1 + at) = make_uint4(0u, 0u, 0u, 0u);
+  }
   if (row == 0) {
     if (a.iters) {
 #pragma unroll
@@ -883,6 +914,17 @@ __global__ __launch_bounds__(64 * kLayPassWaves) void layfix_stage_in(const LayF
     }
     if (lane == 0 && tile == 0) *a.running = a.B;
   }
+}
+}  // namespace
+
+__global__ __launch_bounds__(64 * kLayPassWaves) void layfix_stage_in(const LayFixArgs a, const void* __restrict__ llr,
+                                                                      int dtype, int imax) {
+  layfix_stage_in_body<false>(a, nullptr, llr, dtype, imax);
+}
+__global__ __launch_bounds__(64 * kLayPassWaves) void layfix_stage_in_wide(const LayFixArgs a, uint32_t* S1,
+                                                                           const void* __restrict__ llr, int dtype,
+                                                                           int imax) {
+  layfix_stage_in_body<true>(a, S1, llr, dtype, imax);
 }
 
 // item = (check slot0 + c of the layer, tile of 256), tile fastest
@@ -1012,6 +1054,363 @@ hipError_t layfix_private_bytes(size_t* bytes) {
   *bytes = 0;
   for (const void* f : {(const void*)layfix_stage_in, (const void*)layfix_layer, (const void*)layfix_pack,
                         (const void*)layfix_stage_out}) {
+    hipFuncAttributes fa;
+    const hipError_t e = hipFuncGetAttributes(&fa, f);
+    if (e != hipSuccess) return e;
+    *bytes = std::max(*bytes, (size_t)fa.localSizeBytes);
+  }
+  return hipSuccess;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Wide checks: degrees up to kLayWideMaxD = 32 (include/ibldpc.h "Layered min-sum", wide handles; layered_plan.h
+// layered_is_wide). A handle whose code has a check of degree above 16 runs the kernels below instead of lay_fused,
+// lay_layer and layfix_layer, for EVERY check of the code: kernels of their own, because the degree bodies of one
+// kernel share one register allocation and unrolled degree-32 bodies inside lay_layer would cost the narrow codes
+// their occupancy. Steps and values are those of the narrow bodies; what differs is where the state lives:
+//   fp32        the sign bits of R fill a whole word PS (edge k at bit D - 1 - k as before), and the first argmin
+//               position has a word of its own, PO: four 4-byte words per check and codeword;
+//   fixed point two words per check and codeword in two arrays S0 / S1 [n_c][ldb] (layered_plan.h
+//               fix_state_words_wide): m2' << 11 | m1' << 5 | position, and the sign bits of R, edge k at bit k.
+// The per-layer bodies address a row as a wave-uniform base (the variable index is a scalar load and the tile is
+// the wave's) plus the lane's offset within the tile, so a check's D rows cost scalar registers and one 32-bit
+// vector offset, not D 64-bit vector addresses.
+// Everything else — syndrome, pack, finalise, stage-out, the compaction plan and commit — is shared as it stands.
+namespace {
+
+#define LAY_WIDE_CASES                                                                                          \
+  LAY_CASE(2) LAY_CASE(3) LAY_CASE(4) LAY_CASE(5) LAY_CASE(6) LAY_CASE(7) LAY_CASE(8) LAY_CASE(9) LAY_CASE(10)  \
+  LAY_CASE(11) LAY_CASE(12) LAY_CASE(13) LAY_CASE(14) LAY_CASE(15) LAY_CASE(16) LAY_CASE(17) LAY_CASE(18)       \
+  LAY_CASE(19) LAY_CASE(20) LAY_CASE(21) LAY_CASE(22) LAY_CASE(23) LAY_CASE(24) LAY_CASE(25) LAY_CASE(26)       \
+  LAY_CASE(27) LAY_CASE(28) LAY_CASE(29) LAY_CASE(30) LAY_CASE(31) LAY_CASE(32)
+
+// lay_cn with the position in PO[slot] and all of PS[slot] sign bits
+template <int D>
+__device__ __forceinline__ void lay_cn_wide(float* __restrict__ P, float* __restrict__ M1, float* __restrict__ M2,
+                                            uint32_t* __restrict__ PS, uint32_t* __restrict__ PO,
+                                            const int32_t* __restrict__ idx, int slot, float alpha, float beta,
+                                            float L) {
+  static_assert(D >= kLayMinD && D <= kLayWideMaxD, "degree body out of range");
+  int v[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) v[k] = idx[64 * k];
+  const float m1o = M1[slot], m2o = M2[slot];
+  const uint32_t ps = PS[slot], poso = PO[slot];
+  float q[D];
+  float m1 = __builtin_inff(), m2 = __builtin_inff();
+  uint32_t pos = 0, sx = 0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    const float r = lay_signed((uint32_t)k == poso ? m2o : m1o, ps << (32 - D + k));
+    const float x = __builtin_amdgcn_fmed3f(P[v[k]] - r, -L, L);
+    q[k] = x;
+    sx ^= lay_bits(x);
+    const float a = fabsf(x);
+    pos = a < m1 ? (uint32_t)k : pos;
+    m2 = __builtin_amdgcn_fmed3f(m1, m2, a);
+    m1 = fminf(m1, a);
+  }
+  const float m1n = fmaxf(alpha * m1 - beta, 0.f), m2n = fmaxf(alpha * m2 - beta, 0.f);
+  uint32_t sg = 0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    const uint32_t t = sx ^ lay_bits(q[k]);
+    P[v[k]] = q[k] + lay_signed((uint32_t)k == pos ? m2n : m1n, t);
+    sg = __builtin_amdgcn_alignbit(sg, t, 31);
+  }
+  M1[slot] = m1n;
+  M2[slot] = m2n;
+  PS[slot] = sg;
+  PO[slot] = pos;
+}
+
+// lay_cn_rows with the position in PO and all of PS sign bits. tcol: the tile's first column (wave-uniform), srow:
+// the first state word of (slot, tile) (wave-uniform); the lane's codeword is element `lane` of each.
+template <int D>
+__device__ __forceinline__ void lay_cn_rows_wide(const LayPassArgs& a, uint32_t* __restrict__ PO, int e0, size_t srow,
+                                                 size_t tcol, uint32_t lane, size_t ldb) {
+  static_assert(D >= kLayMinD && D <= kLayWideMaxD, "degree body out of range");
+  float p[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) p[k] = (a.P + ((size_t)sload(a.cols, e0 + k) * ldb + tcol))[lane];
+  const float m1o = (a.M1 + srow)[lane], m2o = (a.M2 + srow)[lane];
+  const uint32_t ps = (a.PS + srow)[lane], poso = (PO + srow)[lane];
+  const float alpha = a.alpha, beta = a.beta, L = a.llr_max;
+  float m1 = __builtin_inff(), m2 = __builtin_inff();
+  uint32_t pos = 0, sx = 0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    const float r = lay_signed((uint32_t)k == poso ? m2o : m1o, ps << (32 - D + k));
+    const float x = __builtin_amdgcn_fmed3f(p[k] - r, -L, L);
+    p[k] = x;   // Q from here on
+    sx ^= lay_bits(x);
+    const float m = fabsf(x);
+    pos = m < m1 ? (uint32_t)k : pos;
+    m2 = __builtin_amdgcn_fmed3f(m1, m2, m);
+    m1 = fminf(m1, m);
+  }
+  const float m1n = fmaxf(alpha * m1 - beta, 0.f), m2n = fmaxf(alpha * m2 - beta, 0.f);
+  uint32_t sg = 0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    const uint32_t t = sx ^ lay_bits(p[k]);
+    (a.P + ((size_t)sload(a.cols, e0 + k) * ldb + tcol))[lane] = p[k] + lay_signed((uint32_t)k == pos ? m2n : m1n, t);
+    sg = __builtin_amdgcn_alignbit(sg, t, 31);
+  }
+  (a.M1 + srow)[lane] = m1n;
+  (a.M2 + srow)[lane] = m2n;
+  (a.PS + srow)[lane] = sg;
+  (PO + srow)[lane] = pos;
+}
+
+// layfix_cn_rows with the two state words of fix_state_words_wide. tcol, srow: wave-uniform as in lay_cn_rows_wide;
+// the lane's four codewords are dword `lane` of a P row's tile and words 4 lane .. 4 lane + 3 of a state row's.
+template <int D>
+__device__ __forceinline__ void layfix_cn_rows_wide(const LayFixArgs& a, uint32_t* __restrict__ S1, int e0,
+                                                    size_t srow, size_t tcol, uint32_t lane, size_t ldb,
+                                                    uint32_t fin) {
+  static_assert(D >= kLayMinD && D <= kLayWideMaxD, "degree body out of range");
+  uint32_t p[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k)
+    p[k] = reinterpret_cast<const uint32_t*>(a.P + ((size_t)sload(a.cols, e0 + k) * ldb + tcol))[lane];
+  const uint4 st0 = reinterpret_cast<const uint4*>(a.S + srow)[lane], st1 = reinterpret_cast<const uint4*>(S1 + srow)[lane];
+  uint32_t w0[kLayFixCw] = {st0.x, st0.y, st0.z, st0.w}, w1[kLayFixCw] = {st1.x, st1.y, st1.z, st1.w};
+  const int alpha16 = a.alpha16, beta = a.beta_q, qm = a.q_max;
+#pragma unroll
+  for (int j = 0; j < kLayFixCw; ++j) {
+    if ((fin >> j) & 1u) continue;   // frozen at its stop iteration
+    const int m1o = (int)fix_wide_m1(w0[j]), m2o = (int)fix_wide_m2(w0[j]);
+    const uint32_t poso = fix_wide_pos(w0[j]), so = w1[j];
+    int t[D];
+    int m1 = kLayFixQMax + 1, m2 = kLayFixQMax + 1;
+    uint32_t pos = 0, neg = 0;
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      const int mag = (uint32_t)k == poso ? m2o : m1o;
+      const int r = ((so >> k) & 1u) ? -mag : mag;
+      const int x = (int)(int8_t)(p[k] >> (8 * j)) - r;
+      t[k] = x;
+      neg |= ((uint32_t)x >> 31) << k;
+      const int m = min(abs(x), qm);
+      pos = m < m1 ? (uint32_t)k : pos;
+      m2 = min(m2, max(m1, m));
+      m1 = min(m1, m);
+    }
+    const int m1n = max(((alpha16 * m1 + 8) >> 4) - beta, 0), m2n = max(((alpha16 * m2 + 8) >> 4) - beta, 0);
+    const uint32_t sg = ((__popc(neg) & 1) ? ~neg : neg) & fix_wide_mask(D);   // s ^ neg_e: R[e] is negated
+#pragma unroll
+    for (int k = 0; k < D; ++k) {
+      const int mag = (uint32_t)k == pos ? m2n : m1n;
+      const int r = ((sg >> k) & 1u) ? -mag : mag;
+      const int pn = min(max(t[k] + r, -kLayFixApp), kLayFixApp);
+      p[k] = (p[k] & ~(0xFFu << (8 * j))) | ((uint32_t)(pn & 0xFF) << (8 * j));
+    }
+    const FixWideWords w = fix_state_words_wide((uint32_t)m1n, (uint32_t)m2n, pos, sg);
+    w0[j] = w.w0;
+    w1[j] = w.w1;
+  }
+#pragma unroll
+  for (int k = 0; k < D; ++k)
+    reinterpret_cast<uint32_t*>(a.P + ((size_t)sload(a.cols, e0 + k) * ldb + tcol))[lane] = p[k];
+  reinterpret_cast<uint4*>(a.S + srow)[lane] = make_uint4(w0[0], w0[1], w0[2], w0[3]);
+  reinterpret_cast<uint4*>(S1 + srow)[lane] = make_uint4(w1[0], w1[1], w1[2], w1[3]);
+}
+
+}  // namespace
+
+// lay_fused for a wide handle: the wave's slice of LDS is P[n_v], M1, M2, PS, PO [n_c] (cw_bytes = 4 N + 16 n_c).
+__global__ __launch_bounds__(64 * kLayMaxCw) void lay_fused_wide(const LayeredArgs a) {
+  extern __shared__ __align__(16) unsigned char lay_lds[];
+  const int lane = (int)(threadIdx.x & 63u);
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int ncw = a.cw_per_group;
+  if (wave >= ncw) return;
+  unsigned char* base = lay_lds + (size_t)wave * (size_t)a.cw_bytes;
+  float* P = reinterpret_cast<float*>(base);
+  float* M1 = P + a.n_v;
+  float* M2 = M1 + a.n_c;
+  uint32_t* PS = reinterpret_cast<uint32_t*>(M2 + a.n_c);
+  uint32_t* PO = PS + a.n_c;
+  const float alpha = a.alpha, beta = a.beta, L = a.llr_max;
+  for (int g = (int)blockIdx.x; g < a.ngroups; g += (int)gridDim.x) {
+    const int b = g * ncw + wave;
+    if (b >= a.B) break;   // wave-uniform; later groups of this workgroup lie further still
+    float* row = a.buf + (size_t)b * (size_t)a.n_v;
+    for (int v = lane; v < a.n_v; v += 64) P[v] = row[v] + 0.f;   // a -0 enters as +0, as in lay_fused
+    for (int c = lane; c < a.n_c; c += 64) {
+      M1[c] = 0.f;
+      M2[c] = 0.f;
+      PS[c] = 0u;
+      PO[c] = 0u;
+    }
+    int it = 1;
+    for (;; ++it) {
+      for (int t = 0; t < a.n_tasks; ++t) {
+        const int first = sload(a.task, 4 * t), cnt = sload(a.task, 4 * t + 1), d = sload(a.task, 4 * t + 2),
+                  s0 = sload(a.task, 4 * t + 3);
+        if (lane < cnt) {
+          const int32_t* idx = a.idx + first + lane;
+          const int slot = s0 + lane;
+          switch (d) {
+#define LAY_CASE(D) case D: lay_cn_wide<D>(P, M1, M2, PS, PO, idx, slot, alpha, beta, L); break;
+            LAY_WIDE_CASES
+#undef LAY_CASE
+            default: break;
+          }
+        }
+        __builtin_amdgcn_wave_barrier();   // the next task's reads stay behind this task's writes (other lanes')
+      }
+      if (it >= a.imax) break;
+      if (a.early) {
+        bool bad = false;
+        for (int t = 0; t < a.n_tasks && !bad; ++t) {
+          const int first = sload(a.task, 4 * t), cnt = sload(a.task, 4 * t + 1), d = sload(a.task, 4 * t + 2);
+          uint32_t par = 0;
+          if (lane < cnt) {
+            const int32_t* ix = a.idx + first + lane;
+            for (int k = 0; k < d; ++k) par ^= (P[ix[64 * k]] < 0.f) ? 1u : 0u;
+          }
+          bad = __builtin_amdgcn_readfirstlane((int)(__ballot(par != 0) != 0ull)) != 0;
+        }
+        if (!bad) break;
+      }
+    }
+    for (int v = lane; v < a.n_v; v += 64) row[v] = P[v];
+    if (a.iters && lane == 0) a.iters[b] = it;
+  }
+}
+
+// lay_layer for a wide handle. item = (check slot0 + c of the layer, tile), tile fastest
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_layer_wide(const LayPassArgs a, uint32_t* PO, int slot0,
+                                                                     int n_checks) {
+  if (sload(a.running, 0) == 0) return;
+  const int lane = (int)(threadIdx.x & 63u);
+  const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (item >= (int64_t)n_checks * a.ntiles) return;
+  const int tile = (int)(item % a.ntiles);
+  const int slot = slot0 + (int)(item / a.ntiles);
+  const uint64_t dm = lay_mask(a.done, tile);
+  if (dm == ~0ull) return;            // wave-uniform: the whole tile is finished
+  if ((dm >> lane) & 1ull) return;    // a finished (or padding) lane loads and stores nothing
+  const int e0 = sload(a.rec, 2 * slot), d = sload(a.rec, 2 * slot + 1);
+  const size_t ldb = (size_t)a.ntiles * kLayTile;
+  const size_t tcol = (size_t)tile * kLayTile;
+  const size_t srow = (size_t)slot * ldb + tcol;
+  switch (d) {
+#define LAY_CASE(D) case D: lay_cn_rows_wide<D>(a, PO, e0, srow, tcol, (uint32_t)lane, ldb); break;
+    LAY_WIDE_CASES
+#undef LAY_CASE
+    default: break;
+  }
+}
+
+// layfix_layer for a wide handle. item = (check slot0 + c of the layer, tile of 256), tile fastest
+__global__ __launch_bounds__(64 * kLayPassWaves) void layfix_layer_wide(const LayFixArgs a, uint32_t* S1, int slot0,
+                                                                        int n_checks) {
+  if (sload(a.running, 0) == 0) return;
+  const int lane = (int)(threadIdx.x & 63u);
+  const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (item >= (int64_t)n_checks * a.ntiles4) return;
+  const int tile = (int)(item % a.ntiles4);
+  const int slot = slot0 + (int)(item / a.ntiles4);
+  bool all;
+  const uint32_t fin = layfix_finished(a.done, tile, lane, &all);
+  if (all) return;             // wave-uniform: the whole tile is finished
+  if (fin == 0xFu) return;     // the lane's four codewords are finished (or padding)
+  const int e0 = sload(a.rec, 2 * slot), d = sload(a.rec, 2 * slot + 1);
+  const size_t ldb = (size_t)a.ntiles4 * kLayFixTile;
+  const size_t tcol = (size_t)tile * kLayFixTile;
+  const size_t srow = (size_t)slot * ldb + tcol;
+  switch (d) {
+#define LAY_CASE(D) case D: layfix_cn_rows_wide<D>(a, S1, e0, srow, tcol, (uint32_t)lane, ldb, fin); break;
+    LAY_WIDE_CASES
+#undef LAY_CASE
+    default: break;
+  }
+}
+#undef LAY_WIDE_CASES
+
+hipError_t lay_fused_wide_occupancy(int cw_per_group, size_t lds, int* blocks_per_cu, size_t* private_bytes) {
+  const void* f = (const void*)lay_fused_wide;
+  hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
+  if (e != hipSuccess) return e;
+  hipFuncAttributes fa;
+  if ((e = hipFuncGetAttributes(&fa, f)) != hipSuccess) return e;
+  *private_bytes = fa.localSizeBytes;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, f, 64 * cw_per_group, lds);
+}
+
+hipError_t launch_lay_fused_wide(const LayeredArgs& a, int grid, size_t lds, hipStream_t s) {
+  if (!a.buf || !a.task || !a.idx || a.cw_per_group < 1 || a.cw_per_group > kLayMaxCw || a.n_tasks < 1 ||
+      a.B < 1 || a.ngroups < 1 || grid < 1 || lds < (size_t)a.cw_per_group * (size_t)a.cw_bytes ||
+      lds > (size_t)kLdsBytes || (size_t)a.cw_bytes < layered_cw_bytes(a.n_v, a.n_c, true))
+    return hipErrorInvalidValue;
+  LayeredArgs args = a;
+  void* p[] = {&args};
+  return hipLaunchKernel((const void*)lay_fused_wide, dim3(grid), dim3(64 * a.cw_per_group), p, lds, s);
+}
+
+hipError_t launch_lay_stage_in_wide(const LayPassArgs& a, const LayCompactArgs* c, uint32_t* PO, const float* llr,
+                                    int imax, hipStream_t s) {
+  if (!lay_pass_args_ok(a) || !PO || !llr || (c && !lay_compact_args_ok(*c))) return hipErrorInvalidValue;
+  LayPassArgs args = a;
+  const int64_t items = (int64_t)std::max(a.n_v, a.n_c) * a.ntiles;
+  if (!c) {
+    void* p[] = {&args, (void*)&PO, (void*)&llr, (void*)&imax};
+    return lay_pass_launch((const void*)lay_stage_in_wide, items, p, s);
+  }
+  LayCompactArgs ca = *c;
+  void* p[] = {&args, &ca, (void*)&PO, (void*)&llr, (void*)&imax};
+  return lay_pass_launch((const void*)lay_stage_in_c_wide, items, p, s);
+}
+
+hipError_t launch_lay_layer_wide(const LayPassArgs& a, uint32_t* PO, int slot0, int n_checks, hipStream_t s) {
+  if (!lay_pass_args_ok(a) || !PO || slot0 < 0 || n_checks < 0 || (int64_t)slot0 + n_checks > a.n_c)
+    return hipErrorInvalidValue;
+  if (n_checks == 0) return hipSuccess;
+  LayPassArgs args = a;
+  void* p[] = {&args, (void*)&PO, (void*)&slot0, (void*)&n_checks};
+  return lay_pass_launch((const void*)lay_layer_wide, pass_items(n_checks, a.B), p, s);
+}
+
+// launch_lay_compact with the row move over the four state arrays
+hipError_t launch_lay_compact_wide(const LayPassArgs& a, const LayCompactArgs& c, uint32_t* PO, hipStream_t s) {
+  if (!lay_pass_args_ok(a) || !lay_compact_args_ok(c) || !PO) return hipErrorInvalidValue;
+  LayPassArgs args = a;
+  LayCompactArgs ca = c;
+  void* p[] = {&args, &ca};
+  void* pr[] = {&args, &ca, (void*)&PO};
+  hipError_t e = hipLaunchKernel((const void*)lay_compact_plan, dim3(1), dim3(64 * kLayPassWaves), p, 0, s);
+  if (e != hipSuccess) return e;
+  if ((e = lay_pass_launch((const void*)lay_compact_rows_wide, pass_compact_rows(a.n_v, a.n_c, true), pr, s)) != hipSuccess)
+    return e;
+  return hipLaunchKernel((const void*)lay_compact_commit, dim3(1), dim3(64 * kLayPassWaves), p, 0, s);
+}
+
+hipError_t launch_layfix_stage_in_wide(const LayFixArgs& a, uint32_t* S1, const void* llr, int32_t dtype, int imax,
+                                       hipStream_t s) {
+  if (!layfix_args_ok(a) || !S1 || !llr || !layfix_dtype_ok(dtype)) return hipErrorInvalidValue;
+  LayFixArgs args = a;
+  void* p[] = {&args, (void*)&S1, (void*)&llr, (void*)&dtype, (void*)&imax};
+  return lay_pass_launch((const void*)layfix_stage_in_wide, (int64_t)std::max(a.n_v, a.n_c) * a.ntiles4, p, s);
+}
+
+hipError_t launch_layfix_layer_wide(const LayFixArgs& a, uint32_t* S1, int slot0, int n_checks, hipStream_t s) {
+  if (!layfix_args_ok(a) || !S1 || slot0 < 0 || n_checks < 0 || (int64_t)slot0 + n_checks > a.n_c)
+    return hipErrorInvalidValue;
+  if (n_checks == 0) return hipSuccess;
+  LayFixArgs args = a;
+  void* p[] = {&args, (void*)&S1, (void*)&slot0, (void*)&n_checks};
+  return lay_pass_launch((const void*)layfix_layer_wide, fix_items(n_checks, a.B), p, s);
+}
+
+// the largest private (scratch) segment over the kernels only a wide handle launches: built to run without one
+hipError_t lay_wide_private_bytes(size_t* bytes) {
+  *bytes = 0;
+  for (const void* f : {(const void*)lay_fused_wide, (const void*)lay_stage_in_wide, (const void*)lay_stage_in_c_wide,
+                        (const void*)lay_layer_wide, (const void*)lay_compact_rows_wide,
+                        (const void*)layfix_stage_in_wide, (const void*)layfix_layer_wide}) {
     hipFuncAttributes fa;
     const hipError_t e = hipFuncGetAttributes(&fa, f);
     if (e != hipSuccess) return e;

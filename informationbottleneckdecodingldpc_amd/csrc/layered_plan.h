@@ -3,8 +3,9 @@
 // Built into libibldpc.so (capi_layered.hip includes this header) and, with AddressSanitizer and
 // UndefinedBehaviorSanitizer, into the CPU-only checkers tests/asan/layered_plan_check.cpp
 // (tests/test_cpu_layered.py), tests/asan/layered_pass_plan_check.cpp (tests/test_cpu_layered_passes.py),
-// tests/asan/layered_fixed_plan_check.cpp (tests/test_cpu_layered_fixed.py) and
-// tests/asan/layered_compact_plan_check.cpp (tests/test_cpu_layered_compact.py).
+// tests/asan/layered_fixed_plan_check.cpp (tests/test_cpu_layered_fixed.py),
+// tests/asan/layered_compact_plan_check.cpp (tests/test_cpu_layered_compact.py) and
+// tests/asan/layered_wide_plan_check.cpp (tests/test_cpu_layered_wide.py).
 //
 // A layer is a set of checks no two of which share a variable; the layers are disjoint, cover every check and
 // are decoded in order (include/ibldpc.h "Layered min-sum"). The device plan cuts every layer into tasks of up
@@ -21,13 +22,24 @@
 
 namespace ibl {
 
-constexpr int kLayMinD = 2, kLayMaxD = 16;      // check degrees of the layered kernel's bodies
+constexpr int kLayMinD = 2, kLayMaxD = 16;      // check degrees of the narrow kernels' bodies
+constexpr int kLayWideMaxD = 32;                // check degrees up to this run the wide kernels (below)
 constexpr int kLayLds = 160 * 1024;             // LDS bytes of a workgroup (gfx950)
 constexpr int kLayMaxCw = 8;                    // codewords (= waves) per workgroup at most
 constexpr int kLayStateBytes = 12;              // per check and codeword: m1', m2', argmin position | sign bits
+constexpr int kLayWideStateBytes = 16;          // wide: m1', m2', 32 sign bits, the argmin position in its own word
+
+// A code (and every handle made for it) is WIDE when some check has a degree above kLayMaxD. A wide handle keeps
+// the sign bits of R in a whole 32-bit word and the argmin position in a word of its own, for every check of the
+// code, and runs the *_wide kernels; a narrow handle is what it always was. Precondition: a valid indptr.
+inline bool layered_is_wide(int32_t n_c, const int32_t* indptr) {
+  for (int32_t c = 0; c < n_c; ++c)
+    if (indptr[c + 1] - indptr[c] > kLayMaxD) return true;
+  return false;
+}
 
 // 0 = valid; -1 = malformed (EINVAL: cover, disjointness, shared variable, bad index), -2 = a check degree
-// outside [2, 16] (EUNSUPPORTED). *err names the first offending check.
+// outside [2, 32] (EUNSUPPORTED). *err names the first offending check.
 inline int validate_layers(int32_t n_v, int32_t n_c, const int32_t* indptr, const int32_t* cols, int32_t n_layers,
                            const int32_t* layer_ptr, const int32_t* layer_checks, std::string* err) {
   if (n_v <= 0 || n_c <= 0 || !indptr || !cols) return *err = "empty graph", -1;
@@ -72,20 +84,21 @@ inline int validate_layers(int32_t n_v, int32_t n_c, const int32_t* indptr, cons
     if (layer_of[c] < 0) return *err = "check " + std::to_string(c) + " is in no layer", -1;
   for (int32_t c = 0; c < n_c; ++c) {
     const int32_t d = indptr[c + 1] - indptr[c];
-    if (d < kLayMinD || d > kLayMaxD)
+    if (d < kLayMinD || d > kLayWideMaxD)
       return *err = "check " + std::to_string(c) + " has degree " + std::to_string(d) +
-                    ": layered decoding supports check degrees 2..16", -2;
+                    ": layered decoding supports check degrees 2..32", -2;
   }
   return 0;
 }
 
-// LDS bytes one codeword occupies: its APP LLRs P (fp32 per variable) and the compressed check state.
-inline size_t layered_cw_bytes(int32_t n_v, int32_t n_c) {
-  return (size_t)4 * (size_t)n_v + (size_t)kLayStateBytes * (size_t)n_c;
+// LDS bytes one codeword occupies: its APP LLRs P (fp32 per variable) and the compressed check state
+// (4 N + 12 n_c; wide: 4 N + 16 n_c).
+inline size_t layered_cw_bytes(int32_t n_v, int32_t n_c, bool wide = false) {
+  return (size_t)4 * (size_t)n_v + (size_t)(wide ? kLayWideStateBytes : kLayStateBytes) * (size_t)n_c;
 }
 // Codewords a workgroup keeps on chip (one wave each): 0 = the code does not fit.
-inline int32_t layered_cw_per_group(int32_t n_v, int32_t n_c) {
-  const size_t per = layered_cw_bytes(n_v, n_c);
+inline int32_t layered_cw_per_group(int32_t n_v, int32_t n_c, bool wide = false) {
+  const size_t per = layered_cw_bytes(n_v, n_c, wide);
   return (int32_t)std::min<size_t>((size_t)kLayMaxCw, (size_t)kLayLds / per);
 }
 
@@ -96,6 +109,7 @@ struct LayeredPlan {
   std::vector<int32_t> layer_task; // n_layers + 1: first task of each layer
   int32_t n_tasks = 0, cw_per_group = 0;
   size_t cw_bytes = 0;
+  bool wide = false;               // some check has a degree above kLayMaxD: the wide state and fit rule
 };
 
 // Precondition: validate_layers(...) == 0.
@@ -127,13 +141,14 @@ inline void plan_layered(int32_t n_v, int32_t n_c, const int32_t* indptr, const 
   }
   pl->layer_task.push_back((int32_t)(pl->task.size() / 4));
   pl->n_tasks = (int32_t)(pl->task.size() / 4);
-  pl->cw_bytes = layered_cw_bytes(n_v, n_c);
-  pl->cw_per_group = layered_cw_per_group(n_v, n_c);
+  pl->wide = layered_is_wide(n_c, indptr);
+  pl->cw_bytes = layered_cw_bytes(n_v, n_c, pl->wide);
+  pl->cw_per_group = layered_cw_per_group(n_v, n_c, pl->wide);
 }
 
 // ---- per-layer path over HBM (codes of any length; checked by tests/asan/layered_pass_plan_check.cpp) --------
-// lane = codeword: P[n_v][ldb] and, per check, the three state rows M1 / M2 / PS [n_c][ldb], the checks in layer
-// order (slot = position in layer_checks). One launch per layer; a wave item is (check of the layer, tile of
+// lane = codeword: P[n_v][ldb] and, per check, the three state rows M1 / M2 / PS [n_c][ldb] (wide: a fourth, PO,
+// the argmin position, PS being all sign bits), the checks in layer order (slot = position in layer_checks). One launch per layer; a wave item is (check of the layer, tile of
 // kLayTile codewords), tile fastest, kLayPassWaves items per workgroup. The syndrome's item is (run of kLaySynRun
 // consecutive slots, tile) in its gather form; its packed form first packs the hard decisions into one 64-bit word
 // per (variable, tile), item (run of kLayTile variables, tile), then XORs them per check, item (run of kLayTile
@@ -159,13 +174,14 @@ inline int32_t pass_pack_runs(int32_t n) { return (int32_t)(((int64_t)n + kLayTi
 // byte sizes of the device scratch a per-layer handle of max_batch owns
 struct LayeredPassBytes {
   size_t P = 0;       // [n_v][ldb] fp32
-  size_t state = 0;   // each of M1, M2, PS: [n_c][ldb] 4-byte words
+  size_t state = 0;   // each of M1, M2, PS (wide: and PO): [n_c][ldb] 4-byte words
   size_t mask = 0;    // each of finished, unsatisfied: one 64-bit word per tile
   size_t counter = 0; // codewords still running
   size_t bits = 0;    // packed hard decisions: one 64-bit word per variable and tile
-  size_t total = 0;   // P + 3 state + 2 mask + counter + bits
+  size_t total = 0;   // P + 3 (wide: 4) state + 2 mask + counter + bits
 };
-inline LayeredPassBytes pass_bytes(int32_t n_v, int32_t n_c, int32_t max_batch) {
+constexpr int pass_state_arrays(bool wide) { return wide ? 4 : 3; }
+inline LayeredPassBytes pass_bytes(int32_t n_v, int32_t n_c, int32_t max_batch, bool wide = false) {
   LayeredPassBytes b;
   const size_t ldb = (size_t)pass_ldb(max_batch);
   b.P = (size_t)4 * (size_t)n_v * ldb;
@@ -173,7 +189,7 @@ inline LayeredPassBytes pass_bytes(int32_t n_v, int32_t n_c, int32_t max_batch) 
   b.mask = (size_t)8 * (size_t)pass_tiles(max_batch);
   b.counter = 4;
   b.bits = (size_t)8 * (size_t)n_v * (size_t)pass_tiles(max_batch);
-  b.total = b.P + 3 * b.state + 2 * b.mask + b.counter + b.bits;
+  b.total = b.P + (size_t)pass_state_arrays(wide) * b.state + 2 * b.mask + b.counter + b.bits;
   return b;
 }
 
@@ -248,8 +264,10 @@ inline LayeredCompactBytes pass_compact_bytes(int32_t max_batch) {
   b.total = b.orig + b.dest + b.ctl;
   return b;
 }
-// wave items of the row move: the n_v rows of P and the n_c rows of each of M1, M2, PS
-inline int64_t pass_compact_rows(int32_t n_v, int32_t n_c) { return (int64_t)n_v + 3 * (int64_t)n_c; }
+// wave items of the row move: the n_v rows of P and the n_c rows of each of M1, M2, PS (wide: and PO)
+inline int64_t pass_compact_rows(int32_t n_v, int32_t n_c, bool wide = false) {
+  return (int64_t)n_v + pass_state_arrays(wide) * (int64_t)n_c;
+}
 
 // ---- fixed point, per-layer path (include/ibldpc.h "Layered min-sum, fixed point"; checked by
 // tests/asan/layered_fixed_plan_check.cpp) ------------------------------------------------------------------------
@@ -271,17 +289,17 @@ inline int64_t fix_grid(int32_t n_checks, int32_t B) { return pass_grid(n_checks
 
 struct LayeredFixBytes {
   size_t P = 0;       // [n_v][ldb] int8
-  size_t state = 0;   // [n_c][ldb] 32-bit words
+  size_t state = 0;   // [n_c][ldb] 32-bit words; wide: two such arrays, one after the other
   size_t mask = 0;    // each of finished, unsatisfied
   size_t counter = 0;
   size_t bits = 0;    // one 64-bit word per variable and tile of kLayTile
   size_t total = 0;   // P + state + 2 mask + counter + bits
 };
-inline LayeredFixBytes fix_bytes(int32_t n_v, int32_t n_c, int32_t max_batch) {
+inline LayeredFixBytes fix_bytes(int32_t n_v, int32_t n_c, int32_t max_batch, bool wide = false) {
   LayeredFixBytes b;
   const size_t ldb = (size_t)fix_ldb(max_batch);
   b.P = (size_t)n_v * ldb;
-  b.state = (size_t)4 * (size_t)n_c * ldb;
+  b.state = (size_t)(wide ? 8 : 4) * (size_t)n_c * ldb;
   b.mask = (size_t)8 * (size_t)fix_mask_words(max_batch);
   b.counter = 4;
   b.bits = (size_t)8 * (size_t)n_v * (size_t)pass_tiles(max_batch);
@@ -297,5 +315,19 @@ constexpr bool fix_params_ok(int32_t alpha16, int32_t beta_q, int32_t q_max) {
 constexpr uint32_t fix_state_word(uint32_t m1, uint32_t m2, uint32_t pos, uint32_t signs) {
   return (m2 << 26) | (m1 << 20) | (pos << 16) | signs;
 }
+// The two state words of a check of a wide handle (degrees up to kLayWideMaxD), in the arrays S0 and S1 [n_c][ldb]:
+//   word 0 = corrected m2 << 11 | corrected m1 << 5 | first argmin position (5 bits);
+//   word 1 = the sign bits of R, edge k at bit k (all 32 bits at degree 32).
+struct FixWideWords {
+  uint32_t w0, w1;
+};
+constexpr FixWideWords fix_state_words_wide(uint32_t m1, uint32_t m2, uint32_t pos, uint32_t signs) {
+  return FixWideWords{(m2 << 11) | (m1 << 5) | pos, signs};
+}
+constexpr uint32_t fix_wide_m1(uint32_t w0) { return (w0 >> 5) & 63u; }
+constexpr uint32_t fix_wide_m2(uint32_t w0) { return (w0 >> 11) & 63u; }
+constexpr uint32_t fix_wide_pos(uint32_t w0) { return w0 & 31u; }
+// the low D bits set, D in [1, 32] (1u << 32 is undefined)
+constexpr uint32_t fix_wide_mask(int D) { return 0xFFFFFFFFu >> (32 - D); }
 
 }  // namespace ibl

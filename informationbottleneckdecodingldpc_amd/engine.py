@@ -295,6 +295,10 @@ class LayeredDecoder:
     kernels over HBM for codes of any length (``codes.dvbs2_layers`` for DVB-S2; they own about 4 N + 12 n_c
     bytes per codeword of ``max_batch``); ``"auto"`` the fused kernel when the codeword fits, else the per-layer
     kernels. The outputs are the same on every path.
+    Check degrees 2..32: a code with a check of degree above 16 (DVB-S2 rates 4/5 to 9/10, 5G NR base graph 1)
+    makes a *wide* decoder (:attr:`wide`), which runs kernels of its own on either path and keeps four state words
+    per check instead of three (4 N + 16 n_c bytes per codeword, in LDS for the fused fit as in HBM). Every other
+    decoder is what it was.
     ``compact`` (per-layer kernels only): ``True`` or ``(every, min_free_pct)`` moves the running codewords together
     between iterations so that whole tiles of finished ones are skipped (``ibl_layered_set_compaction``; the policy
     is in include/ibldpc.h). Values and iteration counts do not change; ``out`` may be written before the decode's
@@ -365,6 +369,14 @@ class LayeredDecoder:
         return int(n.value), int(e.value)
 
     @property
+    def wide(self) -> bool:
+        """Whether the code has a check of degree above 16, so that decodes run the wide kernels and state layout
+        (``ibl_layered_is_wide``)."""
+        w = ctypes.c_int32()
+        _lib.check(_lib.load().ibl_layered_is_wide(self._h, ctypes.byref(w)), "ibl_layered_is_wide")
+        return bool(w.value)
+
+    @property
     def path_in_use(self) -> str:
         """``"fused"`` or ``"passes"``: the kernels decodes run (``ibl_layered_path_in_use``)."""
         f = ctypes.c_int32()
@@ -421,7 +433,9 @@ class LayeredFixedDecoder:
     ``max(((alpha16 * m + 8) >> 4) - beta_q, 0)``, float LLRs quantised as ``rint(llr * scale)``. It runs the
     per-layer kernels over HBM (``path`` ``"auto"`` or ``"passes"``; ``"fused"`` raises :class:`_lib.IBLError`,
     ``IBL_EUNSUPPORTED``: that kernel is not built) and owns about N + 4 n_c + N / 8 bytes per codeword of
-    ``max_batch``. ``decode`` takes and gives float32 or int8 tensors in any combination."""
+    ``max_batch``. ``decode`` takes and gives float32 or int8 tensors in any combination.
+    Check degrees 2..32: a code with a check of degree above 16 makes a *wide* decoder (:attr:`wide`) with two state
+    words per check and codeword, N + 8 n_c + N / 8 bytes per codeword."""
 
     _PATHS = LayeredDecoder._PATHS
     _DT = {torch.float32: _lib.IBL_F32, torch.int8: _lib.IBL_I8}
@@ -448,6 +462,7 @@ class LayeredFixedDecoder:
         self._h = h
 
     path_in_use = LayeredDecoder.path_in_use
+    wide = LayeredDecoder.wide
     geometry = LayeredDecoder.geometry
     __del__ = LayeredDecoder.__del__
 

@@ -18,6 +18,9 @@ and method names so the same drivers (``ber.run_ber``) take it. Keyword-only ext
   between iterations (:class:`.engine.LayeredDecoder`); same results. ``ValueError`` with ``fixed=True`` or
   ``path="fused"``.
 
+Check degrees 2..32: a code with a check of degree above 16 (DVB-S2 rates 4/5 to 9/10) gets the engine's wide
+kernels on every path and in either arithmetic, with nothing to ask for (:attr:`.engine.LayeredDecoder.wide`).
+
 fp32 only unless ``fixed``. The early stop is per codeword; ``last_iterations`` holds the int32 device tensor of the last
 decode's iteration counts.
 """
