@@ -104,27 +104,21 @@ int layered_decode_passes(ibl_layered* h, const float* d_llr, int32_t B, float* 
   c.orig = h->orig; c.dest = h->dest; c.ctl = h->ctl; c.out = d_out; c.min_free_pct = h->compact_pct;
   h->last_B = B;
   h->last_compact = every > 0;
-  // a wide handle: the same chain, the stage-in, the layers and the row move in their wide forms
-  const bool wide = h->wide != 0;
-  if (wide) HIPCHK(launch_lay_stage_in_wide(a, every ? &c : nullptr, h->PO, d_llr, h->imax, s));
-  else if (every) HIPCHK(launch_lay_stage_in_c(a, c, d_llr, h->imax, s));
-  else HIPCHK(launch_lay_stage_in(a, d_llr, h->imax, s));
+  // h->PO is allocated on a wide handle only: with it the stage-in, the layers and the row move run in their wide
+  // forms, in the same chain
+  HIPCHK(launch_lay_stage_in(a, every ? &c : nullptr, h->PO, d_llr, h->imax, s));
   const int32_t n_layers = (int32_t)h->layer_slot.size() - 1;
   for (int32_t it = 1; it <= h->imax; ++it) {
     for (int32_t l = 0; l < n_layers; ++l) {
       const int32_t s0 = h->layer_slot[l], n = h->layer_slot[l + 1] - s0;
-      if (wide) HIPCHK(launch_lay_layer_wide(a, h->PO, s0, n, s));
-      else HIPCHK(launch_lay_layer(a, s0, n, s));
+      HIPCHK(launch_lay_layer(a, h->PO, s0, n, s));
     }
     if (early_stop && it < h->imax) {
       HIPCHK(launch_lay_syndrome(a, h->syn_packed, s));
       if (every) HIPCHK(launch_lay_finalise_c(a, c, it, s));
       else HIPCHK(launch_lay_finalise(a, it, s));
       // the device decides whether the attempt moves anything (layered_plan.h compact_wanted)
-      if (every && it % every == 0) {
-        if (wide) HIPCHK(launch_lay_compact_wide(a, c, h->PO, s));
-        else HIPCHK(launch_lay_compact(a, c, s));
-      }
+      if (every && it % every == 0) HIPCHK(launch_lay_compact(a, c, h->PO, s));
     }
   }
   if (every) HIPCHK(launch_lay_stage_out_c(a, c, s));
@@ -140,15 +134,13 @@ int layered_run_fixed(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int3
   a.rec = h->rec; a.cols = g->csr_cols; a.iters = d_iters;
   a.alpha16 = h->alpha16; a.beta_q = h->beta_q; a.q_max = h->q_max; a.scale = h->scale;
   a.n_v = g->n_v; a.n_c = g->n_c; a.B = B; a.ntiles = pass_tiles(B); a.ntiles4 = fix_tiles(B);
-  const bool wide = h->wide != 0;
-  if (wide) HIPCHK(launch_layfix_stage_in_wide(a, h->S1, d_llr, llr_dtype, h->imax, s));
-  else HIPCHK(launch_layfix_stage_in(a, d_llr, llr_dtype, h->imax, s));
+  // h->S1 is allocated on a wide handle only
+  HIPCHK(launch_layfix_stage_in(a, h->S1, d_llr, llr_dtype, h->imax, s));
   const int32_t n_layers = (int32_t)h->layer_slot.size() - 1;
   for (int32_t it = 1; it <= h->imax; ++it) {
     for (int32_t l = 0; l < n_layers; ++l) {
       const int32_t s0 = h->layer_slot[l], n = h->layer_slot[l + 1] - s0;
-      if (wide) HIPCHK(launch_layfix_layer_wide(a, h->S1, s0, n, s));
-      else HIPCHK(launch_layfix_layer(a, s0, n, s));
+      HIPCHK(launch_layfix_layer(a, h->S1, s0, n, s));
     }
     if (early_stop && it < h->imax) HIPCHK(launch_layfix_stop(a, it, s));
   }
@@ -209,8 +201,7 @@ int ibl_layered_create_path(const ibl_graph* g, int32_t n_layers, const int32_t*
   int bpc = 0;
   size_t priv = 0;
   const size_t lds = (size_t)h->cw_per_group * h->cw_bytes;
-  const hipError_t e = wide ? lay_fused_wide_occupancy(h->cw_per_group, lds, &bpc, &priv)
-                            : lay_fused_occupancy(h->cw_per_group, lds, &bpc, &priv);
+  const hipError_t e = lay_fused_occupancy(wide, h->cw_per_group, lds, &bpc, &priv);
   if (e != hipSuccess) return fail(IBL_EHIP, std::string("layered kernel occupancy: ") + hipGetErrorString(e));
   if (bpc < 1) return fail(IBL_EHIP, "no occupancy for the layered kernel");
   // same guard as the other fused kernels: built to run without scratch
@@ -386,8 +377,7 @@ int ibl_layered_decode(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int
     a.trace = tr.d;
   }
 #endif
-  if (h->wide) HIPCHK(launch_lay_fused_wide(a, grid, (size_t)h->cw_per_group * h->cw_bytes, s));
-  else HIPCHK(launch_lay_fused(a, grid, (size_t)h->cw_per_group * h->cw_bytes, s));
+  HIPCHK(launch_lay_fused(a, h->wide != 0, grid, (size_t)h->cw_per_group * h->cw_bytes, s));
 #if IBL_DIAG
   if (ltrace && (rc = tr.save(s, ltrace, 0, tr.n))) return rc;
 #endif

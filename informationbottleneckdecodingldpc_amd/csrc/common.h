@@ -364,13 +364,19 @@ struct LayeredArgs {
   int32_t n_v, n_c, n_tasks, B, imax, early, ngroups, cw_per_group, cw_bytes;
   uint64_t* trace;          // diagnostics (IBL_TRACE_LAYERED, -DIBL_LAY_TRACE=1 builds): 3 clocks per task, else nullptr
 };
-hipError_t lay_fused_occupancy(int cw_per_group, size_t lds, int* blocks_per_cu, size_t* private_bytes);
-hipError_t launch_lay_fused(const LayeredArgs& a, int grid, size_t lds, hipStream_t s);
+// wide: lay_fused_wide, whose PO follows PS in the wave's LDS slice (cw_bytes = 4 N + 16 n_c)
+hipError_t lay_fused_occupancy(bool wide, int cw_per_group, size_t lds, int* blocks_per_cu, size_t* private_bytes);
+hipError_t launch_lay_fused(const LayeredArgs& a, bool wide, int grid, size_t lds, hipStream_t s);
 // dst[c][r] = src[r][c], fp32
 hipError_t launch_lay_transpose(const float* src, float* dst, int rows, int cols, hipStream_t s);
 
 // Per-layer path over HBM (long codes): lane = codeword, rows [row][ldb], ldb = ntiles * 64 (layered_plan.h
 // "per-layer path"). Every launcher only enqueues on `s`.
+// Wide handles (a check of degree 17..32; layered_plan.h layered_is_wide): the kernels that touch the check state
+// have wide forms, which take the added state array as an argument of their own — PO [n_c][ldb], the fp32 argmin
+// positions (PS is then all sign bits), or S1 [n_c][ldb], the fixed-point sign words (S is then word 0 of
+// fix_state_words_wide) — so the argument structs stay as they are. A launcher with a PO / S1 parameter launches the
+// wide kernel when it is given and the narrow one for nullptr; every other launcher serves both.
 struct LayPassArgs {
   float* P;                 // [n_v][ldb] APP LLRs
   float* M1;                // [n_c][ldb] corrected m1 per slot (checks in layer order)
@@ -386,8 +392,7 @@ struct LayPassArgs {
   float alpha, beta, llr_max;
   int32_t n_v, n_c, B, ntiles;
 };
-hipError_t launch_lay_stage_in(const LayPassArgs& a, const float* llr, int imax, hipStream_t s);
-hipError_t launch_lay_layer(const LayPassArgs& a, int slot0, int n_checks, hipStream_t s);
+hipError_t launch_lay_layer(const LayPassArgs& a, uint32_t* PO, int slot0, int n_checks, hipStream_t s);
 // packed = 0: gather form, one launch; 1: pack the hard decisions, then XOR the packed words per check (two)
 hipError_t launch_lay_syndrome(const LayPassArgs& a, int packed, hipStream_t s);
 hipError_t launch_lay_finalise(const LayPassArgs& a, int it, hipStream_t s);
@@ -403,12 +408,14 @@ struct LayCompactArgs {
   float* out;               // the caller's [n_v][B] output: finished codewords are delivered when they are dropped
   int32_t min_free_pct;
 };
-// the _c launchers are lay_stage_in / lay_finalise / lay_stage_out through `orig` and the extent
-hipError_t launch_lay_stage_in_c(const LayPassArgs& a, const LayCompactArgs& c, const float* llr, int imax, hipStream_t s);
+// c: nullptr without compaction (lay_stage_in, else lay_stage_in_c)
+hipError_t launch_lay_stage_in(const LayPassArgs& a, const LayCompactArgs* c, uint32_t* PO, const float* llr,
+                               int imax, hipStream_t s);
+// the _c launchers are lay_finalise / lay_stage_out through `orig` and the extent
 hipError_t launch_lay_finalise_c(const LayPassArgs& a, const LayCompactArgs& c, int it, hipStream_t s);
 hipError_t launch_lay_stage_out_c(const LayPassArgs& a, const LayCompactArgs& c, hipStream_t s);
 // one attempt: plan (decides on the device), row move, commit — three launches, the last two leave when `do` is 0
-hipError_t launch_lay_compact(const LayPassArgs& a, const LayCompactArgs& c, hipStream_t s);
+hipError_t launch_lay_compact(const LayPassArgs& a, const LayCompactArgs& c, uint32_t* PO, hipStream_t s);
 hipError_t lay_compact_private_bytes(size_t* bytes);
 
 // Fixed-point per-layer path (include/ibldpc.h "Layered min-sum, fixed point"): a lane owns 4 consecutive
@@ -430,28 +437,14 @@ struct LayFixArgs {
   int32_t n_v, n_c, B, ntiles, ntiles4;   // tiles of 64 (masks, bits) and of 256 (rows) codewords of B
 };
 // llr / out: [N][B] of dtype kF32 (quantised on the way in, divided by scale on the way out) or kI8
-hipError_t launch_layfix_stage_in(const LayFixArgs& a, const void* llr, int32_t dtype, int imax, hipStream_t s);
-hipError_t launch_layfix_layer(const LayFixArgs& a, int slot0, int n_checks, hipStream_t s);
+hipError_t launch_layfix_stage_in(const LayFixArgs& a, uint32_t* S1, const void* llr, int32_t dtype, int imax,
+                                  hipStream_t s);
+hipError_t launch_layfix_layer(const LayFixArgs& a, uint32_t* S1, int slot0, int n_checks, hipStream_t s);
 // pack the hard decisions of the int8 rows, XOR the packed words per check, finish the satisfied codewords (three)
 hipError_t launch_layfix_stop(const LayFixArgs& a, int it, hipStream_t s);
 hipError_t launch_layfix_stage_out(const LayFixArgs& a, void* out, int32_t dtype, hipStream_t s);
 hipError_t layfix_private_bytes(size_t* bytes);
-
-// Wide handles (a check of degree 17..32; layered_plan.h layered_is_wide): the kernels that touch the check state
-// have wide forms, which take the added state array as an argument of their own — PO [n_c][ldb], the fp32 argmin
-// positions (PS is then all sign bits), or S1 [n_c][ldb], the fixed-point sign words (S is then word 0 of
-// fix_state_words_wide) — so the argument structs and every narrow launch stay as they are. The fused kernel's PO
-// follows PS in the wave's LDS slice (cw_bytes = 4 N + 16 n_c). Every other launcher above serves both.
-hipError_t lay_fused_wide_occupancy(int cw_per_group, size_t lds, int* blocks_per_cu, size_t* private_bytes);
-hipError_t launch_lay_fused_wide(const LayeredArgs& a, int grid, size_t lds, hipStream_t s);
-// c: nullptr without compaction
-hipError_t launch_lay_stage_in_wide(const LayPassArgs& a, const LayCompactArgs* c, uint32_t* PO, const float* llr,
-                                    int imax, hipStream_t s);
-hipError_t launch_lay_layer_wide(const LayPassArgs& a, uint32_t* PO, int slot0, int n_checks, hipStream_t s);
-hipError_t launch_lay_compact_wide(const LayPassArgs& a, const LayCompactArgs& c, uint32_t* PO, hipStream_t s);
-hipError_t launch_layfix_stage_in_wide(const LayFixArgs& a, uint32_t* S1, const void* llr, int32_t dtype, int imax,
-                                       hipStream_t s);
-hipError_t launch_layfix_layer_wide(const LayFixArgs& a, uint32_t* S1, int slot0, int n_checks, hipStream_t s);
+// over the kernels only a wide handle launches, fp32 and fixed point
 hipError_t lay_wide_private_bytes(size_t* bytes);
 
 }  // namespace ibl

@@ -47,21 +47,87 @@ __device__ __forceinline__ float lay_signed(float mag, uint32_t sign) {
   return __builtin_bit_cast(float, lay_bits(mag) | (sign & 0x80000000u));
 }
 
-// One task of checks of degree D: lane < cnt owns check `slot`; v-index rows at idx + 64 k.
-// The kernel is bound by vector-ALU issue (two waves a SIMD), so the body is written for few instructions
-// per edge; every step keeps the VALUES of the specification:
+// Narrow and wide handles (include/ibldpc.h "Layered min-sum", wide handles; layered_plan.h layered_is_wide). A handle
+// whose code has a check of degree above kLayMaxD = 16 is wide and runs lay_fused_wide, lay_layer_wide and
+// layfix_layer_wide instead of lay_fused, lay_layer and layfix_layer, for EVERY check of the code: kernels of their
+// own, because the degree bodies of one kernel share one register allocation and unrolled degree-32 bodies inside
+// lay_layer would cost the narrow codes their occupancy. The arithmetic is written once for both (lay_minsum,
+// layfix_minsum); what differs is where the state lives:
+//   fp32        narrow: one word PS, argmin position << 16 | sign bits of R. Wide: the sign bits fill PS (edge k at
+//               bit D - 1 - k in both) and the position has a word of its own, PO: four 4-byte words per check and
+//               codeword;
+//   fixed point narrow: one word S (layered_plan.h fix_state_word). Wide: two words in two arrays S / S1 [n_c][ldb]
+//               (fix_state_words_wide): m2' << 11 | m1' << 5 | position, and the sign bits of R, edge k at bit k.
+// The wide form of a kernel takes the added array as an argument of its own. Syndrome, pack, finalise, stage-out,
+// the compaction plan and commit serve both as they stand.
+//
+// The degrees with an unrolled body: 2..kLayMaxD on a narrow handle, 2..kLayWideMaxD on a wide one. Every kernel
+// that switches on a check's degree defines LAY_CASE(D) around one of the two lists.
+#define LAY_CASES_16                                                                                           \
+  LAY_CASE(2) LAY_CASE(3) LAY_CASE(4) LAY_CASE(5) LAY_CASE(6) LAY_CASE(7) LAY_CASE(8) LAY_CASE(9) LAY_CASE(10) \
+  LAY_CASE(11) LAY_CASE(12) LAY_CASE(13) LAY_CASE(14) LAY_CASE(15) LAY_CASE(16)
+#define LAY_CASES_32                                                                                             \
+  LAY_CASES_16 LAY_CASE(17) LAY_CASE(18) LAY_CASE(19) LAY_CASE(20) LAY_CASE(21) LAY_CASE(22) LAY_CASE(23)        \
+  LAY_CASE(24) LAY_CASE(25) LAY_CASE(26) LAY_CASE(27) LAY_CASE(28) LAY_CASE(29) LAY_CASE(30) LAY_CASE(31)        \
+  LAY_CASE(32)
+
+// The fp32 check update of one check of degree D, the one statement of it for every kernel: load(k) is P of edge k,
+// store(k, x) writes it back, and both are called inside the unrolled edge loops, so a caller's memory accesses sit
+// where the arithmetic uses them. In: the corrected minima m1s, m2s, the first argmin position pos and the sign bits
+// of R of the previous iteration (edge k at bit D - 1 - k of `signs`; higher bits are ignored); out: those of this one
+// (`signs` then holds nothing else). Where the four words live is the caller's business.
+// The kernels are bound by vector-ALU issue (two waves a SIMD on the fused one), so the body is written for few
+// instructions per edge; every step keeps the VALUES of the specification:
 //   - clamp = median(x, -L, +L) (x is finite);
-//   - no P, R or Q is ever -0 (lay_fused loads the channel values as x + 0; P - R is -0 only for P = -0,
+//   - no P, R or Q is ever -0 (the stage-in loads the channel values as x + 0; P - R is -0 only for P = -0,
 //     Q + R only for Q = R = -0, and a magnitude max(., 0) is +0), so the sign bit of Q IS (Q < 0): the check's
 //     parity is the XOR of the Q words' sign bits, and the sign of R[e] the sign bit of (that XOR ^ Q_e);
 //   - m2 = median(m1, m2, a) before m1 = min(m1, a): the running two smallest; the position moves only on
 //     a < m1, so it is the FIRST position attaining the minimum;
-//   - state word: argmin position << 16 | sign bits of R, edge k at bit D - 1 - k (shifted in one edge at a
-//     time by v_alignbit_b32).
-template <int D>
+//   - the sign bits of R are shifted in one edge at a time by v_alignbit_b32.
+template <int D, class Load, class Store>
+__device__ __forceinline__ void lay_minsum(Load load, Store store, float& m1s, float& m2s, uint32_t& pos,
+                                           uint32_t& signs, float alpha, float beta, float L) {
+  static_assert(D >= kLayMinD && D <= kLayWideMaxD, "degree body out of range");
+  const float m1o = m1s, m2o = m2s;
+  const uint32_t poso = pos, ps = signs;
+  float q[D];
+  float m1 = __builtin_inff(), m2 = __builtin_inff();
+  uint32_t at = 0, sx = 0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    const float r = lay_signed((uint32_t)k == poso ? m2o : m1o, ps << (32 - D + k));
+    const float x = __builtin_amdgcn_fmed3f(load(k) - r, -L, L);
+    q[k] = x;
+    sx ^= lay_bits(x);
+    const float a = fabsf(x);
+    at = a < m1 ? (uint32_t)k : at;
+    m2 = __builtin_amdgcn_fmed3f(m1, m2, a);
+    m1 = fminf(m1, a);
+  }
+  const float m1n = fmaxf(alpha * m1 - beta, 0.f), m2n = fmaxf(alpha * m2 - beta, 0.f);
+  uint32_t sg = 0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    const uint32_t t = sx ^ lay_bits(q[k]);   // sign bit: s ^ neg_e, R[e] is negated
+    store(k, q[k] + lay_signed((uint32_t)k == at ? m2n : m1n, t));
+    sg = __builtin_amdgcn_alignbit(sg, t, 31);   // (sg << 1) | (t >> 31)
+  }
+  m1s = m1n;
+  m2s = m2n;
+  pos = at;
+  signs = sg;
+}
+
+// One task of checks of degree D of the fused kernel: lane < cnt owns check `slot`; v-index rows at idx + 64 k.
+// Narrow state word PS: argmin position << 16 | sign bits of R (the core's shifts drop the position); wide: PS is
+// all sign bits and the position is PO[slot].
+template <int D, bool kWide>
 __device__ __forceinline__ void lay_cn(float* __restrict__ P, float* __restrict__ M1, float* __restrict__ M2,
-                                       uint32_t* __restrict__ PS, const int32_t* __restrict__ idx, int slot,
-                                       float alpha, float beta, float L, uint64_t* tr) {
+                                       uint32_t* __restrict__ PS, uint32_t* __restrict__ PO,
+                                       const int32_t* __restrict__ idx, int slot, float alpha, float beta, float L,
+                                       uint64_t* tr) {
+  static_assert(D <= (kWide ? kLayWideMaxD : kLayMaxD), "degree body out of range");
   int v[D];
 #pragma unroll
   for (int k = 0; k < D; ++k) v[k] = idx[64 * k];
@@ -71,50 +137,44 @@ __device__ __forceinline__ void lay_cn(float* __restrict__ P, float* __restrict_
     if ((threadIdx.x & 63u) == 0) tr[1] = t;
   }
 #endif
-  const float m1o = M1[slot], m2o = M2[slot];
-  const uint32_t ps = PS[slot];
-  const uint32_t poso = ps >> 16;
-  float q[D];
-  float m1 = __builtin_inff(), m2 = __builtin_inff();
-  uint32_t pos = 0, sx = 0;
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    const float r = lay_signed((uint32_t)k == poso ? m2o : m1o, ps << (32 - D + k));
-    const float x = __builtin_amdgcn_fmed3f(P[v[k]] - r, -L, L);
-    q[k] = x;
-    sx ^= lay_bits(x);
-    const float a = fabsf(x);
-    pos = a < m1 ? (uint32_t)k : pos;
-    m2 = __builtin_amdgcn_fmed3f(m1, m2, a);
-    m1 = fminf(m1, a);
+  float m1 = M1[slot], m2 = M2[slot];
+  uint32_t sg = PS[slot], pos;
+  if constexpr (kWide) pos = PO[slot];
+  else pos = sg >> 16;
+  lay_minsum<D>([&](int k) { return P[v[k]]; }, [&](int k, float x) { P[v[k]] = x; }, m1, m2, pos, sg, alpha, beta, L);
+  M1[slot] = m1;
+  M2[slot] = m2;
+  if constexpr (kWide) {
+    PS[slot] = sg;
+    PO[slot] = pos;
+  } else {
+    PS[slot] = (pos << 16) | sg;
   }
-  const float m1n = fmaxf(alpha * m1 - beta, 0.f), m2n = fmaxf(alpha * m2 - beta, 0.f);
-  uint32_t sg = 0;
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    const uint32_t t = sx ^ lay_bits(q[k]);   // sign bit: s ^ neg_e, R[e] is negated
-    P[v[k]] = q[k] + lay_signed((uint32_t)k == pos ? m2n : m1n, t);
-    sg = __builtin_amdgcn_alignbit(sg, t, 31);   // (sg << 1) | (t >> 31)
-  }
-  M1[slot] = m1n;
-  M2[slot] = m2n;
-  PS[slot] = (pos << 16) | sg;
 }
 
-__device__ __forceinline__ void lay_cn_any(int d, float* P, float* M1, float* M2, uint32_t* PS, const int32_t* idx,
-                                           int slot, float alpha, float beta, float L, uint64_t* tr) {
-  switch (d) {
-#define LAY_CASE(D) case D: lay_cn<D>(P, M1, M2, PS, idx, slot, alpha, beta, L, tr); break;
-    LAY_CASE(2) LAY_CASE(3) LAY_CASE(4) LAY_CASE(5) LAY_CASE(6) LAY_CASE(7) LAY_CASE(8) LAY_CASE(9)
-    LAY_CASE(10) LAY_CASE(11) LAY_CASE(12) LAY_CASE(13) LAY_CASE(14) LAY_CASE(15) LAY_CASE(16)
+template <bool kWide>
+__device__ __forceinline__ void lay_cn_any(int d, float* P, float* M1, float* M2, uint32_t* PS, uint32_t* PO,
+                                           const int32_t* idx, int slot, float alpha, float beta, float L,
+                                           uint64_t* tr) {
+#define LAY_CASE(D) case D: lay_cn<D, kWide>(P, M1, M2, PS, PO, idx, slot, alpha, beta, L, tr); break;
+  if constexpr (kWide) {
+    switch (d) {
+      LAY_CASES_32
+      default: break;
+    }
+  } else {
+    switch (d) {
+      LAY_CASES_16
+      default: break;
+    }
+  }
 #undef LAY_CASE
-    default: break;
-  }
 }
 
-}  // namespace
-
-__global__ __launch_bounds__(64 * kLayMaxCw) void lay_fused(const LayeredArgs a) {
+// The fused kernel. kWide: the wave's slice of LDS is P[n_v], M1, M2, PS, PO [n_c] (cw_bytes = 4 N + 16 n_c).
+// (the arguments by value, as the kernels have them: by reference the scalar code of the prologue changes)
+template <bool kWide>
+__device__ __forceinline__ void lay_fused_body(const LayeredArgs a) {
   extern __shared__ __align__(16) unsigned char lay_lds[];
   const int lane = (int)(threadIdx.x & 63u);
   const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -125,18 +185,20 @@ __global__ __launch_bounds__(64 * kLayMaxCw) void lay_fused(const LayeredArgs a)
   float* M1 = P + a.n_v;
   float* M2 = M1 + a.n_c;
   uint32_t* PS = reinterpret_cast<uint32_t*>(M2 + a.n_c);
+  uint32_t* PO = kWide ? PS + a.n_c : nullptr;
   const float alpha = a.alpha, beta = a.beta, L = a.llr_max;
   for (int g = (int)blockIdx.x; g < a.ngroups; g += (int)gridDim.x) {
     const int b = g * ncw + wave;
     if (b >= a.B) break;   // wave-uniform; later groups of this workgroup lie further still
     // + 0: a -0 channel value enters as +0 (equal as a value); no later step produces a -0 from inputs
-    // without one, which lay_cn's sign-bit arithmetic relies on
+    // without one, which lay_minsum's sign-bit arithmetic relies on
     float* row = a.buf + (size_t)b * (size_t)a.n_v;
     for (int v = lane; v < a.n_v; v += 64) P[v] = row[v] + 0.f;
     for (int c = lane; c < a.n_c; c += 64) {
       M1[c] = 0.f;
       M2[c] = 0.f;
       PS[c] = 0u;
+      if constexpr (kWide) PO[c] = 0u;
     }
     int it = 1;
     for (;; ++it) {
@@ -151,7 +213,8 @@ __global__ __launch_bounds__(64 * kLayMaxCw) void lay_fused(const LayeredArgs a)
           if (lane == 0) tr[0] = t0;
         }
 #endif
-        if (lane < cnt) lay_cn_any(d, P, M1, M2, PS, a.idx + first + lane, s0 + lane, alpha, beta, L, tr);
+        if (lane < cnt)
+          lay_cn_any<kWide>(d, P, M1, M2, PS, PO, a.idx + first + lane, s0 + lane, alpha, beta, L, tr);
         __builtin_amdgcn_wave_barrier();   // the next task's reads stay behind this task's writes (other lanes')
 #if IBL_LAY_TRACE
         if (tr) {
@@ -182,6 +245,11 @@ __global__ __launch_bounds__(64 * kLayMaxCw) void lay_fused(const LayeredArgs a)
   }
 }
 
+}  // namespace
+
+__global__ __launch_bounds__(64 * kLayMaxCw) void lay_fused(const LayeredArgs a) { lay_fused_body<false>(a); }
+__global__ __launch_bounds__(64 * kLayMaxCw) void lay_fused_wide(const LayeredArgs a) { lay_fused_body<true>(a); }
+
 // dst[c][r] = src[r][c] for r < rows, c < cols (fp32; 64 x 64 tiles through LDS, 256 threads)
 __global__ __launch_bounds__(256) void lay_transpose(const float* __restrict__ src, float* __restrict__ dst, int rows,
                                                      int cols) {
@@ -200,8 +268,8 @@ __global__ __launch_bounds__(256) void lay_transpose(const float* __restrict__ s
   }
 }
 
-hipError_t lay_fused_occupancy(int cw_per_group, size_t lds, int* blocks_per_cu, size_t* private_bytes) {
-  const void* f = (const void*)lay_fused;
+hipError_t lay_fused_occupancy(bool wide, int cw_per_group, size_t lds, int* blocks_per_cu, size_t* private_bytes) {
+  const void* f = wide ? (const void*)lay_fused_wide : (const void*)lay_fused;
   hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
   if (e != hipSuccess) return e;
   hipFuncAttributes fa;
@@ -210,14 +278,15 @@ hipError_t lay_fused_occupancy(int cw_per_group, size_t lds, int* blocks_per_cu,
   return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, f, 64 * cw_per_group, lds);
 }
 
-hipError_t launch_lay_fused(const LayeredArgs& a, int grid, size_t lds, hipStream_t s) {
+hipError_t launch_lay_fused(const LayeredArgs& a, bool wide, int grid, size_t lds, hipStream_t s) {
   if (!a.buf || !a.task || !a.idx || a.cw_per_group < 1 || a.cw_per_group > kLayMaxCw || a.n_tasks < 1 ||
       a.B < 1 || a.ngroups < 1 || grid < 1 || lds < (size_t)a.cw_per_group * (size_t)a.cw_bytes ||
-      lds > (size_t)kLdsBytes)
+      lds > (size_t)kLdsBytes || (wide && (size_t)a.cw_bytes < layered_cw_bytes(a.n_v, a.n_c, true)))
     return hipErrorInvalidValue;
   LayeredArgs args = a;
   void* p[] = {&args};
-  return hipLaunchKernel((const void*)lay_fused, dim3(grid), dim3(64 * a.cw_per_group), p, lds, s);
+  const void* f = wide ? (const void*)lay_fused_wide : (const void*)lay_fused;
+  return hipLaunchKernel(f, dim3(grid), dim3(64 * a.cw_per_group), p, lds, s);
 }
 
 hipError_t launch_lay_transpose(const float* src, float* dst, int rows, int cols, hipStream_t s) {
@@ -251,44 +320,46 @@ __device__ __forceinline__ uint64_t lay_mask(const uint64_t* m, int tile) {
   return (uint64_t)(uint32_t)sload(w, 2 * tile) | ((uint64_t)(uint32_t)sload(w, 2 * tile + 1) << 32);
 }
 
-// One check of degree D for the lane's codeword (column `col` of every row): the steps and values of lay_cn.
+// One check of degree D for the lane's codeword, narrow handle: column `col` of every row, a 64-bit element index
+// per edge; the state word as in lay_cn.
 template <int D>
 __device__ __forceinline__ void lay_cn_rows(const LayPassArgs& a, int e0, size_t srow, size_t col, size_t ldb) {
+  static_assert(D <= kLayMaxD, "degree body out of range");
   size_t v[D];
 #pragma unroll
   for (int k = 0; k < D; ++k) v[k] = (size_t)sload(a.cols, e0 + k) * ldb + col;
   float p[D];
 #pragma unroll
   for (int k = 0; k < D; ++k) p[k] = a.P[v[k]];
-  const float m1o = a.M1[srow], m2o = a.M2[srow];
-  const uint32_t ps = a.PS[srow];
-  const uint32_t poso = ps >> 16;
-  const float alpha = a.alpha, beta = a.beta, L = a.llr_max;
-  float q[D];
-  float m1 = __builtin_inff(), m2 = __builtin_inff();
-  uint32_t pos = 0, sx = 0;
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    const float r = lay_signed((uint32_t)k == poso ? m2o : m1o, ps << (32 - D + k));
-    const float x = __builtin_amdgcn_fmed3f(p[k] - r, -L, L);
-    q[k] = x;
-    sx ^= lay_bits(x);
-    const float m = fabsf(x);
-    pos = m < m1 ? (uint32_t)k : pos;
-    m2 = __builtin_amdgcn_fmed3f(m1, m2, m);
-    m1 = fminf(m1, m);
-  }
-  const float m1n = fmaxf(alpha * m1 - beta, 0.f), m2n = fmaxf(alpha * m2 - beta, 0.f);
-  uint32_t sg = 0;
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    const uint32_t t = sx ^ lay_bits(q[k]);
-    a.P[v[k]] = q[k] + lay_signed((uint32_t)k == pos ? m2n : m1n, t);
-    sg = __builtin_amdgcn_alignbit(sg, t, 31);
-  }
-  a.M1[srow] = m1n;
-  a.M2[srow] = m2n;
+  float m1 = a.M1[srow], m2 = a.M2[srow];
+  uint32_t sg = a.PS[srow], pos = sg >> 16;
+  lay_minsum<D>([&](int k) { return p[k]; }, [&](int k, float x) { a.P[v[k]] = x; }, m1, m2, pos, sg, a.alpha, a.beta,
+                a.llr_max);
+  a.M1[srow] = m1;
+  a.M2[srow] = m2;
   a.PS[srow] = (pos << 16) | sg;
+}
+
+// The same for a wide handle: the position in PO and all of PS sign bits. tcol: the tile's first column, srow: the
+// first state word of (slot, tile), both wave-uniform; the lane's codeword is element `lane` of each. A row is
+// addressed as a wave-uniform base (the variable index is a scalar load and the tile is the wave's) plus the lane,
+// formed again for the store, so a check's D rows cost scalar registers and one 32-bit vector offset, not D 64-bit
+// vector addresses.
+template <int D>
+__device__ __forceinline__ void lay_cn_rows_wide(const LayPassArgs& a, uint32_t* __restrict__ PO, int e0, size_t srow,
+                                                 size_t tcol, uint32_t lane, size_t ldb) {
+  const auto row = [&](int k) { return a.P + ((size_t)sload(a.cols, e0 + k) * ldb + tcol); };
+  float p[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) p[k] = row(k)[lane];
+  float m1 = (a.M1 + srow)[lane], m2 = (a.M2 + srow)[lane];
+  uint32_t sg = (a.PS + srow)[lane], pos = (PO + srow)[lane];
+  lay_minsum<D>([&](int k) { return p[k]; }, [&](int k, float x) { row(k)[lane] = x; }, m1, m2, pos, sg, a.alpha,
+                a.beta, a.llr_max);
+  (a.M1 + srow)[lane] = m1;
+  (a.M2 + srow)[lane] = m2;
+  (a.PS + srow)[lane] = sg;
+  (PO + srow)[lane] = pos;
 }
 
 }  // namespace
@@ -354,7 +425,8 @@ __global__ __launch_bounds__(64 * kLayPassWaves) void lay_stage_in_c_wide(const 
   lay_stage_in_body<true, true>(a, llr, imax, &c, PO);
 }
 
-// item = (check slot0 + c of the layer, tile), tile fastest
+// One layer: item = (check slot0 + c of the layer, tile), tile fastest. The two kernels differ in the degree list and
+// in how the body addresses a row; a wide handle runs lay_layer_wide for every check of its code.
 __global__ __launch_bounds__(64 * kLayPassWaves) void lay_layer(const LayPassArgs a, int slot0, int n_checks) {
   if (sload(a.running, 0) == 0) return;
   const int lane = (int)(threadIdx.x & 63u);
@@ -371,8 +443,29 @@ __global__ __launch_bounds__(64 * kLayPassWaves) void lay_layer(const LayPassArg
   const size_t srow = (size_t)slot * ldb + col;
   switch (d) {
 #define LAY_CASE(D) case D: lay_cn_rows<D>(a, e0, srow, col, ldb); break;
-    LAY_CASE(2) LAY_CASE(3) LAY_CASE(4) LAY_CASE(5) LAY_CASE(6) LAY_CASE(7) LAY_CASE(8) LAY_CASE(9)
-    LAY_CASE(10) LAY_CASE(11) LAY_CASE(12) LAY_CASE(13) LAY_CASE(14) LAY_CASE(15) LAY_CASE(16)
+    LAY_CASES_16
+#undef LAY_CASE
+    default: break;
+  }
+}
+__global__ __launch_bounds__(64 * kLayPassWaves) void lay_layer_wide(const LayPassArgs a, uint32_t* PO, int slot0,
+                                                                     int n_checks) {
+  if (sload(a.running, 0) == 0) return;
+  const int lane = (int)(threadIdx.x & 63u);
+  const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (item >= (int64_t)n_checks * a.ntiles) return;
+  const int tile = (int)(item % a.ntiles);
+  const int slot = slot0 + (int)(item / a.ntiles);
+  const uint64_t dm = lay_mask(a.done, tile);
+  if (dm == ~0ull) return;
+  if ((dm >> lane) & 1ull) return;
+  const int e0 = sload(a.rec, 2 * slot), d = sload(a.rec, 2 * slot + 1);
+  const size_t ldb = (size_t)a.ntiles * kLayTile;
+  const size_t tcol = (size_t)tile * kLayTile;
+  const size_t srow = (size_t)slot * ldb + tcol;
+  switch (d) {
+#define LAY_CASE(D) case D: lay_cn_rows_wide<D>(a, PO, e0, srow, tcol, (uint32_t)lane, ldb); break;
+    LAY_CASES_32
 #undef LAY_CASE
     default: break;
   }
@@ -670,22 +763,50 @@ hipError_t lay_pass_launch(const void* f, int64_t items, void** p, hipStream_t s
   if (grid < 1 || grid > 0x7fffffffll) return hipErrorInvalidValue;
   return hipLaunchKernel(f, dim3((unsigned)grid), dim3(64 * kLayPassWaves), p, 0, s);
 }
+bool lay_compact_args_ok(const LayCompactArgs& c) {
+  return c.orig && c.dest && c.ctl && c.out && c.min_free_pct >= 1 && c.min_free_pct <= 100;
+}
+// the largest private (scratch) segment over `kernels`
+hipError_t lay_private_bytes(std::initializer_list<const void*> kernels, size_t* bytes) {
+  *bytes = 0;
+  for (const void* f : kernels) {
+    hipFuncAttributes fa;
+    const hipError_t e = hipFuncGetAttributes(&fa, f);
+    if (e != hipSuccess) return e;
+    *bytes = std::max(*bytes, (size_t)fa.localSizeBytes);
+  }
+  return hipSuccess;
+}
 }  // namespace
 
-hipError_t launch_lay_stage_in(const LayPassArgs& a, const float* llr, int imax, hipStream_t s) {
-  if (!lay_pass_args_ok(a) || !llr) return hipErrorInvalidValue;
+// The launchers that touch the check state take the wide handle's added array (PO here, S1 in fixed point) and
+// launch the wide kernel when it is there; nullptr is a narrow handle. The kernels receive it after the structs.
+hipError_t launch_lay_stage_in(const LayPassArgs& a, const LayCompactArgs* c, uint32_t* PO, const float* llr,
+                               int imax, hipStream_t s) {
+  if (!lay_pass_args_ok(a) || !llr || (c && !lay_compact_args_ok(*c))) return hipErrorInvalidValue;
   LayPassArgs args = a;
-  void* p[] = {&args, (void*)&llr, (void*)&imax};
-  return lay_pass_launch((const void*)lay_stage_in, (int64_t)std::max(a.n_v, a.n_c) * a.ntiles, p, s);
+  LayCompactArgs ca = c ? *c : LayCompactArgs{};
+  void* p[5];
+  int n = 0;
+  p[n++] = &args;
+  if (c) p[n++] = &ca;
+  if (PO) p[n++] = (void*)&PO;
+  p[n++] = (void*)&llr;
+  p[n++] = (void*)&imax;
+  const void* f = c ? (PO ? (const void*)lay_stage_in_c_wide : (const void*)lay_stage_in_c)
+                    : (PO ? (const void*)lay_stage_in_wide : (const void*)lay_stage_in);
+  return lay_pass_launch(f, (int64_t)std::max(a.n_v, a.n_c) * a.ntiles, p, s);
 }
 
-hipError_t launch_lay_layer(const LayPassArgs& a, int slot0, int n_checks, hipStream_t s) {
+hipError_t launch_lay_layer(const LayPassArgs& a, uint32_t* PO, int slot0, int n_checks, hipStream_t s) {
   if (!lay_pass_args_ok(a) || slot0 < 0 || n_checks < 0 || (int64_t)slot0 + n_checks > a.n_c)
     return hipErrorInvalidValue;
   if (n_checks == 0) return hipSuccess;
   LayPassArgs args = a;
-  void* p[] = {&args, (void*)&slot0, (void*)&n_checks};
-  return lay_pass_launch((const void*)lay_layer, pass_items(n_checks, a.B), p, s);
+  void* pn[] = {&args, (void*)&slot0, (void*)&n_checks};
+  void* pw[] = {&args, (void*)&PO, (void*)&slot0, (void*)&n_checks};
+  return lay_pass_launch(PO ? (const void*)lay_layer_wide : (const void*)lay_layer, pass_items(n_checks, a.B),
+                         PO ? pw : pn, s);
 }
 
 hipError_t launch_lay_syndrome(const LayPassArgs& a, int packed, hipStream_t s) {
@@ -712,21 +833,6 @@ hipError_t launch_lay_stage_out(const LayPassArgs& a, float* out, hipStream_t s)
   return lay_pass_launch((const void*)lay_stage_out, (int64_t)a.n_v * a.ntiles, p, s);
 }
 
-namespace {
-bool lay_compact_args_ok(const LayCompactArgs& c) {
-  return c.orig && c.dest && c.ctl && c.out && c.min_free_pct >= 1 && c.min_free_pct <= 100;
-}
-}  // namespace
-
-hipError_t launch_lay_stage_in_c(const LayPassArgs& a, const LayCompactArgs& c, const float* llr, int imax,
-                                 hipStream_t s) {
-  if (!lay_pass_args_ok(a) || !lay_compact_args_ok(c) || !llr) return hipErrorInvalidValue;
-  LayPassArgs args = a;
-  LayCompactArgs ca = c;
-  void* p[] = {&args, &ca, (void*)&llr, (void*)&imax};
-  return lay_pass_launch((const void*)lay_stage_in_c, (int64_t)std::max(a.n_v, a.n_c) * a.ntiles, p, s);
-}
-
 hipError_t launch_lay_finalise_c(const LayPassArgs& a, const LayCompactArgs& c, int it, hipStream_t s) {
   if (!lay_pass_args_ok(a) || !lay_compact_args_ok(c)) return hipErrorInvalidValue;
   LayPassArgs args = a;
@@ -743,41 +849,31 @@ hipError_t launch_lay_stage_out_c(const LayPassArgs& a, const LayCompactArgs& c,
   return lay_pass_launch((const void*)lay_stage_out_c, (int64_t)a.n_v * a.ntiles, p, s);
 }
 
-hipError_t launch_lay_compact(const LayPassArgs& a, const LayCompactArgs& c, hipStream_t s) {
+// PO: the row move then covers the four state arrays
+hipError_t launch_lay_compact(const LayPassArgs& a, const LayCompactArgs& c, uint32_t* PO, hipStream_t s) {
   if (!lay_pass_args_ok(a) || !lay_compact_args_ok(c)) return hipErrorInvalidValue;
   LayPassArgs args = a;
   LayCompactArgs ca = c;
-  void* p[] = {&args, &ca};
+  void* p[] = {&args, &ca, (void*)&PO};   // the narrow kernels take the first two
   hipError_t e = hipLaunchKernel((const void*)lay_compact_plan, dim3(1), dim3(64 * kLayPassWaves), p, 0, s);
   if (e != hipSuccess) return e;
-  if ((e = lay_pass_launch((const void*)lay_compact_rows, pass_compact_rows(a.n_v, a.n_c), p, s)) != hipSuccess) return e;
+  const void* rows = PO ? (const void*)lay_compact_rows_wide : (const void*)lay_compact_rows;
+  if ((e = lay_pass_launch(rows, pass_compact_rows(a.n_v, a.n_c, PO != nullptr), p, s)) != hipSuccess) return e;
   return hipLaunchKernel((const void*)lay_compact_commit, dim3(1), dim3(64 * kLayPassWaves), p, 0, s);
 }
 
+// The create-time guards: every kernel here is built to run without a private (scratch) segment.
 hipError_t lay_compact_private_bytes(size_t* bytes) {
-  *bytes = 0;
-  for (const void* f : {(const void*)lay_stage_in_c, (const void*)lay_finalise_c, (const void*)lay_stage_out_c,
-                        (const void*)lay_compact_plan, (const void*)lay_compact_rows, (const void*)lay_compact_commit}) {
-    hipFuncAttributes fa;
-    const hipError_t e = hipFuncGetAttributes(&fa, f);
-    if (e != hipSuccess) return e;
-    *bytes = std::max(*bytes, (size_t)fa.localSizeBytes);
-  }
-  return hipSuccess;
+  return lay_private_bytes({(const void*)lay_stage_in_c, (const void*)lay_finalise_c, (const void*)lay_stage_out_c,
+                            (const void*)lay_compact_plan, (const void*)lay_compact_rows,
+                            (const void*)lay_compact_commit},
+                           bytes);
 }
-
-// the largest private (scratch) segment over the per-layer kernels: built to run without one
 hipError_t lay_pass_private_bytes(size_t* bytes) {
-  *bytes = 0;
-  for (const void* f : {(const void*)lay_stage_in, (const void*)lay_layer, (const void*)lay_syndrome,
-                        (const void*)lay_pack, (const void*)lay_syndrome_packed, (const void*)lay_finalise,
-                        (const void*)lay_stage_out}) {
-    hipFuncAttributes fa;
-    const hipError_t e = hipFuncGetAttributes(&fa, f);
-    if (e != hipSuccess) return e;
-    *bytes = std::max(*bytes, (size_t)fa.localSizeBytes);
-  }
-  return hipSuccess;
+  return lay_private_bytes({(const void*)lay_stage_in, (const void*)lay_layer, (const void*)lay_syndrome,
+                            (const void*)lay_pack, (const void*)lay_syndrome_packed, (const void*)lay_finalise,
+                            (const void*)lay_stage_out},
+                           bytes);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -809,10 +905,57 @@ __device__ __forceinline__ uint32_t layfix_finished(const uint64_t* done, int ti
   return (uint32_t)(dm >> ((lane & 15) * 4)) & 0xFu;
 }
 
-// One check of degree D for the lane's 4 codewords (bytes at `col` of every P row, words at srow of S).
+// The fixed-point check update of one check of degree D and ONE codeword, the one statement of it for both layer
+// kernels: codeword j of the lane's four, whose APP values are byte j of the row dwords p[D]. Both kernels load the
+// rows into registers first and store them after the fourth codeword, so the core takes them as they are: there is no
+// memory access to place, as lay_minsum's callables do. In: the corrected minima m1s, m2s
+// (6 bits), the first argmin position and the sign bits of R of the previous iteration, edge k at bit k of `signs`
+// (higher bits are ignored); out: those of this one. Plain integer C++ (include/ibldpc.h "Layered min-sum, fixed
+// point"): messages saturate at q_max, the correction is (alpha16 m + 8) >> 4 less beta_q, floored at 0; the
+// position moves only on m < m1, so it is the FIRST position attaining the minimum; P saturates at 127.
+template <int D>
+__device__ __forceinline__ void layfix_minsum(uint32_t (&p)[D], int j, int& m1s, int& m2s, uint32_t& pos,
+                                              uint32_t& signs, int alpha16, int beta, int qm) {
+  static_assert(D >= kLayMinD && D <= kLayWideMaxD, "degree body out of range");
+  const int m1o = m1s, m2o = m2s;
+  const uint32_t poso = pos, so = signs;
+  int t[D];
+  int m1 = kLayFixQMax + 1, m2 = kLayFixQMax + 1;
+  uint32_t at = 0, neg = 0;
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    const int mag = (uint32_t)k == poso ? m2o : m1o;
+    const int r = ((so >> k) & 1u) ? -mag : mag;
+    const int x = (int)(int8_t)(p[k] >> (8 * j)) - r;
+    t[k] = x;
+    neg |= ((uint32_t)x >> 31) << k;
+    const int m = min(abs(x), qm);
+    at = m < m1 ? (uint32_t)k : at;
+    m2 = min(m2, max(m1, m));
+    m1 = min(m1, m);
+  }
+  const int m1n = max(((alpha16 * m1 + 8) >> 4) - beta, 0), m2n = max(((alpha16 * m2 + 8) >> 4) - beta, 0);
+  // s ^ neg_e: R[e] is negated; fix_wide_mask: the low D bits, defined at D = 32 too
+  const uint32_t sg = ((__popc(neg) & 1) ? ~neg : neg) & fix_wide_mask(D);
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+    const int mag = (uint32_t)k == at ? m2n : m1n;
+    const int r = ((sg >> k) & 1u) ? -mag : mag;
+    const int pn = min(max(t[k] + r, -kLayFixApp), kLayFixApp);
+    p[k] = (p[k] & ~(0xFFu << (8 * j))) | ((uint32_t)(pn & 0xFF) << (8 * j));
+  }
+  m1s = m1n;
+  m2s = m2n;
+  pos = at;
+  signs = sg;
+}
+
+// One check of degree D for the lane's 4 codewords, narrow handle: bytes at `col` of every P row, words at srow of
+// S (fix_state_word), a 64-bit element index per edge.
 template <int D>
 __device__ __forceinline__ void layfix_cn_rows(const LayFixArgs& a, int e0, size_t srow, size_t col, size_t ldb,
                                                uint32_t fin) {
+  static_assert(D <= kLayMaxD, "degree body out of range");
   size_t v[D];
 #pragma unroll
   for (int k = 0; k < D; ++k) v[k] = (size_t)sload(a.cols, e0 + k) * ldb + col;
@@ -825,38 +968,46 @@ __device__ __forceinline__ void layfix_cn_rows(const LayFixArgs& a, int e0, size
 #pragma unroll
   for (int j = 0; j < kLayFixCw; ++j) {
     if ((fin >> j) & 1u) continue;   // frozen at its stop iteration
-    const uint32_t ws = w[j];
-    const int m1o = (int)((ws >> 20) & 63u), m2o = (int)(ws >> 26);
-    const uint32_t poso = (ws >> 16) & 15u;
-    int t[D];
-    int m1 = kLayFixQMax + 1, m2 = kLayFixQMax + 1;
-    uint32_t pos = 0, neg = 0;
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      const int mag = (uint32_t)k == poso ? m2o : m1o;
-      const int r = ((ws >> k) & 1u) ? -mag : mag;
-      const int x = (int)(int8_t)(p[k] >> (8 * j)) - r;
-      t[k] = x;
-      neg |= ((uint32_t)x >> 31) << k;
-      const int m = min(abs(x), qm);
-      pos = m < m1 ? (uint32_t)k : pos;   // moves only on m < m1: the first position attaining the minimum
-      m2 = min(m2, max(m1, m));
-      m1 = min(m1, m);
-    }
-    const int m1n = max(((alpha16 * m1 + 8) >> 4) - beta, 0), m2n = max(((alpha16 * m2 + 8) >> 4) - beta, 0);
-    const uint32_t sg = ((__popc(neg) & 1) ? ~neg : neg) & ((1u << D) - 1u);   // s ^ neg_e: R[e] is negated
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      const int mag = (uint32_t)k == pos ? m2n : m1n;
-      const int r = ((sg >> k) & 1u) ? -mag : mag;
-      const int pn = min(max(t[k] + r, -kLayFixApp), kLayFixApp);
-      p[k] = (p[k] & ~(0xFFu << (8 * j))) | ((uint32_t)(pn & 0xFF) << (8 * j));
-    }
-    w[j] = fix_state_word((uint32_t)m1n, (uint32_t)m2n, pos, sg);
+    int m1 = (int)((w[j] >> 20) & 63u), m2 = (int)(w[j] >> 26);
+    uint32_t pos = (w[j] >> 16) & 15u, sg = w[j];
+    layfix_minsum<D>(p, j, m1, m2, pos, sg, alpha16, beta, qm);
+    w[j] = fix_state_word((uint32_t)m1, (uint32_t)m2, pos, sg);
   }
 #pragma unroll
   for (int k = 0; k < D; ++k) *reinterpret_cast<uint32_t*>(a.P + v[k]) = p[k];
   *reinterpret_cast<uint4*>(a.S + srow) = make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// The same for a wide handle: the two state words of fix_state_words_wide in S and S1. tcol, srow: wave-uniform as
+// in lay_cn_rows_wide; the lane's four codewords are dword `lane` of a P row's tile and words 4 lane .. 4 lane + 3
+// of a state row's.
+template <int D>
+__device__ __forceinline__ void layfix_cn_rows_wide(const LayFixArgs& a, uint32_t* __restrict__ S1, int e0,
+                                                    size_t srow, size_t tcol, uint32_t lane, size_t ldb,
+                                                    uint32_t fin) {
+  const auto row = [&](int k) {
+    return reinterpret_cast<uint32_t*>(a.P + ((size_t)sload(a.cols, e0 + k) * ldb + tcol));
+  };
+  uint32_t p[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) p[k] = row(k)[lane];
+  const uint4 st0 = reinterpret_cast<const uint4*>(a.S + srow)[lane], st1 = reinterpret_cast<const uint4*>(S1 + srow)[lane];
+  uint32_t w0[kLayFixCw] = {st0.x, st0.y, st0.z, st0.w}, w1[kLayFixCw] = {st1.x, st1.y, st1.z, st1.w};
+  const int alpha16 = a.alpha16, beta = a.beta_q, qm = a.q_max;
+#pragma unroll
+  for (int j = 0; j < kLayFixCw; ++j) {
+    if ((fin >> j) & 1u) continue;   // frozen at its stop iteration
+    int m1 = (int)fix_wide_m1(w0[j]), m2 = (int)fix_wide_m2(w0[j]);
+    uint32_t pos = fix_wide_pos(w0[j]), sg = w1[j];
+    layfix_minsum<D>(p, j, m1, m2, pos, sg, alpha16, beta, qm);
+    const FixWideWords w = fix_state_words_wide((uint32_t)m1, (uint32_t)m2, pos, sg);
+    w0[j] = w.w0;
+    w1[j] = w.w1;
+  }
+#pragma unroll
+  for (int k = 0; k < D; ++k) row(k)[lane] = p[k];
+  reinterpret_cast<uint4*>(a.S + srow)[lane] = make_uint4(w0[0], w0[1], w0[2], w0[3]);
+  reinterpret_cast<uint4*>(S1 + srow)[lane] = make_uint4(w1[0], w1[1], w1[2], w1[3]);
 }
 
 }  // namespace
@@ -927,7 +1078,7 @@ __global__ __launch_bounds__(64 * kLayPassWaves) void layfix_stage_in_wide(const
   layfix_stage_in_body<true>(a, S1, llr, dtype, imax);
 }
 
-// item = (check slot0 + c of the layer, tile of 256), tile fastest
+// One layer: item = (check slot0 + c of the layer, tile of 256); narrow and wide as lay_layer and lay_layer_wide
 __global__ __launch_bounds__(64 * kLayPassWaves) void layfix_layer(const LayFixArgs a, int slot0, int n_checks) {
   if (sload(a.running, 0) == 0) return;
   const int lane = (int)(threadIdx.x & 63u);
@@ -945,8 +1096,30 @@ __global__ __launch_bounds__(64 * kLayPassWaves) void layfix_layer(const LayFixA
   const size_t srow = (size_t)slot * ldb + col;
   switch (d) {
 #define LAY_CASE(D) case D: layfix_cn_rows<D>(a, e0, srow, col, ldb, fin); break;
-    LAY_CASE(2) LAY_CASE(3) LAY_CASE(4) LAY_CASE(5) LAY_CASE(6) LAY_CASE(7) LAY_CASE(8) LAY_CASE(9)
-    LAY_CASE(10) LAY_CASE(11) LAY_CASE(12) LAY_CASE(13) LAY_CASE(14) LAY_CASE(15) LAY_CASE(16)
+    LAY_CASES_16
+#undef LAY_CASE
+    default: break;
+  }
+}
+__global__ __launch_bounds__(64 * kLayPassWaves) void layfix_layer_wide(const LayFixArgs a, uint32_t* S1, int slot0,
+                                                                        int n_checks) {
+  if (sload(a.running, 0) == 0) return;
+  const int lane = (int)(threadIdx.x & 63u);
+  const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  if (item >= (int64_t)n_checks * a.ntiles4) return;
+  const int tile = (int)(item % a.ntiles4);
+  const int slot = slot0 + (int)(item / a.ntiles4);
+  bool all;
+  const uint32_t fin = layfix_finished(a.done, tile, lane, &all);
+  if (all) return;
+  if (fin == 0xFu) return;
+  const int e0 = sload(a.rec, 2 * slot), d = sload(a.rec, 2 * slot + 1);
+  const size_t ldb = (size_t)a.ntiles4 * kLayFixTile;
+  const size_t tcol = (size_t)tile * kLayFixTile;
+  const size_t srow = (size_t)slot * ldb + tcol;
+  switch (d) {
+#define LAY_CASE(D) case D: layfix_cn_rows_wide<D>(a, S1, e0, srow, tcol, (uint32_t)lane, ldb, fin); break;
+    LAY_CASES_32
 #undef LAY_CASE
     default: break;
   }
@@ -1009,20 +1182,25 @@ bool layfix_args_ok(const LayFixArgs& a) {
 bool layfix_dtype_ok(int32_t dtype) { return dtype == kF32 || dtype == kI8; }
 }  // namespace
 
-hipError_t launch_layfix_stage_in(const LayFixArgs& a, const void* llr, int32_t dtype, int imax, hipStream_t s) {
+hipError_t launch_layfix_stage_in(const LayFixArgs& a, uint32_t* S1, const void* llr, int32_t dtype, int imax,
+                                  hipStream_t s) {
   if (!layfix_args_ok(a) || !llr || !layfix_dtype_ok(dtype)) return hipErrorInvalidValue;
   LayFixArgs args = a;
-  void* p[] = {&args, (void*)&llr, (void*)&dtype, (void*)&imax};
-  return lay_pass_launch((const void*)layfix_stage_in, (int64_t)std::max(a.n_v, a.n_c) * a.ntiles4, p, s);
+  void* pn[] = {&args, (void*)&llr, (void*)&dtype, (void*)&imax};
+  void* pw[] = {&args, (void*)&S1, (void*)&llr, (void*)&dtype, (void*)&imax};
+  return lay_pass_launch(S1 ? (const void*)layfix_stage_in_wide : (const void*)layfix_stage_in,
+                         (int64_t)std::max(a.n_v, a.n_c) * a.ntiles4, S1 ? pw : pn, s);
 }
 
-hipError_t launch_layfix_layer(const LayFixArgs& a, int slot0, int n_checks, hipStream_t s) {
+hipError_t launch_layfix_layer(const LayFixArgs& a, uint32_t* S1, int slot0, int n_checks, hipStream_t s) {
   if (!layfix_args_ok(a) || slot0 < 0 || n_checks < 0 || (int64_t)slot0 + n_checks > a.n_c)
     return hipErrorInvalidValue;
   if (n_checks == 0) return hipSuccess;
   LayFixArgs args = a;
-  void* p[] = {&args, (void*)&slot0, (void*)&n_checks};
-  return lay_pass_launch((const void*)layfix_layer, fix_items(n_checks, a.B), p, s);
+  void* pn[] = {&args, (void*)&slot0, (void*)&n_checks};
+  void* pw[] = {&args, (void*)&S1, (void*)&slot0, (void*)&n_checks};
+  return lay_pass_launch(S1 ? (const void*)layfix_layer_wide : (const void*)layfix_layer, fix_items(n_checks, a.B),
+                         S1 ? pw : pn, s);
 }
 
 hipError_t launch_layfix_stop(const LayFixArgs& a, int it, hipStream_t s) {
@@ -1049,374 +1227,22 @@ hipError_t launch_layfix_stage_out(const LayFixArgs& a, void* out, int32_t dtype
   return lay_pass_launch((const void*)layfix_stage_out, (int64_t)a.n_v * a.ntiles4, p, s);
 }
 
-// the largest private (scratch) segment over the fixed-point kernels: built to run without one
 hipError_t layfix_private_bytes(size_t* bytes) {
-  *bytes = 0;
-  for (const void* f : {(const void*)layfix_stage_in, (const void*)layfix_layer, (const void*)layfix_pack,
-                        (const void*)layfix_stage_out}) {
-    hipFuncAttributes fa;
-    const hipError_t e = hipFuncGetAttributes(&fa, f);
-    if (e != hipSuccess) return e;
-    *bytes = std::max(*bytes, (size_t)fa.localSizeBytes);
-  }
-  return hipSuccess;
+  return lay_private_bytes({(const void*)layfix_stage_in, (const void*)layfix_layer, (const void*)layfix_pack,
+                            (const void*)layfix_stage_out},
+                           bytes);
 }
-
-// ---------------------------------------------------------------------------------------------------------------
-// Wide checks: degrees up to kLayWideMaxD = 32 (include/ibldpc.h "Layered min-sum", wide handles; layered_plan.h
-// layered_is_wide). A handle whose code has a check of degree above 16 runs the kernels below instead of lay_fused,
-// lay_layer and layfix_layer, for EVERY check of the code: kernels of their own, because the degree bodies of one
-// kernel share one register allocation and unrolled degree-32 bodies inside lay_layer would cost the narrow codes
-// their occupancy. Steps and values are those of the narrow bodies; what differs is where the state lives:
-//   fp32        the sign bits of R fill a whole word PS (edge k at bit D - 1 - k as before), and the first argmin
-//               position has a word of its own, PO: four 4-byte words per check and codeword;
-//   fixed point two words per check and codeword in two arrays S0 / S1 [n_c][ldb] (layered_plan.h
-//               fix_state_words_wide): m2' << 11 | m1' << 5 | position, and the sign bits of R, edge k at bit k.
-// The per-layer bodies address a row as a wave-uniform base (the variable index is a scalar load and the tile is
-// the wave's) plus the lane's offset within the tile, so a check's D rows cost scalar registers and one 32-bit
-// vector offset, not D 64-bit vector addresses.
-// Everything else — syndrome, pack, finalise, stage-out, the compaction plan and commit — is shared as it stands.
-namespace {
-
-#define LAY_WIDE_CASES                                                                                          \
-  LAY_CASE(2) LAY_CASE(3) LAY_CASE(4) LAY_CASE(5) LAY_CASE(6) LAY_CASE(7) LAY_CASE(8) LAY_CASE(9) LAY_CASE(10)  \
-  LAY_CASE(11) LAY_CASE(12) LAY_CASE(13) LAY_CASE(14) LAY_CASE(15) LAY_CASE(16) LAY_CASE(17) LAY_CASE(18)       \
-  LAY_CASE(19) LAY_CASE(20) LAY_CASE(21) LAY_CASE(22) LAY_CASE(23) LAY_CASE(24) LAY_CASE(25) LAY_CASE(26)       \
-  LAY_CASE(27) LAY_CASE(28) LAY_CASE(29) LAY_CASE(30) LAY_CASE(31) LAY_CASE(32)
-
-// lay_cn with the position in PO[slot] and all of PS[slot] sign bits
-template <int D>
-__device__ __forceinline__ void lay_cn_wide(float* __restrict__ P, float* __restrict__ M1, float* __restrict__ M2,
-                                            uint32_t* __restrict__ PS, uint32_t* __restrict__ PO,
-                                            const int32_t* __restrict__ idx, int slot, float alpha, float beta,
-                                            float L) {
-  static_assert(D >= kLayMinD && D <= kLayWideMaxD, "degree body out of range");
-  int v[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) v[k] = idx[64 * k];
-  const float m1o = M1[slot], m2o = M2[slot];
-  const uint32_t ps = PS[slot], poso = PO[slot];
-  float q[D];
-  float m1 = __builtin_inff(), m2 = __builtin_inff();
-  uint32_t pos = 0, sx = 0;
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    const float r = lay_signed((uint32_t)k == poso ? m2o : m1o, ps << (32 - D + k));
-    const float x = __builtin_amdgcn_fmed3f(P[v[k]] - r, -L, L);
-    q[k] = x;
-    sx ^= lay_bits(x);
-    const float a = fabsf(x);
-    pos = a < m1 ? (uint32_t)k : pos;
-    m2 = __builtin_amdgcn_fmed3f(m1, m2, a);
-    m1 = fminf(m1, a);
-  }
-  const float m1n = fmaxf(alpha * m1 - beta, 0.f), m2n = fmaxf(alpha * m2 - beta, 0.f);
-  uint32_t sg = 0;
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    const uint32_t t = sx ^ lay_bits(q[k]);
-    P[v[k]] = q[k] + lay_signed((uint32_t)k == pos ? m2n : m1n, t);
-    sg = __builtin_amdgcn_alignbit(sg, t, 31);
-  }
-  M1[slot] = m1n;
-  M2[slot] = m2n;
-  PS[slot] = sg;
-  PO[slot] = pos;
-}
-
-// lay_cn_rows with the position in PO and all of PS sign bits. tcol: the tile's first column (wave-uniform), srow:
-// the first state word of (slot, tile) (wave-uniform); the lane's codeword is element `lane` of each.
-template <int D>
-__device__ __forceinline__ void lay_cn_rows_wide(const LayPassArgs& a, uint32_t* __restrict__ PO, int e0, size_t srow,
-                                                 size_t tcol, uint32_t lane, size_t ldb) {
-  static_assert(D >= kLayMinD && D <= kLayWideMaxD, "degree body out of range");
-  float p[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) p[k] = (a.P + ((size_t)sload(a.cols, e0 + k) * ldb + tcol))[lane];
-  const float m1o = (a.M1 + srow)[lane], m2o = (a.M2 + srow)[lane];
-  const uint32_t ps = (a.PS + srow)[lane], poso = (PO + srow)[lane];
-  const float alpha = a.alpha, beta = a.beta, L = a.llr_max;
-  float m1 = __builtin_inff(), m2 = __builtin_inff();
-  uint32_t pos = 0, sx = 0;
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    const float r = lay_signed((uint32_t)k == poso ? m2o : m1o, ps << (32 - D + k));
-    const float x = __builtin_amdgcn_fmed3f(p[k] - r, -L, L);
-    p[k] = x;   // Q from here on
-    sx ^= lay_bits(x);
-    const float m = fabsf(x);
-    pos = m < m1 ? (uint32_t)k : pos;
-    m2 = __builtin_amdgcn_fmed3f(m1, m2, m);
-    m1 = fminf(m1, m);
-  }
-  const float m1n = fmaxf(alpha * m1 - beta, 0.f), m2n = fmaxf(alpha * m2 - beta, 0.f);
-  uint32_t sg = 0;
-#pragma unroll
-  for (int k = 0; k < D; ++k) {
-    const uint32_t t = sx ^ lay_bits(p[k]);
-    (a.P + ((size_t)sload(a.cols, e0 + k) * ldb + tcol))[lane] = p[k] + lay_signed((uint32_t)k == pos ? m2n : m1n, t);
-    sg = __builtin_amdgcn_alignbit(sg, t, 31);
-  }
-  (a.M1 + srow)[lane] = m1n;
-  (a.M2 + srow)[lane] = m2n;
-  (a.PS + srow)[lane] = sg;
-  (PO + srow)[lane] = pos;
-}
-
-// layfix_cn_rows with the two state words of fix_state_words_wide. tcol, srow: wave-uniform as in lay_cn_rows_wide;
-// the lane's four codewords are dword `lane` of a P row's tile and words 4 lane .. 4 lane + 3 of a state row's.
-template <int D>
-__device__ __forceinline__ void layfix_cn_rows_wide(const LayFixArgs& a, uint32_t* __restrict__ S1, int e0,
-                                                    size_t srow, size_t tcol, uint32_t lane, size_t ldb,
-                                                    uint32_t fin) {
-  static_assert(D >= kLayMinD && D <= kLayWideMaxD, "degree body out of range");
-  uint32_t p[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k)
-    p[k] = reinterpret_cast<const uint32_t*>(a.P + ((size_t)sload(a.cols, e0 + k) * ldb + tcol))[lane];
-  const uint4 st0 = reinterpret_cast<const uint4*>(a.S + srow)[lane], st1 = reinterpret_cast<const uint4*>(S1 + srow)[lane];
-  uint32_t w0[kLayFixCw] = {st0.x, st0.y, st0.z, st0.w}, w1[kLayFixCw] = {st1.x, st1.y, st1.z, st1.w};
-  const int alpha16 = a.alpha16, beta = a.beta_q, qm = a.q_max;
-#pragma unroll
-  for (int j = 0; j < kLayFixCw; ++j) {
-    if ((fin >> j) & 1u) continue;   // frozen at its stop iteration
-    const int m1o = (int)fix_wide_m1(w0[j]), m2o = (int)fix_wide_m2(w0[j]);
-    const uint32_t poso = fix_wide_pos(w0[j]), so = w1[j];
-    int t[D];
-    int m1 = kLayFixQMax + 1, m2 = kLayFixQMax + 1;
-    uint32_t pos = 0, neg = 0;
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      const int mag = (uint32_t)k == poso ? m2o : m1o;
-      const int r = ((so >> k) & 1u) ? -mag : mag;
-      const int x = (int)(int8_t)(p[k] >> (8 * j)) - r;
-      t[k] = x;
-      neg |= ((uint32_t)x >> 31) << k;
-      const int m = min(abs(x), qm);
-      pos = m < m1 ? (uint32_t)k : pos;
-      m2 = min(m2, max(m1, m));
-      m1 = min(m1, m);
-    }
-    const int m1n = max(((alpha16 * m1 + 8) >> 4) - beta, 0), m2n = max(((alpha16 * m2 + 8) >> 4) - beta, 0);
-    const uint32_t sg = ((__popc(neg) & 1) ? ~neg : neg) & fix_wide_mask(D);   // s ^ neg_e: R[e] is negated
-#pragma unroll
-    for (int k = 0; k < D; ++k) {
-      const int mag = (uint32_t)k == pos ? m2n : m1n;
-      const int r = ((sg >> k) & 1u) ? -mag : mag;
-      const int pn = min(max(t[k] + r, -kLayFixApp), kLayFixApp);
-      p[k] = (p[k] & ~(0xFFu << (8 * j))) | ((uint32_t)(pn & 0xFF) << (8 * j));
-    }
-    const FixWideWords w = fix_state_words_wide((uint32_t)m1n, (uint32_t)m2n, pos, sg);
-    w0[j] = w.w0;
-    w1[j] = w.w1;
-  }
-#pragma unroll
-  for (int k = 0; k < D; ++k)
-    reinterpret_cast<uint32_t*>(a.P + ((size_t)sload(a.cols, e0 + k) * ldb + tcol))[lane] = p[k];
-  reinterpret_cast<uint4*>(a.S + srow)[lane] = make_uint4(w0[0], w0[1], w0[2], w0[3]);
-  reinterpret_cast<uint4*>(S1 + srow)[lane] = make_uint4(w1[0], w1[1], w1[2], w1[3]);
-}
-
-}  // namespace
-
-// lay_fused for a wide handle: the wave's slice of LDS is P[n_v], M1, M2, PS, PO [n_c] (cw_bytes = 4 N + 16 n_c).
-__global__ __launch_bounds__(64 * kLayMaxCw) void lay_fused_wide(const LayeredArgs a) {
-  extern __shared__ __align__(16) unsigned char lay_lds[];
-  const int lane = (int)(threadIdx.x & 63u);
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int ncw = a.cw_per_group;
-  if (wave >= ncw) return;
-  unsigned char* base = lay_lds + (size_t)wave * (size_t)a.cw_bytes;
-  float* P = reinterpret_cast<float*>(base);
-  float* M1 = P + a.n_v;
-  float* M2 = M1 + a.n_c;
-  uint32_t* PS = reinterpret_cast<uint32_t*>(M2 + a.n_c);
-  uint32_t* PO = PS + a.n_c;
-  const float alpha = a.alpha, beta = a.beta, L = a.llr_max;
-  for (int g = (int)blockIdx.x; g < a.ngroups; g += (int)gridDim.x) {
-    const int b = g * ncw + wave;
-    if (b >= a.B) break;   // wave-uniform; later groups of this workgroup lie further still
-    float* row = a.buf + (size_t)b * (size_t)a.n_v;
-    for (int v = lane; v < a.n_v; v += 64) P[v] = row[v] + 0.f;   // a -0 enters as +0, as in lay_fused
-    for (int c = lane; c < a.n_c; c += 64) {
-      M1[c] = 0.f;
-      M2[c] = 0.f;
-      PS[c] = 0u;
-      PO[c] = 0u;
-    }
-    int it = 1;
-    for (;; ++it) {
-      for (int t = 0; t < a.n_tasks; ++t) {
-        const int first = sload(a.task, 4 * t), cnt = sload(a.task, 4 * t + 1), d = sload(a.task, 4 * t + 2),
-                  s0 = sload(a.task, 4 * t + 3);
-        if (lane < cnt) {
-          const int32_t* idx = a.idx + first + lane;
-          const int slot = s0 + lane;
-          switch (d) {
-#define LAY_CASE(D) case D: lay_cn_wide<D>(P, M1, M2, PS, PO, idx, slot, alpha, beta, L); break;
-            LAY_WIDE_CASES
-#undef LAY_CASE
-            default: break;
-          }
-        }
-        __builtin_amdgcn_wave_barrier();   // the next task's reads stay behind this task's writes (other lanes')
-      }
-      if (it >= a.imax) break;
-      if (a.early) {
-        bool bad = false;
-        for (int t = 0; t < a.n_tasks && !bad; ++t) {
-          const int first = sload(a.task, 4 * t), cnt = sload(a.task, 4 * t + 1), d = sload(a.task, 4 * t + 2);
-          uint32_t par = 0;
-          if (lane < cnt) {
-            const int32_t* ix = a.idx + first + lane;
-            for (int k = 0; k < d; ++k) par ^= (P[ix[64 * k]] < 0.f) ? 1u : 0u;
-          }
-          bad = __builtin_amdgcn_readfirstlane((int)(__ballot(par != 0) != 0ull)) != 0;
-        }
-        if (!bad) break;
-      }
-    }
-    for (int v = lane; v < a.n_v; v += 64) row[v] = P[v];
-    if (a.iters && lane == 0) a.iters[b] = it;
-  }
-}
-
-// lay_layer for a wide handle. item = (check slot0 + c of the layer, tile), tile fastest
-__global__ __launch_bounds__(64 * kLayPassWaves) void lay_layer_wide(const LayPassArgs a, uint32_t* PO, int slot0,
-                                                                     int n_checks) {
-  if (sload(a.running, 0) == 0) return;
-  const int lane = (int)(threadIdx.x & 63u);
-  const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (item >= (int64_t)n_checks * a.ntiles) return;
-  const int tile = (int)(item % a.ntiles);
-  const int slot = slot0 + (int)(item / a.ntiles);
-  const uint64_t dm = lay_mask(a.done, tile);
-  if (dm == ~0ull) return;            // wave-uniform: the whole tile is finished
-  if ((dm >> lane) & 1ull) return;    // a finished (or padding) lane loads and stores nothing
-  const int e0 = sload(a.rec, 2 * slot), d = sload(a.rec, 2 * slot + 1);
-  const size_t ldb = (size_t)a.ntiles * kLayTile;
-  const size_t tcol = (size_t)tile * kLayTile;
-  const size_t srow = (size_t)slot * ldb + tcol;
-  switch (d) {
-#define LAY_CASE(D) case D: lay_cn_rows_wide<D>(a, PO, e0, srow, tcol, (uint32_t)lane, ldb); break;
-    LAY_WIDE_CASES
-#undef LAY_CASE
-    default: break;
-  }
-}
-
-// layfix_layer for a wide handle. item = (check slot0 + c of the layer, tile of 256), tile fastest
-__global__ __launch_bounds__(64 * kLayPassWaves) void layfix_layer_wide(const LayFixArgs a, uint32_t* S1, int slot0,
-                                                                        int n_checks) {
-  if (sload(a.running, 0) == 0) return;
-  const int lane = (int)(threadIdx.x & 63u);
-  const int64_t item = (int64_t)blockIdx.x * kLayPassWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  if (item >= (int64_t)n_checks * a.ntiles4) return;
-  const int tile = (int)(item % a.ntiles4);
-  const int slot = slot0 + (int)(item / a.ntiles4);
-  bool all;
-  const uint32_t fin = layfix_finished(a.done, tile, lane, &all);
-  if (all) return;             // wave-uniform: the whole tile is finished
-  if (fin == 0xFu) return;     // the lane's four codewords are finished (or padding)
-  const int e0 = sload(a.rec, 2 * slot), d = sload(a.rec, 2 * slot + 1);
-  const size_t ldb = (size_t)a.ntiles4 * kLayFixTile;
-  const size_t tcol = (size_t)tile * kLayFixTile;
-  const size_t srow = (size_t)slot * ldb + tcol;
-  switch (d) {
-#define LAY_CASE(D) case D: layfix_cn_rows_wide<D>(a, S1, e0, srow, tcol, (uint32_t)lane, ldb, fin); break;
-    LAY_WIDE_CASES
-#undef LAY_CASE
-    default: break;
-  }
-}
-#undef LAY_WIDE_CASES
-
-hipError_t lay_fused_wide_occupancy(int cw_per_group, size_t lds, int* blocks_per_cu, size_t* private_bytes) {
-  const void* f = (const void*)lay_fused_wide;
-  hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-  if (e != hipSuccess) return e;
-  hipFuncAttributes fa;
-  if ((e = hipFuncGetAttributes(&fa, f)) != hipSuccess) return e;
-  *private_bytes = fa.localSizeBytes;
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, f, 64 * cw_per_group, lds);
-}
-
-hipError_t launch_lay_fused_wide(const LayeredArgs& a, int grid, size_t lds, hipStream_t s) {
-  if (!a.buf || !a.task || !a.idx || a.cw_per_group < 1 || a.cw_per_group > kLayMaxCw || a.n_tasks < 1 ||
-      a.B < 1 || a.ngroups < 1 || grid < 1 || lds < (size_t)a.cw_per_group * (size_t)a.cw_bytes ||
-      lds > (size_t)kLdsBytes || (size_t)a.cw_bytes < layered_cw_bytes(a.n_v, a.n_c, true))
-    return hipErrorInvalidValue;
-  LayeredArgs args = a;
-  void* p[] = {&args};
-  return hipLaunchKernel((const void*)lay_fused_wide, dim3(grid), dim3(64 * a.cw_per_group), p, lds, s);
-}
-
-hipError_t launch_lay_stage_in_wide(const LayPassArgs& a, const LayCompactArgs* c, uint32_t* PO, const float* llr,
-                                    int imax, hipStream_t s) {
-  if (!lay_pass_args_ok(a) || !PO || !llr || (c && !lay_compact_args_ok(*c))) return hipErrorInvalidValue;
-  LayPassArgs args = a;
-  const int64_t items = (int64_t)std::max(a.n_v, a.n_c) * a.ntiles;
-  if (!c) {
-    void* p[] = {&args, (void*)&PO, (void*)&llr, (void*)&imax};
-    return lay_pass_launch((const void*)lay_stage_in_wide, items, p, s);
-  }
-  LayCompactArgs ca = *c;
-  void* p[] = {&args, &ca, (void*)&PO, (void*)&llr, (void*)&imax};
-  return lay_pass_launch((const void*)lay_stage_in_c_wide, items, p, s);
-}
-
-hipError_t launch_lay_layer_wide(const LayPassArgs& a, uint32_t* PO, int slot0, int n_checks, hipStream_t s) {
-  if (!lay_pass_args_ok(a) || !PO || slot0 < 0 || n_checks < 0 || (int64_t)slot0 + n_checks > a.n_c)
-    return hipErrorInvalidValue;
-  if (n_checks == 0) return hipSuccess;
-  LayPassArgs args = a;
-  void* p[] = {&args, (void*)&PO, (void*)&slot0, (void*)&n_checks};
-  return lay_pass_launch((const void*)lay_layer_wide, pass_items(n_checks, a.B), p, s);
-}
-
-// launch_lay_compact with the row move over the four state arrays
-hipError_t launch_lay_compact_wide(const LayPassArgs& a, const LayCompactArgs& c, uint32_t* PO, hipStream_t s) {
-  if (!lay_pass_args_ok(a) || !lay_compact_args_ok(c) || !PO) return hipErrorInvalidValue;
-  LayPassArgs args = a;
-  LayCompactArgs ca = c;
-  void* p[] = {&args, &ca};
-  void* pr[] = {&args, &ca, (void*)&PO};
-  hipError_t e = hipLaunchKernel((const void*)lay_compact_plan, dim3(1), dim3(64 * kLayPassWaves), p, 0, s);
-  if (e != hipSuccess) return e;
-  if ((e = lay_pass_launch((const void*)lay_compact_rows_wide, pass_compact_rows(a.n_v, a.n_c, true), pr, s)) != hipSuccess)
-    return e;
-  return hipLaunchKernel((const void*)lay_compact_commit, dim3(1), dim3(64 * kLayPassWaves), p, 0, s);
-}
-
-hipError_t launch_layfix_stage_in_wide(const LayFixArgs& a, uint32_t* S1, const void* llr, int32_t dtype, int imax,
-                                       hipStream_t s) {
-  if (!layfix_args_ok(a) || !S1 || !llr || !layfix_dtype_ok(dtype)) return hipErrorInvalidValue;
-  LayFixArgs args = a;
-  void* p[] = {&args, (void*)&S1, (void*)&llr, (void*)&dtype, (void*)&imax};
-  return lay_pass_launch((const void*)layfix_stage_in_wide, (int64_t)std::max(a.n_v, a.n_c) * a.ntiles4, p, s);
-}
-
-hipError_t launch_layfix_layer_wide(const LayFixArgs& a, uint32_t* S1, int slot0, int n_checks, hipStream_t s) {
-  if (!layfix_args_ok(a) || !S1 || slot0 < 0 || n_checks < 0 || (int64_t)slot0 + n_checks > a.n_c)
-    return hipErrorInvalidValue;
-  if (n_checks == 0) return hipSuccess;
-  LayFixArgs args = a;
-  void* p[] = {&args, (void*)&S1, (void*)&slot0, (void*)&n_checks};
-  return lay_pass_launch((const void*)layfix_layer_wide, fix_items(n_checks, a.B), p, s);
-}
-
-// the largest private (scratch) segment over the kernels only a wide handle launches: built to run without one
+// the kernels only a wide handle launches
 hipError_t lay_wide_private_bytes(size_t* bytes) {
-  *bytes = 0;
-  for (const void* f : {(const void*)lay_fused_wide, (const void*)lay_stage_in_wide, (const void*)lay_stage_in_c_wide,
-                        (const void*)lay_layer_wide, (const void*)lay_compact_rows_wide,
-                        (const void*)layfix_stage_in_wide, (const void*)layfix_layer_wide}) {
-    hipFuncAttributes fa;
-    const hipError_t e = hipFuncGetAttributes(&fa, f);
-    if (e != hipSuccess) return e;
-    *bytes = std::max(*bytes, (size_t)fa.localSizeBytes);
-  }
-  return hipSuccess;
+  return lay_private_bytes({(const void*)lay_fused_wide, (const void*)lay_stage_in_wide,
+                            (const void*)lay_stage_in_c_wide, (const void*)lay_layer_wide,
+                            (const void*)lay_compact_rows_wide, (const void*)layfix_stage_in_wide,
+                            (const void*)layfix_layer_wide},
+                           bytes);
 }
+
+#undef LAY_CASES_32
+#undef LAY_CASES_16
 
 }  // namespace ibl
+
