@@ -167,6 +167,69 @@ __device__ __forceinline__ uint32_t colq(uint32_t w, int k, uint32_t lane4) {
   return __builtin_amdgcn_perm(src, lane4, 0x03020000u | ((4u + (uint32_t)(k >> 1)) << 8));
 }
 
+// First-level lookups (both operands raw input nibbles, T_0(x_a, x_j) / V_0(c, x_j)): byte 1 of the address,
+// row nibble high and column nibble low, is formed for a whole word at once - one v_bfi_b32 (and a shift) per
+// parity on the two words, shared by the word's groups - and colb takes the whole address with the one
+// v_perm_b32 a column term costs anyway: no v_bfe_u32 and no v_lshl_or_b32 per codeword.
+// rowcol<P>: byte b = (row nibble 2b+P of x) << 4 | (column nibble 2b+P of y)
+template <int P>
+__device__ __forceinline__ uint32_t rowcol(uint32_t x, uint32_t y) {
+  if constexpr (P == 0) return ((x << 4) & 0xF0F0F0F0u) | (y & 0x0F0F0F0Fu);
+  else return (x & 0xF0F0F0F0u) | ((y >> 4) & 0x0F0F0F0Fu);
+}
+// address of codeword k's first-level lookup: byte 1 = byte k / 2 of the rowcol word of k's parity, bytes
+// 0, 2, 3 from the lane term (byte 1 of which is 0, as for colq)
+__device__ __forceinline__ uint32_t colb(uint32_t e, int k, uint32_t lane4) {
+  return __builtin_amdgcn_perm(e, lane4, 0x03020000u | ((4u + (uint32_t)(k >> 1)) << 8));
+}
+// Output packing: a word's nibbles join one dependent chain acc = (t << 4K) | acc, one v_lshl_or_b32 per nibble
+// and none for nibble 0, which starts the word (7 instructions per 8 nibbles; written out, or the compiler
+// rebuilds its shift / shift / v_or3 tree, 10 per 8).
+template <int K>
+__device__ __forceinline__ uint32_t pk(uint32_t acc, uint32_t t) {
+  static_assert(K >= 0 && K < 8, "nibble of a dword");
+  if constexpr (K == 0) {
+    return t;
+  } else {
+    uint32_t r;
+    asm("v_lshl_or_b32 %0, %1, %2, %3" : "=v"(r) : "v"(t), "n"(4 * K), "v"(acc));
+    return r;
+  }
+}
+
+// End of a step of an unrolled body (tools/gen_sched.py, "Unrolled bodies"): the scheduler keeps the generated
+// issue order.
+#ifndef IBL_STEP_FENCE
+#define IBL_STEP_FENCE 1
+#endif
+__device__ __forceinline__ void step_fence() {
+  if constexpr (IBL_STEP_FENCE) __builtin_amdgcn_sched_barrier(0);
+}
+// One line of ib_unrolled.inc = one chain step over the S sub-slots of a group (values n_0 .. n_{S-1});
+// K0, ST, k-th codeword K0 + ST s, lane4c and FC are the enclosing body's.
+#define IBL_E(e, x, y) const uint32_t e##_0 = rowcol<0>(x, y), e##_1 = rowcol<1>(x, y)
+#define IBL_EP(e, s) ((ST == 2 ? (K0 & 1) : ((s) & 1)) ? e##_1 : e##_0)   /* rowcol word of codeword K0 + ST s */
+#define IBL_X2(M, ...) M(0, __VA_ARGS__), M(1, __VA_ARGS__)
+#define IBL_X4(M, ...) IBL_X2(M, __VA_ARGS__), M(2, __VA_ARGS__), M(3, __VA_ARGS__)
+#define IBL_Q_(s, q, w, base) q##_##s = colq(w, K0 + ST * s, base)
+#define IBL_QC_(s, q, on, w) q##_##s = (on) ? colq(w, K0 + ST * s, lane4c) : 0u
+#define IBL_LUC_(s, n, p, q, c) n##_##s = luc(p##_##s, q##_##s, c)
+#define IBL_LU1_(s, n, e, base, c) n##_##s = lu(colb(IBL_EP(e, s), K0 + ST * s, base), c)
+#define IBL_LINK_(s, n, on, p, q) n##_##s = (on) ? luc(p##_##s, q##_##s, 0u) : p##_##s
+#define IBL_PK_(s, o, v) o = pk<K0 + ST * s>(o, v##_##s)
+#define IBL_Q2(...) const uint32_t IBL_X2(IBL_Q_, __VA_ARGS__)
+#define IBL_Q4(...) const uint32_t IBL_X4(IBL_Q_, __VA_ARGS__)
+#define IBL_QC2(...) const uint32_t IBL_X2(IBL_QC_, __VA_ARGS__)
+#define IBL_QC4(...) const uint32_t IBL_X4(IBL_QC_, __VA_ARGS__)
+#define IBL_LUC2(...) const uint32_t IBL_X2(IBL_LUC_, __VA_ARGS__)
+#define IBL_LUC4(...) const uint32_t IBL_X4(IBL_LUC_, __VA_ARGS__)
+#define IBL_LU12(...) const uint32_t IBL_X2(IBL_LU1_, __VA_ARGS__)
+#define IBL_LU14(...) const uint32_t IBL_X4(IBL_LU1_, __VA_ARGS__)
+#define IBL_LINK2(...) const uint32_t IBL_X2(IBL_LINK_, __VA_ARGS__)
+#define IBL_LINK4(...) const uint32_t IBL_X4(IBL_LINK_, __VA_ARGS__)
+#define IBL_PK2(...) IBL_X2(IBL_PK_, __VA_ARGS__)
+#define IBL_PK4(...) IBL_X4(IBL_PK_, __VA_ARGS__)
+
 // all-ones nibbles for the codewords of a word that lie inside the batch
 __device__ __forceinline__ uint32_t valid_nib8(int remaining) {
   return remaining >= 8 ? 0xFFFFFFFFu : (remaining <= 0 ? 0u : ((1u << (4 * remaining)) - 1u));
@@ -329,9 +392,11 @@ __device__ __forceinline__ void settle(const Buf& b) {
   asm volatile("" ::"v"(b.tgv));
 }
 
-// nibbles 4g..4g+3 of an output word
-__device__ __forceinline__ uint32_t pack4n(const uint32_t (&t)[4], int g) {
-  return (t[0] | (t[1] << 4) | (t[2] << 8) | (t[3] << 12)) << (16 * g);
+// nibbles 4g..4g+3 join an output word's pk chain (g = 0 starts the word; g is a constant of an unrolled loop, so
+// one arm remains)
+__device__ __forceinline__ uint32_t pack4n(uint32_t acc, const uint32_t (&t)[4], int g) {
+  return g == 0 ? pk<3>(pk<2>(pk<1>(pk<0>(acc, t[0]), t[1]), t[2]), t[3])
+                : pk<7>(pk<6>(pk<5>(pk<4>(acc, t[0]), t[1]), t[2]), t[3]);
 }
 
 // ------------------------------------------------------------------ check node
@@ -345,23 +410,87 @@ __device__ __forceinline__ uint32_t pack4n(const uint32_t (&t)[4], int g) {
 #define IBL_SCHED_FILE "ib_sched.inc"
 #endif
 #include IBL_SCHED_FILE
+// Unrolled bodies (tools/gen_sched.py --unrolled -> ib_unrolled.inc), run by the check pass of the maximum-degree-8
+// per-pass kernels and by the fused kernel's light bodies. IBL_WORD_CT = 0 builds without them (the loops over the
+// group position of before everywhere); a build with another schedule file names its own unrolled file, generated
+// with the same S / L (IBL_UNROLLED_FILE; tools/variants.py does both).
+#ifndef IBL_WORD_CT
+#define IBL_WORD_CT 1
+#endif
+#ifndef IBL_UNROLLED_FILE
+#define IBL_UNROLLED_FILE "ib_unrolled.inc"
+#endif
+template <int D, int MAXD = 8> constexpr bool kWordCT = IBL_WORD_CT && D <= 8 && MAXD <= 8;
+#if IBL_WORD_CT
+#include IBL_UNROLLED_FILE
+// the plain unrolled check body is the folding one with nothing folded
+template <int D, int K0, int ST>
+__device__ __forceinline__ void cn_group_ct(uint32_t lane4, const uint32_t (&in)[D], uint32_t fbase, uint32_t (&o)[D]) {
+  cn_group_fold_ct<D, 0, K0, ST>(lane4, in, fbase, 0u, 0u, 0u, o);
+}
+#else   // never called
+template <int D, int K0, int ST, class... A> __device__ void cn_group_ct(A...);
+template <int D, int FC, int K0, int ST, class... A> __device__ void cn_group_fold_ct(A...);
+template <int D, int K0, int ST, class... A> __device__ void vn_group_ct(A...);
+#endif
 
+// A word's groups one after the other with their positions known at compile time (K0 / ST template arguments
+// of the generated bodies): the output packing is then the pk chain (the callers' zeroed accumulators are dead:
+// pk<0> starts the word), and the perm selectors and shifts are constants. Whole words (NCW = 8) run as groups
+// of one parity, even codewords first (word_k0): a group then needs one of each input word's two nibble spreads
+// and one rowcol word per first-level pair, half the registers of consecutive codewords, which is what lets the
+// unrolled folding check body stay under its 128-VGPR cap (consecutive codewords spill 60 B there). The
+// scheduling barrier keeps the groups from interleaving (their chains would share the register file).
+template <int NCW> constexpr int kWordST = NCW == 8 ? 2 : 1;
+// first codeword of group gi of S codewords
+template <int S, int NCW>
+__host__ __device__ constexpr int word_k0(int gi) {
+  if (kWordST<NCW> == 1) return gi * S;
+  const int npp = 4 / S;   // groups per parity
+  return gi / npp + (gi % npp) * 2 * S;
+}
+template <int D, int GI, int NCW>
+__device__ __forceinline__ void cn_word_ct(uint32_t lane4, const uint32_t (&in)[D], uint32_t fbase,
+                                           uint32_t (&outw)[D]) {
+  constexpr int S = cn_sched_s(D);
+  static_assert(S == 2 || S == 4, "parity groups of 2 or 4 codewords");
+  cn_group_ct<D, word_k0<S, NCW>(GI), kWordST<NCW>>(lane4, in, fbase, outw);
+  if constexpr ((GI + 1) * S < NCW) {
+    __builtin_amdgcn_sched_barrier(0);
+    cn_word_ct<D, GI + 1, NCW>(lane4, in, fbase, outw);
+  }
+}
 // NCW: codewords of the word that are computed (nibbles 0 .. NCW-1; 4 = the fused kernel's half groups)
-template <int D, int NCW = 8>
+// CT: groups unrolled with compile-time positions (cn_word_ct) instead of a loop over the group's position
+template <int D, int NCW = 8, bool CT = false>
 __device__ __forceinline__ void cn_word(uint32_t lane4, const uint32_t (&in)[D], uint32_t fbase,
                                         const uint32_t (&cb)[4], uint32_t (&outw)[D]) {
-#pragma unroll 1   // unrolled (the spread words shared by a word's groups) the check body spills: 56 B at MAXD=8
-  for (int k0 = 0; k0 < NCW; k0 += cn_sched_s(D)) cn_group<D>(lane4, in, fbase, cb, outw, k0);
+  if constexpr (CT) {
+    cn_word_ct<D, 0, NCW>(lane4, in, fbase, outw);
+  } else {
+#pragma unroll 1
+    for (int k0 = 0; k0 < NCW; k0 += cn_sched_s(D)) cn_group<D>(lane4, in, fbase, cb, outw, k0);
+  }
 }
 
 // the folding bodies (degree-2 variable fold): class FC, lane4c = lane term with the fold table's slot,
 // ch0 / ch1 = channel words of the variables at inputs D-2 / D-1
-template <int D, int FC>
+template <int D, int FC, int GI = 0>
 __device__ __forceinline__ void cn_word_fold(uint32_t lane4, const uint32_t (&in)[D], uint32_t fbase,
                                              const uint32_t (&cb)[4], uint32_t lane4c, uint32_t ch0, uint32_t ch1,
                                              uint32_t (&outw)[D]) {
+  if constexpr (kWordCT<D>) {
+    constexpr int S = cn_sched_s(D);
+    static_assert(S == 2 || S == 4, "parity groups of 2 or 4 codewords");
+    cn_group_fold_ct<D, FC, word_k0<S, 8>(GI), kWordST<8>>(lane4, in, fbase, lane4c, ch0, ch1, outw);
+    if constexpr ((GI + 1) * S < 8) {
+      __builtin_amdgcn_sched_barrier(0);
+      cn_word_fold<D, FC, GI + 1>(lane4, in, fbase, cb, lane4c, ch0, ch1, outw);
+    }
+  } else {
 #pragma unroll 1
-  for (int k0 = 0; k0 < 8; k0 += cn_sched_s(D)) cn_group_fold<D, FC>(lane4, in, fbase, cb, lane4c, ch0, ch1, outw, k0);
+    for (int k0 = 0; k0 < 8; k0 += cn_sched_s(D)) cn_group_fold<D, FC>(lane4, in, fbase, cb, lane4c, ch0, ch1, outw, k0);
+  }
 }
 // the fold of a finished output word (the keeping passes, which need the unfolded word too): nibble out,
 // lookup against the channel word's column term, nibble back in
@@ -372,7 +501,7 @@ __device__ __forceinline__ uint32_t fold_word(uint32_t w, uint32_t ch, uint32_t 
     uint32_t t[4];
 #pragma unroll
     for (int s = 0; s < 4; ++s) t[s] = luc(nib(w, 4 * g + s), colq(ch, 4 * g + s, lane4c), 0u);
-    r |= pack4n(t, g);
+    r = pack4n(r, t, g);
   }
   return r;
 }
@@ -426,6 +555,9 @@ __device__ __forceinline__ void cn_compute(const IbFastArgs& a, uint32_t lane4, 
 #pragma unroll
   for (int i = 0; i < W; ++i) {
     uint32_t in[D], o[D];
+    if constexpr (kWordCT<D, Buf::kMax>) {   // the item's words do not interleave either
+      if (i) __builtin_amdgcn_sched_barrier(0);
+    }
 #pragma unroll
     for (int j = 0; j < D; ++j) {
       in[j] = b.row[j][i];
@@ -441,8 +573,8 @@ __device__ __forceinline__ void cn_compute(const IbFastArgs& a, uint32_t lane4, 
             t0[s] = lu((nib(in[1], 4 * g + s) << kRowSh) + lane4, fbase);
             t1[s] = lu((nib(in[0], 4 * g + s) << kRowSh) + lane4, fbase);
           }
-          o[0] |= pack4n(t0, g);
-          o[1] |= pack4n(t1, g);
+          o[0] = pack4n(o[0], t0, g);
+          o[1] = pack4n(o[1], t1, g);
         }
       } else {
         o[0] = in[1];
@@ -452,7 +584,7 @@ __device__ __forceinline__ void cn_compute(const IbFastArgs& a, uint32_t lane4, 
       const uint32_t c0 = GATHER ? in[D - 2] : chf[0][i], c1 = GATHER ? in[D - 1] : chf[1][i];
       cn_word_fold<D, FC>(lane4, in, fbase, cb, lane4 + slot_off(a.fold_slot), c0, c1, o);
     } else {
-      cn_word<D>(lane4, in, fbase, cb, o);
+      cn_word<D, 8, kWordCT<D, Buf::kMax>>(lane4, in, fbase, cb, o);
     }
 #pragma unroll
     for (int w = 0; w < D; ++w) outw[w][i] = o[w];
@@ -513,11 +645,26 @@ __device__ __forceinline__ void cn_compute_fold(const IbFastArgs& a, uint32_t la
 // c and the other inputs (kernels_template_irreg.cl:151-160): step 0 = channel table V_0,
 // step l = V_l; the last step (l = D-2) uses fslot (matching composed). Degree 1 forwards c
 // (:131-136). Schedules as for the check node (vn_group in ib_sched.inc).
-template <int D, int NCW = 8>
+template <int D, int GI, int NCW>
+__device__ __forceinline__ void vn_word_ct(uint32_t lane4, const uint32_t (&in)[D], uint32_t chw,
+                                           uint32_t fbase, uint32_t (&outw)[D]) {
+  constexpr int S = vn_sched_s(D);
+  static_assert(S == 2 || S == 4, "parity groups of 2 or 4 codewords");
+  vn_group_ct<D, word_k0<S, NCW>(GI), kWordST<NCW>>(lane4, in, fbase, chw, outw);
+  if constexpr ((GI + 1) * S < NCW) {
+    __builtin_amdgcn_sched_barrier(0);
+    vn_word_ct<D, GI + 1, NCW>(lane4, in, chw, fbase, outw);
+  }
+}
+template <int D, int NCW = 8, bool CT = false>
 __device__ __forceinline__ void vn_word(uint32_t lane4, const uint32_t (&in)[D], uint32_t chw,
                                         uint32_t fbase, const uint32_t (&cb)[4], uint32_t (&outw)[D]) {
+  if constexpr (CT) {
+    vn_word_ct<D, 0, NCW>(lane4, in, chw, fbase, outw);
+  } else {
 #pragma unroll 1
-  for (int k0 = 0; k0 < NCW; k0 += vn_sched_s(D)) vn_group<D>(lane4, in, chw, fbase, cb, outw, k0);
+    for (int k0 = 0; k0 < NCW; k0 += vn_sched_s(D)) vn_group<D>(lane4, in, chw, fbase, cb, outw, k0);
+  }
 }
 
 template <int D, class Buf>
@@ -540,6 +687,7 @@ __device__ __forceinline__ void vn_compute(const IbFastArgs& a, uint32_t lane4, 
         in[j] = b.row[j][i];
         o[j] = 0;
       }
+      // (the loop bodies: unrolled, the variable pass issued 12 % fewer VALU per lookup and was no faster)
       vn_word<D>(lane4, in, b.chw[i], fbase, cb, o);
 #pragma unroll
       for (int w = 0; w < D; ++w) outw[w][i] = o[w];
@@ -954,8 +1102,8 @@ __device__ __forceinline__ void cn_small_item(const IbFastArgs& a, uint32_t lane
           t0[s] = lu((nib(in[1], 4 * g + s) << kRowSh) + lane4, fbase);
           t1[s] = lu((nib(in[0], 4 * g + s) << kRowSh) + lane4, fbase);
         }
-        o[0] |= pack4n(t0, g);
-        o[1] |= pack4n(t1, g);
+        o[0] = pack4n(o[0], t0, g);
+        o[1] = pack4n(o[1], t1, g);
       }
     } else {
       o[0] = in[1];
@@ -1116,7 +1264,9 @@ __global__ __launch_bounds__(kSmallBlock) void ib_dec_small(IbDecArgs a) {
 template <int D, int NCW>
 __device__ __forceinline__ void fused_cn_word(uint32_t lane4, const uint32_t (&in)[D], uint32_t fbase,
                                               const uint32_t (&cb)[4], uint32_t (&o)[D]) {
-  if constexpr (IBL_FUSED_UNROLL && D <= 6) {
+  if constexpr (IBL_FUSED_UNROLL && IBL_WORD_CT && D <= 6) {
+    cn_word<D, NCW, true>(lane4, in, fbase, cb, o);
+  } else if constexpr (IBL_FUSED_UNROLL && D <= 6) {
 #pragma unroll
     for (int k0 = 0; k0 < NCW; k0 += cn_sched_s(D)) cn_group<D>(lane4, in, fbase, cb, o, k0);
   } else {
@@ -1126,7 +1276,9 @@ __device__ __forceinline__ void fused_cn_word(uint32_t lane4, const uint32_t (&i
 template <int D, int NCW>
 __device__ __forceinline__ void fused_vn_word(uint32_t lane4, const uint32_t (&in)[D], uint32_t chw, uint32_t fbase,
                                               const uint32_t (&cb)[4], uint32_t (&o)[D]) {
-  if constexpr (IBL_FUSED_UNROLL && D <= 4) {
+  if constexpr (IBL_FUSED_UNROLL && IBL_WORD_CT && D <= 4) {
+    vn_word<D, NCW, true>(lane4, in, chw, fbase, cb, o);
+  } else if constexpr (IBL_FUSED_UNROLL && D <= 4) {
 #pragma unroll
     for (int k0 = 0; k0 < NCW; k0 += vn_sched_s(D)) vn_group<D>(lane4, in, chw, fbase, cb, o, k0);
   } else {
@@ -1161,8 +1313,8 @@ __device__ __forceinline__ void fused_cn_dword(uint32_t* msg, int first, int cnt
           t0[s] = lu((nib(in[1], 4 * g + s) << kRowSh) + lane4, fbase);
           t1[s] = lu((nib(in[0], 4 * g + s) << kRowSh) + lane4, fbase);
         }
-        o[0] |= pack4n(t0, g);
-        o[1] |= pack4n(t1, g);
+        o[0] = pack4n(o[0], t0, g);
+        o[1] = pack4n(o[1], t1, g);
       }
     } else {
       o[0] = in[1];

@@ -39,6 +39,8 @@ column images, the byte-lookup schedules of before); the option stays for other 
 usage: python tools/gen_sched.py [S_cn L_cn S_vn L_vn [NC_cn NC_vn]] > informationbottleneckdecodingldpc_amd/csrc/ib_sched.inc
 (measured on DVB-S2: CN S=4 L=2, VN S=2 L=4, NC 0 0; NC_cn / NC_vn must equal IBL_NC_CN / IBL_NC_VN
 of the build that includes the file - the file static_asserts it)
+       python tools/gen_sched.py --unrolled [S_cn L_cn S_vn L_vn] > informationbottleneckdecodingldpc_amd/csrc/ib_unrolled.inc
+(the unrolled bodies of the degree <= 8 kernels, see "Unrolled bodies" below)
 """
 import sys
 
@@ -248,5 +250,121 @@ def main():
         print("}")
 
 
+# ----------------------------------------------------------------------------------------------------------------
+# Unrolled bodies (csrc/ib_unrolled.inc, `python tools/gen_sched.py --unrolled [S_cn L_cn S_vn L_vn]`), degrees
+# <= 8. The per-pass fast kernels of maximum degree 8 (and the fused kernel's light bodies) run a word's groups one
+# after the other with the group's position a template argument: K0 = first codeword, ST = stride, codeword of
+# sub-slot s = K0 + ST s. ST = 2 groups hold codewords of one parity, so a group needs one of each input word's two
+# nibble spreads and one row/column word per first-level pair. Against the bodies above:
+#   * output packing is one dependent chain acc = (t << 4k) | acc per word (pk<K>): 7 v_lshl_or_b32 per 8 nibbles,
+#     none for nibble 0, no zeroing (the loop form: 10 per 8 and a v_mov_b32);
+#   * a lookup whose two operands are raw input nibbles (chain start, or the channel) takes its whole address with
+#     one v_perm_b32 (colb) from a word-level row/column byte (rowcol<P>: a shift and a v_bfi_b32 per word and
+#     parity): no v_bfe_u32 and no v_lshl_or_b32 per codeword;
+#   * an input whose column term meets only the final table at its run-time slot carries the slot in its lane term;
+#   * emission order = issue order: every step ends with a scheduling barrier (step_fence), and a step is [column
+#     terms first used here] [fold links of the chains that ended one step ago] [its lookups] [packing of the values
+#     read one step ago], so the v_perm_b32 and the packing run in the shadow of LDS reads already issued. (Left to
+#     itself the scheduler, at the register cap in a block this long, advances the chains diagonally and drains the
+#     LDS queue 78 times per item instead of 41.)
+# One line per chain step: the IBL_*<S> macros of ib_kernels.hip expand it over the S sub-slots (names n_0 .. n_{S-1}).
+def emit_unrolled(kind, D, S, L, fold=False):
+    chains = cn_chains(D) if kind == "cn" else vn_chains(D)
+    by_id = {c["id"]: c for c in chains}
+    sched = schedule(chains, L)
+    assert S in (2, 4)
+
+    def first_level(c, k):
+        step = c["steps"][k]
+        if step[0] == "c":
+            return ("c", step[1])
+        if k == 0 and c["start"][0] == "nib":
+            return (c["start"][1], step[1])
+        return None
+
+    steps = [(c, k, st) for c in chains for k, st in enumerate(c["steps"])]
+    fl = sorted({first_level(c, k) for c, k, _ in steps} - {None}, key=str)
+    u8_in = sorted({st[1] for c, k, st in steps if not first_level(c, k)})
+    uses = {j: {st[2] for c, k, st in steps if st[1] == j and not first_level(c, k)} for j in u8_in}
+    q_final = {j for j in u8_in if j == D - 1 or uses[j] == {"fbase"}}
+    lines = ["  const uint32_t lane4f = lane4 + fbase;"]
+    for a, j in fl:
+        lines.append(f"  IBL_E(E{a}_{j}, {'chw' if a == 'c' else f'in[{a}]'}, in[{j}]);")
+    defined, links, packs = set(), [], []
+
+    def need(key):
+        if key in defined:
+            return []
+        defined.add(key)
+        if isinstance(key, tuple):
+            return [f"  IBL_QC{S}(qc{key[1]}, FC & {1 << key[1]}, ch{key[1]});"]
+        return [f"  IBL_Q{S}(q{key}, in[{key}], {'lane4f' if key in q_final else 'lane4'});"]
+
+    def flush(pre, look, done):
+        nonlocal links, packs
+        for a, cid, v in links:
+            lines.extend(need(("qc", a)))
+        lines.extend(pre)
+        for a, cid, v in links:   # fold link: the degree-2 variable's update, F2(channel, this output)
+            lines.append(f"  IBL_LINK{S}(f_{cid}, FC & {1 << a}, {v}, qc{a});")
+        lines.extend(look)
+        for out, v in packs:
+            lines.append(f"  IBL_PK{S}(o[{out}], {v});")
+        packs = [(by_id[cid]["out"], f"f_{cid}") for a, cid, v in links] + [d for d in done if d[0] is not None]
+        links = [(d[1], d[2], d[3]) for d in done if d[0] is None]
+        lines.append("  step_fence();")
+
+    for t, issued in sched:
+        pre, look, done = [], [], []
+        for cid, k in issued:
+            c = by_id[cid]
+            op, j, sl, _ = c["steps"][k]
+            f1 = first_level(c, k)
+            name = f"v_{cid}_{k}"
+            if f1:
+                final = sl == "fbase" or j == D - 1
+                look.append(f"  IBL_LU1{S}({name}, E{f1[0]}_{f1[1]}, {'lane4f, 0u' if final else 'lane4, ' + sl});")
+            else:
+                pre.extend(need(j))
+                st = c["start"]
+                prev = f"v_{cid}_{k - 1}" if k else f"v_{st[1]}_{st[2]}"
+                assert k or st[0] == "val"
+                look.append(f"  IBL_LUC{S}({name}, {prev}, q{j}, {'0u' if j in q_final else sl});")
+            if k == len(c["steps"]) - 1:
+                a = c["out"] - (D - 2)
+                done.append((None, a, cid, name) if fold and a >= 0 else (c["out"], name))
+        flush(pre, look, done)
+    while links or packs:
+        flush([], [], [])
+    return lines
+
+
+def main_unrolled(a):
+    Sc, Lc, Sv, Lv = a or [4, 2, 2, 4]
+    print(f"// GENERATED by tools/gen_sched.py {' '.join(['--unrolled', *map(str, a)])} -- do not edit.")
+    print(f"// Unrolled fold schedules of the IB fast path, degrees <= 8 (see tools/gen_sched.py): CN groups of {Sc}")
+    print(f"// codewords, {Lc} chains; VN groups of {Sv}, {Lv} chains. K0 = first codeword, ST = stride of the group.")
+    print(f"static_assert(cn_sched_s(8) == {Sc} && vn_sched_s(8) == {Sv} && cn_ncols(7) == 0 && vn_ncols(8) == 0,")
+    print("              \"the unrolled bodies were generated for another schedule (IBL_UNROLLED_FILE)\");")
+    cargs = "uint32_t lane4, const uint32_t (&in)[D], uint32_t fbase"
+    # (the plain check bodies are the folding ones at FC = 0: cn_group_ct in ib_kernels.hip)
+    # The variable bodies stop at degree 4, the fused kernel's light bodies: the per-pass variable kernel keeps the
+    # loop bodies (unrolled it issued 12 % fewer VALU per lookup and was no faster).
+    for kind, lo, hi, fold in (("cn", 3, 8, True), ("vn", 2, 4, False)):
+        fn = f"{kind}_group{'_fold' if fold else ''}_ct"
+        extra = (", uint32_t lane4c, uint32_t ch0, uint32_t ch1" if fold else "") + (", uint32_t chw" if kind == "vn" else "")
+        print(f"template <int D, {'int FC, ' if fold else ''}int K0, int ST> __device__ __forceinline__ void {fn}({cargs}{extra},")
+        print("    uint32_t (&o)[D]) {")
+        print(f"  static_assert(D >= {lo} && D <= {hi} && K0 >= 0 && (ST == 1 || ST == 2), \"unrolled bodies: degrees {lo}..{hi}\");")
+        for D in range(lo, hi + 1):
+            print(f"  if constexpr (D == {D}) {{")
+            print("\n".join("  " + l for l in emit_unrolled(kind, D, Sc if kind == "cn" else Sv, Lc if kind == "cn" else Lv, fold)))
+            print("  }")
+        print("}")
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:2] == ["--unrolled"]:
+        main_unrolled([int(x) for x in sys.argv[2:]])
+    else:
+        main()

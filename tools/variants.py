@@ -81,6 +81,10 @@ VARIANTS = {
     "ieeeon": [],
     # min-sum check node with the (min, second min) pair for every degree (the round-3 form)
     "msps0": ["IBL_MS_PS=0"],
+    # generated node bodies (DESIGN.md "VALU per lookup"): without the unrolled bodies (the parent's loops); the
+    # unrolled bodies without the scheduling barrier after each step
+    "loopw": ["IBL_WORD_CT=0"],
+    "nofence": ["IBL_STEP_FENCE=0"],
     # fused float check tasks without the constant-stride body for full tasks
     "cn64off": ["IBL_FL_CN64=0"],
 }
@@ -95,11 +99,21 @@ if __name__ == "__main__":
     outdir = os.path.join(_build.PKG, "variants")
     os.makedirs(outdir, exist_ok=True)
     for n in names:
+        defines = list(VARIANTS[n])
         if n in SCHED_ARGS:
+            gen = [sys.executable, os.path.join(os.path.dirname(__file__), "gen_sched.py")]
+            args = SCHED_ARGS[n].split()
             inc = os.path.join(_build.CSRC, f"ib_sched_{n}.inc")
             with open(inc, "w") as f:
-                subprocess.run([sys.executable, os.path.join(os.path.dirname(__file__), "gen_sched.py"),
-                                *SCHED_ARGS[n].split()], stdout=f, check=True)
+                subprocess.run([*gen, *args], stdout=f, check=True)
+            # the unrolled bodies follow the variant's S / L (their own file); schedules they do not exist for
+            # (column fetches, groups of 8) build without them
+            if args[4:6] == ["0", "0"] and args[0] in ("2", "4") and args[2] in ("2", "4"):
+                with open(os.path.join(_build.CSRC, f"ib_sched_{n}_unrolled.inc"), "w") as f:
+                    subprocess.run([*gen, "--unrolled", *args[:4]], stdout=f, check=True)
+                defines.append(f'IBL_UNROLLED_FILE="ib_sched_{n}_unrolled.inc"')
+            else:
+                defines.append("IBL_WORD_CT=0")
         lib = os.path.join(outdir, f"libibldpc_{n}.so")
-        _build.build(defines=VARIANTS[n], lib=lib, tag=n, src_flags=SRC_FLAGS.get(n), force="--force" in os.environ.get("VARIANT_FLAGS", ""))
+        _build.build(defines=defines, lib=lib, tag=n, src_flags=SRC_FLAGS.get(n), force="--force" in os.environ.get("VARIANT_FLAGS", ""))
         print(lib)
