@@ -340,9 +340,9 @@ int ibl_float_create(const ibl_graph* g, int32_t kind, int32_t imax, double llr_
   HIPCHK(hipSetDevice(g->device));
   std::unique_ptr<ibl_float> h(new ibl_float());
   h->g = g; h->kind = kind; h->imax = imax; h->prec = precision; h->max_batch = max_batch; h->llr_max = llr_max;
-  // rows padded to the widest wave item of the per-pass kernels (fp32 256 / fp64 128 codewords; 512 with IBL_FL_VN2
-  // builds), not beyond: the reference's DVB-S2 driver decodes msg_at_time = 2 in fp64
-  const int pad = std::max(64 * (precision == kF32 ? 4 : 2), fl_vn_chunk(precision, g->dvm));
+  // rows padded to the wave item of the per-pass kernels (fp32 256 / fp64 128 codewords), not beyond: the
+  // reference's DVB-S2 driver decodes msg_at_time = 2 in fp64
+  const int pad = fl_vn_chunk(precision, g->dvm);
   h->ldb = (max_batch + pad - 1) / pad * pad;
   const size_t es = precision == kF32 ? 4 : 8;
   const size_t inbox = (size_t)g->n_e * h->ldb * es;

@@ -24,9 +24,6 @@ struct ibl_ib {
   DevBuf<uint32_t> cn_img, vn_img, dec_img;
   int cn_nt = 0, vn_nt = 0, dec_nt = 0;   // fast path: LDS table quads (4 tables each) per pass
   int32_t cn_fslot[kMaxD + 1] = {0}, vn_fslot[kMaxD + 1] = {0};
-  DevBuf<uint32_t> cn_cimg, vn_cimg;      // column images per pass (ncs x 32 dwords)
-  int cn_ncs = 0, vn_ncs = 0;
-  int8_t cn_ccol[kMaxD + 1][4] = {{0}}, vn_ccol[kMaxD + 1][4] = {{0}};
   KCfg kcn, kvn, kdec;
   KTimer timer;
   // degree-2 variable fold of the per-pass path (plan.h plan_ib_fold; ib_cn_fast<8, ., FOLD>): the host plan
@@ -69,10 +66,9 @@ struct IbSlots {   // one pass's LDS table slots (ib_plan_slots)
   std::vector<int> cdeg, vdeg;            // the degrees present
   int cn_nraw = 0, vn_nraw = 0;           // raw (reference) tables of a check / variable pass
   int cn_nt = 0, vn_nt = 0;               // all tables of a pass: raw, matching-composed finals, the fold's
-  std::vector<int> ccol_slot, vcol_slot;  // column image index -> table slot
 };
 struct IbImages {
-  std::vector<uint32_t> cimg, vimg, dimg, ccimg, vcimg;
+  std::vector<uint32_t> cn_img, vn_img, dec_img;
 };
 
 Table make_table(int T, const std::function<int(int, int)>& f) {
@@ -104,27 +100,11 @@ std::vector<int> present(const std::vector<int32_t>& deg) {
   return d;
 }
 
-// LDS bytes of a fast CN / VN launch: table quads, column images, the 2 work counters
-size_t fast_lds(int nt, int ncs) {
-  return lds_of_quads(regions_of(nt)) + (size_t)ncs * kColImg + 64;
-}
+// LDS bytes of a fast CN / VN launch: table quads, the 2 work counters
+size_t fast_lds(int nt) { return lds_of_quads(regions_of(nt)) + 64; }
 
-// One pass's column images (colf): per image slot, 16 columns m x {entries t = 0..7, t = 8..15} as nibbles
-void append_cols(std::vector<uint32_t>& img, const std::vector<Table>& tbs, const std::vector<int>& slots) {
-  for (int s : slots)
-    for (int m = 0; m < kTP; ++m) {
-      uint32_t lo = 0, hi = 0;
-      for (int t = 0; t < 8; ++t) {
-        lo |= (uint32_t)(tbs[s][t * kTP + m] & 15) << (4 * t);
-        hi |= (uint32_t)(tbs[s][(t + 8) * kTP + m] & 15) << (4 * t);
-      }
-      img.push_back(lo);
-      img.push_back(hi);
-    }
-}
-
-int pick_cfg(int which, int maxd, int nt, int ncs, int num_cus, KCfg* k) {
-  k->lds = fast_lds(nt, ncs);
+int pick_cfg(int which, int maxd, int nt, int num_cus, KCfg* k) {
+  k->lds = fast_lds(nt);
   int best_waves = 0;
   // largest block first at equal occupancy: a CU's waves then share one work counter
   for (int block : {1024, 768, 640, 512, 384, 256}) {
@@ -163,7 +143,7 @@ int ib_validate(const ibl_graph* g, int32_t Tc, int32_t T, int32_t imax, const I
   return IBL_OK;
 }
 
-// Table slots of the pass images (each degree's final one: cn_fslot / vn_fslot), column-fetched inputs, whether
+// Table slots of the pass images (each degree's final one: cn_fslot / vn_fslot), whether
 // the code takes the fast path (h->fast), and the degree-2 variable fold's plan with its slot.
 IbSlots ib_plan_slots(ibl_ib* h, int32_t flags) {
   const ibl_graph* g = h->g;
@@ -179,37 +159,18 @@ IbSlots ib_plan_slots(ibl_ib* h, int32_t flags) {
     for (int d : sl.vdeg) sl.vn_nt += (d >= 2);
   }
   const int max_nt = (kLdsBytes / kSuper) * 8;   // whole super-regions of 2 quads: 16 tables
-  // table slot of each column-fetched input (cn_ncols / vn_ncols): raw fold table, or the degree's
-  // final (matching-composed) table; slots are numbered as in the pass images (ib_build_images)
-  auto col_index = [](std::vector<int>& v, int s) {
-    for (size_t i = 0; i < v.size(); ++i)
-      if (v[i] == s) return (int8_t)i;
-    v.push_back(s);
-    return (int8_t)(v.size() - 1);
-  };
   int slot = sl.cn_nraw;
   for (int d : sl.cdeg) {
     const int fs = h->match ? slot++ : (d >= 3 ? d - 3 : 0);
     if (deg_ok) h->cn_fslot[d] = fs;
-    for (int i = 0, nc = cn_ncols(d); i < nc; ++i) {
-      const int l = d - nc + i - 2;   // input j = d-nc+i meets table j-2 in every non-prefix chain
-      h->cn_ccol[d][i] = col_index(sl.ccol_slot, l == d - 3 ? fs : l);
-    }
   }
   slot = sl.vn_nraw;
   for (int d : sl.vdeg) {
     if (d < 2) continue;
     const int fs = h->match ? slot++ : d - 2;
     if (deg_ok) h->vn_fslot[d] = fs;
-    for (int i = 0, nc = vn_ncols(d); i < nc; ++i) {
-      const int l = d - nc + i - 1;   // input j meets table j-1
-      h->vn_ccol[d][i] = col_index(sl.vcol_slot, l == d - 2 ? fs : l);
-    }
   }
-  h->cn_ncs = (int)sl.ccol_slot.size();
-  h->vn_ncs = (int)sl.vcol_slot.size();
-  const bool lds_ok = fast_lds(sl.cn_nt, h->cn_ncs) <= (size_t)kLdsBytes &&
-                      fast_lds(std::max(sl.vn_nt, 1), h->vn_ncs) <= (size_t)kLdsBytes;
+  const bool lds_ok = fast_lds(sl.cn_nt) <= (size_t)kLdsBytes && fast_lds(std::max(sl.vn_nt, 1)) <= (size_t)kLdsBytes;
   h->fast = !(flags & IBL_FLAG_FORCE_GENERIC) && h->Tc == h->T && h->T <= kTP && deg_ok && sl.cn_nt <= max_nt &&
             sl.vn_nt <= max_nt && VM <= max_nt && sl.cn_nt > 0 && lds_ok;
   if (h->fast && CM <= 8) {
@@ -218,7 +179,7 @@ IbSlots ib_plan_slots(ibl_ib* h, int32_t flags) {
     // 8 used), or one more quad if the LDS has room for it.
     std::vector<int32_t> rec, rest;
     const int32_t n = plan_ib_fold(*g, &rec, &rest);
-    if (n > 0 && sl.cn_nt + 1 <= max_nt && fast_lds(sl.cn_nt + 1, h->cn_ncs) <= (size_t)kLdsBytes) {
+    if (n > 0 && sl.cn_nt + 1 <= max_nt && fast_lds(sl.cn_nt + 1) <= (size_t)kLdsBytes) {
       h->n_folded = n;
       h->fold_slot = sl.cn_nt++;
       std::vector<int32_t> cls((size_t)g->n_c), all((size_t)g->n_c);
@@ -272,8 +233,7 @@ IbImages ib_build_images(ibl_ib* h, const IbLuts& lu, const IbSlots& sl) {
         return h->match ? lu.mv[mrow + r] : r;
       }));
     }
-    append_pass(im.cimg, tbs, regions_of(sl.cn_nt));
-    append_cols(im.ccimg, tbs, sl.ccol_slot);
+    append_pass(im.cn_img, tbs, regions_of(sl.cn_nt));
   }
   h->cn_nt = regions_of(sl.cn_nt);
   // ---------------- VN images: pass k = 0 .. imax-2 (extrinsic), decision images k = 0 .. imax-1
@@ -285,25 +245,24 @@ IbImages ib_build_images(ibl_ib* h, const IbLuts& lu, const IbSlots& sl) {
       const int64_t mrow = (int64_t)k * T * VM + (int64_t)(d - 1) * T;
       tbs.push_back(make_table(T, [&](int t, int m) { return lu.mv[mrow + vn_raw(k, d - 2, t, m)]; }));
     }
-    append_pass(im.vimg, tbs, regions_of(std::max(sl.vn_nt, 1)));
-    append_cols(im.vcimg, tbs, sl.vcol_slot);
+    append_pass(im.vn_img, tbs, regions_of(std::max(sl.vn_nt, 1)));
   }
   h->vn_nt = regions_of(std::max(sl.vn_nt, 1));
   for (int k = 0; k < imax; ++k) {
     std::vector<Table> tbs;
     for (int l = 0; l < VM; ++l) tbs.push_back(make_table(T, [&](int t, int m) { return vn_raw(k, l, t, m); }));
-    append_pass(im.dimg, tbs, regions_of(VM));
+    append_pass(im.dec_img, tbs, regions_of(VM));
   }
   h->dec_nt = regions_of(VM);
   return im;
 }
 
-// Fused IB decoder eligibility (fast path, no column images, messages + the largest pass's table
+// Fused IB decoder eligibility (fast path, messages + the largest pass's table
 // quads within the CU's LDS, check degree >= 2, an occupancy of >= 1 block without scratch) and
 // task tables. Leaves fused_ok false when the code does not fit.
 int ib_fused_setup(ibl_ib* h) {
   const ibl_graph* g = h->g;
-  if (!h->fast || h->cn_ncs || h->vn_ncs || g->n_e == 0 || g->dc_min < 2) return IBL_OK;
+  if (!h->fast || g->n_e == 0 || g->dc_min < 2) return IBL_OK;
   const int nreg = std::max(h->cn_nt, std::max(h->vn_nt, h->dec_nt));
   // one table set: tables, raw images, slots; two sets (see TablePrefetch; a single quad's two sets share
   // one super-region) where they fit beside the slots; IBL_FUSED_DBUF=0 turns them off (A/B)
@@ -360,12 +319,11 @@ int ib_configure_fast(ibl_ib* h, const IbImages& im) {
   const ibl_graph* g = h->g;
   const int CM = h->CM, VM = h->VM;
   int rc;
-  if ((rc = h->cn_img.upload(im.cimg)) || (rc = h->vn_img.upload(im.vimg)) || (rc = h->dec_img.upload(im.dimg)) ||
-      (rc = h->cn_cimg.upload(im.ccimg)) || (rc = h->vn_cimg.upload(im.vcimg)))
+  if ((rc = h->cn_img.upload(im.cn_img)) || (rc = h->vn_img.upload(im.vn_img)) || (rc = h->dec_img.upload(im.dec_img)))
     return rc;
-  if ((rc = pick_cfg(0, CM, 4 * h->cn_nt, h->cn_ncs, g->num_cus, &h->kcn)) ||
-      (rc = pick_cfg(1, VM, 4 * h->vn_nt, h->vn_ncs, g->num_cus, &h->kvn)) ||
-      (rc = pick_cfg(2, VM, 4 * h->dec_nt, 0, g->num_cus, &h->kdec)))
+  if ((rc = pick_cfg(0, CM, 4 * h->cn_nt, g->num_cus, &h->kcn)) ||
+      (rc = pick_cfg(1, VM, 4 * h->vn_nt, g->num_cus, &h->kvn)) ||
+      (rc = pick_cfg(2, VM, 4 * h->dec_nt, g->num_cus, &h->kdec)))
     return rc;
   size_t priv = 0;
   const char* kname = "";
@@ -379,16 +337,14 @@ int ib_configure_fast(ibl_ib* h, const IbImages& im) {
                                              "-byte private segment (register spill / scratch item): rebuild required")))
     return rc;
   if ((rc = ib_fused_setup(h))) return rc;
-  // small-batch per-pass kernels: the fast path's tables without column images; used for B <= small_b
-  // (IBL_SMALL_B at create overrides the default, 0 turns them off)
-  if (h->cn_ncs == 0 && h->vn_ncs == 0) {
-    HIPCHK(ib_small_private_bytes(CM, VM, &priv, &kname));
-    h->s_ok = priv == 0;
-    small_batch_env(h->s_ok, kSmallBatchDefault, &h->small_b, &h->s_graphs);
-    h->s_lds_cn = lds_of_quads(h->cn_nt);
-    h->s_lds_vn = lds_of_quads(h->vn_nt);
-    h->s_lds_dec = lds_of_quads(h->dec_nt);
-  }
+  // small-batch per-pass kernels: the fast path's tables; used for B <= small_b (IBL_SMALL_B at create overrides
+  // the default, 0 turns them off)
+  HIPCHK(ib_small_private_bytes(CM, VM, &priv, &kname));
+  h->s_ok = priv == 0;
+  small_batch_env(h->s_ok, kSmallBatchDefault, &h->small_b, &h->s_graphs);
+  h->s_lds_cn = lds_of_quads(h->cn_nt);
+  h->s_lds_vn = lds_of_quads(h->vn_nt);
+  h->s_lds_dec = lds_of_quads(h->dec_nt);
   return IBL_OK;
 }
 
@@ -603,12 +559,8 @@ int ib_decode_fast(ibl_ib* h, const void* d_ch, int32_t ch_dtype, int32_t B, voi
 #endif
   cn.nchunks = (B + ccn - 1) / ccn;
   vn.nchunks = (B + cvn - 1) / cvn;
-  std::memcpy(cn.ccol, h->cn_ccol, sizeof(cn.ccol));
-  std::memcpy(vn.ccol, h->vn_ccol, sizeof(vn.ccol));
-  cn.ncs = h->cn_ncs; vn.ncs = h->vn_ncs;
   // pass 0: send + checknode_update_iter0, inputs gathered from the staged channel rows
   cn.in = nullptr; cn.gather = g->csr_cols; cn.img = h->cn_img; cn.gate = nullptr; cn.unsat = nullptr;
-  cn.cimg = h->cn_cimg;
   cn_fold(0);
   auto launch_cn = [&]() { return launch_ib_cn_fast(cn, h->CM, h->kcn.grid, h->kcn.block, h->kcn.lds, s); };
   HIPCHK(h->timer.timed(0, s, launch_cn));
@@ -630,13 +582,11 @@ int ib_decode_fast(ibl_ib* h, const void* d_ch, int32_t ch_dtype, int32_t B, voi
   for (int j = 1; j < I; ++j) {
     const int32_t* gate = flag_row(h->flags, early && j >= 2, j - 1);
     vn.img = h->vn_img + (size_t)(j - 1) * h->vn_nt * 256;
-    vn.cimg = h->vn_cimg + (size_t)(j - 1) * h->vn_ncs * 32;
     vn.gate = gate;
     vn.trace = (trace && j == I / 2) ? trace : nullptr;
     vn.out = cb[j & 1];
     HIPCHK(h->timer.timed(1, s, [&] { return launch_ib_vn_fast(vn, h->VM, h->kvn.grid, h->kvn.block, h->kvn.lds, s); }));
     cn.img = h->cn_img + (size_t)j * h->cn_nt * 256;
-    cn.cimg = h->cn_cimg + (size_t)j * h->cn_ncs * 32;
     cn.gate = gate;
     cn.unsat = flag_row(h->flags, early, j);
     cn.trace = (trace && j == I / 2) ? trace + 3 * nwv : nullptr;
@@ -730,7 +680,7 @@ int ibl_ib_path(const ibl_ib* h) { return h && h->fast ? 1 : 0; }
 int ibl_ib_set_small_batch(ibl_ib* h, int32_t max_b) {
   if (!h) return fail(IBL_EINVAL, "decoder is NULL");
   if (max_b < 0) return fail(IBL_EINVAL, "max_b must be >= 0");
-  if (max_b > 0 && !(h->fast && h->cn_ncs == 0 && h->vn_ncs == 0 && h->s_lds_cn > 0))
+  if (max_b > 0 && !(h->fast && h->s_lds_cn > 0))
     return fail(IBL_EUNSUPPORTED, "the small-batch kernels need the fast path (T_ch = T_dec <= 16, degrees <= 16)");
   if (max_b > 0 && !h->s_ok)   // create turned them off: this build's small-batch kernels need scratch
     return fail(IBL_EUNSUPPORTED, "the small-batch kernels of this build have a private segment: rebuild required");

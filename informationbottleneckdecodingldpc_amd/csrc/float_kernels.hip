@@ -229,15 +229,12 @@ __device__ __forceinline__ bool syndrome_bit(const F (&m)[D][NC], int s) {
 }
 
 // Check-node body on the inputs m of NC codewords (min-sum or BP); put(w, o) receives output w (any
-// order of w). IBL_MS_PS = 0 keeps the (min, second min) form for every degree (A/B).
-#ifndef IBL_MS_PS
-#define IBL_MS_PS 1
-#endif
+// order of w).
 template <int KIND, typename F, int D, int NC, class Put>
 __device__ __forceinline__ void fl_cn_body(const F (&m)[D][NC], F lm, Put&& put) {
   constexpr int N = NC;
   F o[N];
-  if constexpr (KIND == 0 && D <= 8 && IBL_MS_PS) {
+  if constexpr (KIND == 0 && D <= 8) {
     // min-sum (kernels_min_and_BP.cl:156-162) with prefix / suffix minima: |out_w| = min over the others =
     // min(P_w, S_{w+1}), P_w = min |m_0..m_{w-1}|, S_j = min |m_j..m_{D-1}| — 3(D-2) v_min (|x| as an input
     // modifier) instead of the running (min, second min) pair plus a compare and a select per output
@@ -502,50 +499,7 @@ __device__ __forceinline__ void fl_vn_item(const FlArgs& a, int node, int st, in
   ob.flush(sink);
 }
 
-// IBL_FL_VN2 = 1: the per-pass variable items take two adjacent 16-byte pieces of every row per lane (2-KiB row
-// segments per wave, the guide's faster gather shape: 5.7-5.8 vs 5.5-5.6 TB/s), outputs stored as computed
-#ifndef IBL_FL_VN2
-#define IBL_FL_VN2 0
-#endif
-// lane l takes the pieces at cw0 = chunk base + l*N and cw0 + 64*N: each load / store instruction covers 1 KiB
-// contiguous, two instructions a 2-KiB segment
-template <typename F, int D>
-__device__ __forceinline__ void fl_vn_item2(const FlArgs& a, int node, int st, int cw0) {
-  constexpr int N = Vec<F>::N, N2 = 2 * N;
-  const F* src = reinterpret_cast<const F*>(a.in);
-  const F* ch = reinterpret_cast<const F*>(a.ch);
-  const F lm = (F)a.llr_max;
-  int tg[D];
-#pragma unroll
-  for (int w = 0; w < D; ++w) tg[w] = sload(a.tgt, st + w);
-  F c[N2], m[D][N2];
-  {
-    F lo[N], hi[N];
-    fl_row_load<F>(ch + (size_t)node * a.ldb + cw0, lo);
-    fl_row_load<F>(ch + (size_t)node * a.ldb + cw0 + 64 * N, hi);
-#pragma unroll
-    for (int s = 0; s < N; ++s) { c[s] = lo[s]; c[N + s] = hi[s]; }
-  }
-#pragma unroll
-  for (int j = 0; j < D; ++j) {
-    F lo[N], hi[N];
-    fl_row_load<F>(src + (size_t)(st + j) * a.ldb + cw0, lo);
-    fl_row_load<F>(src + (size_t)(st + j) * a.ldb + cw0 + 64 * N, hi);
-#pragma unroll
-    for (int s = 0; s < N; ++s) { m[j][s] = lo[s]; m[j][N + s] = hi[s]; }
-  }
-  fl_vn_body<F, D, N2>(c, m, lm, [&](int w, const F (&o)[N2]) __attribute__((always_inline)) {
-    F lo[N], hi[N];
-#pragma unroll
-    for (int s = 0; s < N; ++s) { lo[s] = o[s]; hi[s] = o[N + s]; }
-    fl_store_to<F>(a.out, a.ldb, tg[w], cw0, lo);
-    fl_store_to<F>(a.out, a.ldb, tg[w], cw0 + 64 * N, hi);
-  });
-}
-// (the degree > 8 bodies keep one piece per lane: two would spill)
-template <int MAXD>
-constexpr bool fl_vn_wide() { return IBL_FL_VN2 && MAXD <= 8; }
-int fl_vn_chunk(int prec, int maxd) { return 64 * (prec == kF32 ? 4 : 2) * ((IBL_FL_VN2 && maxd <= 8) ? 2 : 1); }
+int fl_vn_chunk(int prec, int maxd) { return 64 * (prec == kF32 ? 4 : 2); }
 
 #define FL_DEG_CASES(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
 
@@ -612,7 +566,7 @@ template <typename F, int MAXD>
 __global__ __launch_bounds__((fl_block_of<1, MAXD>())) void fl_vn(FlArgs a) {
   const int lane = fl_tid() & 63;
   if (!fl_gate(a.gate, lane)) return;
-  constexpr int CWL = Vec<F>::N * (fl_vn_wide<MAXD>() ? 2 : 1);
+  constexpr int CWL = Vec<F>::N;
   constexpr int CH = 64 * CWL;
   __shared__ int ctr;
   if (fl_tid() == 0) ctr = 0;
@@ -625,23 +579,13 @@ __global__ __launch_bounds__((fl_block_of<1, MAXD>())) void fl_vn(FlArgs a) {
     const int chunk = __builtin_amdgcn_readfirstlane(item - pos * a.nchunks);
     const int node = a.nodes ? sload(a.nodes, pos) : pos;   // the fold's variable list skips folded nodes
     const int d = sload(a.deg, node), st = sload(a.start, node);
-    const int cw0 = chunk * CH + lane * Vec<F>::N;   // (wide items: the second piece 64 * N further)
-    if constexpr (fl_vn_wide<MAXD>()) {
-      switch (d) {
-        case 1: fl_vn_item2<F, 1>(a, node, st, cw0); break;
-#define X(D) case D: if constexpr (D <= MAXD) fl_vn_item2<F, D>(a, node, st, cw0); break;
-        FL_DEG_CASES(X)
-#undef X
-        default: break;
-      }
-    } else {
-      switch (d) {
-        case 1: fl_vn_item<F, 1>(a, node, st, cw0); break;
+    const int cw0 = chunk * CH + lane * CWL;
+    switch (d) {
+      case 1: fl_vn_item<F, 1>(a, node, st, cw0); break;
 #define X(D) case D: if constexpr (D <= MAXD) fl_vn_item<F, D>(a, node, st, cw0); break;
-        FL_DEG_CASES(X)
+      FL_DEG_CASES(X)
 #undef X
-        default: break;
-      }
+      default: break;
     }
   }
 }
@@ -990,10 +934,6 @@ __global__ __launch_bounds__(kFlSmallBlock) void fl_dec_small(FlDecArgs a) {
 }
 
 // ------------------------------------------------------------ fused on-chip decoder
-// IBL_FL_CN64: full check tasks (64 nodes) run a body with the constant edge stride (A/B: 0 = off)
-#ifndef IBL_FL_CN64
-#define IBL_FL_CN64 1
-#endif
 // For codes whose messages fit in LDS ((E + N) * 16 B <= 160 KiB, e.g. WLAN N=1944: 142.6 KB), one
 // workgroup decodes Vec<F>::N codewords (4 fp32 / 2 fp64, one 16-byte slot per edge and per
 // variable) through ALL iterations without touching HBM: the flooding schedule of
@@ -1120,9 +1060,9 @@ __global__ __launch_bounds__((fl_fused_block_of<CMAX, KIND, F>())) void fl_fused
   };
   auto cn_task = [&](int t, int valid, bool do_par, bool& unsat) __attribute__((always_inline)) {
     const int first = sload(a.cn_task, 4 * t), cnt = sload(a.cn_task, 4 * t + 1), d = sload(a.cn_task, 4 * t + 2);
-    // the constant-stride body exists for degrees <= 8 only; full tasks of larger degrees take the general
-    // branch below (every lane < cnt = 64)
-    if (IBL_FL_CN64 && cnt == 64 && d <= 8) {
+    // full tasks (64 nodes) run a body with the constant edge stride; it exists for degrees <= 8 only, and full
+    // tasks of larger degrees take the general branch below (every lane < cnt = 64)
+    if (cnt == 64 && d <= 8) {
       switch (d) {
 #define X(D) case D: if constexpr (D <= CMAX && D <= 8) fused_cn_item<KIND, F, D, NCs, 64>(msg, first, cnt, lane, h, lm, do_par, valid, unsat); break;
         FL_DEG_CASES(X)

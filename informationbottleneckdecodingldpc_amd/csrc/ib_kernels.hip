@@ -27,7 +27,6 @@
 //     into the check-node pass (parity of its inputs), and published as device flags that
 //     gate the next launches — no host readback inside the iteration loop.
 #include <algorithm>
-#include <type_traits>
 
 #include "common.h"
 
@@ -53,23 +52,6 @@ __device__ __forceinline__ uint32_t luc(uint32_t t, uint32_t q, uint32_t c) {
   static_assert(kRowSh == 12, "luc's shift is the row shift of the table layout");
   asm("v_lshl_or_b32 %0, %1, 12, %2" : "=v"(x) : "v"(t), "v"(q));
   return *(lds8_t*)(size_t)(x + c);
-}
-// Column fetch (tools/gen_sched.py, "Column fetches"): column T(., m) of one table as 16 nibbles
-// (entry t at bits 4t..4t+3), one ds_read_b64 from the bank-replicated column image at byte
-// m*256 + 8*(lane&31) of the table's 4-KiB image; cb = 8*(lane&31) + image base. The 32 lanes of a
-// bank group read 2 of the 64 banks each: conflict free.
-typedef __attribute__((address_space(3))) const uint64_t lds64_t;
-__device__ __forceinline__ uint64_t colf(uint32_t m, uint32_t cb) {
-  uint32_t x;
-  asm("v_lshl_or_b32 %0, %1, 8, %2" : "=v"(x) : "v"(m), "v"(cb));
-  return *(lds64_t*)(size_t)x;
-}
-// entry t of a fetched column, sh = 4t in its low 6 bits (v_lshrrev_b64 reads only those): a
-// previous column result r, whose bits above its nibble hold the next entries, passes as r << 2.
-__device__ __forceinline__ uint32_t csel(uint64_t col, uint32_t sh) {
-  uint64_t r;
-  asm("v_lshrrev_b64 %0, %1, %2" : "=v"(r) : "v"(sh), "v"(col));
-  return (uint32_t)r;
 }
 __device__ __forceinline__ uint32_t lds_base(const uint8_t* p) { return (uint32_t)(size_t)(lds8_t*)p; }
 __device__ __forceinline__ void lds_at_zero(const uint8_t* lds) {
@@ -97,28 +79,7 @@ __device__ __forceinline__ bool gate_open(const int32_t* gate, int lane) {
 // unit loop needed one round trip per 4 units a thread (8 for 3 quads at 256 threads). An odd quad count
 // leaves the last super-region's half 1 unwritten (never read).
 constexpr int kStageR = 4;
-#ifndef IBL_STAGE_UNITS
-#define IBL_STAGE_UNITS 0   // 1: the earlier loop, four 16-byte units per thread and round trip (A/B)
-#endif
 __device__ __forceinline__ void stage_tables(uint8_t* lds, const uint32_t* img, int nreg) {
-  if constexpr (IBL_STAGE_UNITS) {
-    uint4* l4 = reinterpret_cast<uint4*>(lds);
-    const int n = (int)(lds_of_quads(nreg) / 16), bd = blockDim.x;
-    for (int u = threadIdx.x; u < n; u += 4 * bd) {
-      uint32_t w[4];
-      bool ok[4];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        const int v = u + k * bd, q = ((v >> 12) << 1) | ((v >> 3) & 1);
-        ok[k] = v < n && q < nreg;
-        w[k] = ok[k] ? img[q * 256 + ((v >> 4) & 255)] : 0u;
-      }
-#pragma unroll
-      for (int k = 0; k < 4; ++k)
-        if (ok[k]) l4[u + k * bd] = make_uint4(w[k], w[k], w[k], w[k]);
-    }
-    return;
-  }
   const int nraw = nreg * 256, lane = threadIdx.x & 63;
   const int wv = threadIdx.x >> 6, nwv = blockDim.x >> 6, nchunk = (nraw + 63) >> 6;
   for (int c0 = 0; c0 < nchunk; c0 += kStageR * nwv) {
@@ -142,14 +103,6 @@ __device__ __forceinline__ void stage_tables(uint8_t* lds, const uint32_t* img, 
       }
     }
   }
-}
-
-// column images: ncs tables x 16 columns x 2 dwords (entries t < 8, t >= 8) replicated for the 32
-// lanes of a bank group: LDS dword c*1024 + m*64 + 2*L + h (see colf)
-__device__ __forceinline__ void stage_cols(uint8_t* dst, const uint32_t* cimg, int ncs) {
-  uint32_t* l32 = reinterpret_cast<uint32_t*>(dst);
-  const int n = ncs * 1024;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) l32[i] = cimg[((i >> 10) << 5) | (((i >> 6) & 15) << 1) | (i & 1)];
 }
 
 // Fast-path message format: T <= 16, so every message is a 4-bit nibble; an edge row stores
@@ -199,12 +152,7 @@ __device__ __forceinline__ uint32_t pk(uint32_t acc, uint32_t t) {
 
 // End of a step of an unrolled body (tools/gen_sched.py, "Unrolled bodies"): the scheduler keeps the generated
 // issue order.
-#ifndef IBL_STEP_FENCE
-#define IBL_STEP_FENCE 1
-#endif
-__device__ __forceinline__ void step_fence() {
-  if constexpr (IBL_STEP_FENCE) __builtin_amdgcn_sched_barrier(0);
-}
+__device__ __forceinline__ void step_fence() { __builtin_amdgcn_sched_barrier(0); }
 // One line of ib_unrolled.inc = one chain step over the S sub-slots of a group (values n_0 .. n_{S-1});
 // K0, ST, k-th codeword K0 + ST s, lane4c and FC are the enclosing body's.
 #define IBL_E(e, x, y) const uint32_t e##_0 = rowcol<0>(x, y), e##_1 = rowcol<1>(x, y)
@@ -411,28 +359,18 @@ __device__ __forceinline__ uint32_t pack4n(uint32_t acc, const uint32_t (&t)[4],
 #endif
 #include IBL_SCHED_FILE
 // Unrolled bodies (tools/gen_sched.py --unrolled -> ib_unrolled.inc), run by the check pass of the maximum-degree-8
-// per-pass kernels and by the fused kernel's light bodies. IBL_WORD_CT = 0 builds without them (the loops over the
-// group position of before everywhere); a build with another schedule file names its own unrolled file, generated
-// with the same S / L (IBL_UNROLLED_FILE; tools/variants.py does both).
-#ifndef IBL_WORD_CT
-#define IBL_WORD_CT 1
-#endif
+// per-pass kernels and by the fused kernel's light bodies. A build with another schedule file names its own unrolled
+// file, generated with the same S / L (IBL_UNROLLED_FILE; tools/variants.py does both).
 #ifndef IBL_UNROLLED_FILE
 #define IBL_UNROLLED_FILE "ib_unrolled.inc"
 #endif
-template <int D, int MAXD = 8> constexpr bool kWordCT = IBL_WORD_CT && D <= 8 && MAXD <= 8;
-#if IBL_WORD_CT
+template <int D, int MAXD = 8> constexpr bool kWordCT = D <= 8 && MAXD <= 8;
 #include IBL_UNROLLED_FILE
 // the plain unrolled check body is the folding one with nothing folded
 template <int D, int K0, int ST>
 __device__ __forceinline__ void cn_group_ct(uint32_t lane4, const uint32_t (&in)[D], uint32_t fbase, uint32_t (&o)[D]) {
   cn_group_fold_ct<D, 0, K0, ST>(lane4, in, fbase, 0u, 0u, 0u, o);
 }
-#else   // never called
-template <int D, int K0, int ST, class... A> __device__ void cn_group_ct(A...);
-template <int D, int FC, int K0, int ST, class... A> __device__ void cn_group_fold_ct(A...);
-template <int D, int K0, int ST, class... A> __device__ void vn_group_ct(A...);
-#endif
 
 // A word's groups one after the other with their positions known at compile time (K0 / ST template arguments
 // of the generated bodies): the output packing is then the pk chain (the callers' zeroed accumulators are dead:
@@ -464,12 +402,12 @@ __device__ __forceinline__ void cn_word_ct(uint32_t lane4, const uint32_t (&in)[
 // CT: groups unrolled with compile-time positions (cn_word_ct) instead of a loop over the group's position
 template <int D, int NCW = 8, bool CT = false>
 __device__ __forceinline__ void cn_word(uint32_t lane4, const uint32_t (&in)[D], uint32_t fbase,
-                                        const uint32_t (&cb)[4], uint32_t (&outw)[D]) {
+                                        uint32_t (&outw)[D]) {
   if constexpr (CT) {
     cn_word_ct<D, 0, NCW>(lane4, in, fbase, outw);
   } else {
 #pragma unroll 1
-    for (int k0 = 0; k0 < NCW; k0 += cn_sched_s(D)) cn_group<D>(lane4, in, fbase, cb, outw, k0);
+    for (int k0 = 0; k0 < NCW; k0 += cn_sched_s(D)) cn_group<D>(lane4, in, fbase, outw, k0);
   }
 }
 
@@ -477,19 +415,13 @@ __device__ __forceinline__ void cn_word(uint32_t lane4, const uint32_t (&in)[D],
 // ch0 / ch1 = channel words of the variables at inputs D-2 / D-1
 template <int D, int FC, int GI = 0>
 __device__ __forceinline__ void cn_word_fold(uint32_t lane4, const uint32_t (&in)[D], uint32_t fbase,
-                                             const uint32_t (&cb)[4], uint32_t lane4c, uint32_t ch0, uint32_t ch1,
-                                             uint32_t (&outw)[D]) {
-  if constexpr (kWordCT<D>) {
-    constexpr int S = cn_sched_s(D);
-    static_assert(S == 2 || S == 4, "parity groups of 2 or 4 codewords");
-    cn_group_fold_ct<D, FC, word_k0<S, 8>(GI), kWordST<8>>(lane4, in, fbase, lane4c, ch0, ch1, outw);
-    if constexpr ((GI + 1) * S < 8) {
-      __builtin_amdgcn_sched_barrier(0);
-      cn_word_fold<D, FC, GI + 1>(lane4, in, fbase, cb, lane4c, ch0, ch1, outw);
-    }
-  } else {
-#pragma unroll 1
-    for (int k0 = 0; k0 < 8; k0 += cn_sched_s(D)) cn_group_fold<D, FC>(lane4, in, fbase, cb, lane4c, ch0, ch1, outw, k0);
+                                             uint32_t lane4c, uint32_t ch0, uint32_t ch1, uint32_t (&outw)[D]) {
+  constexpr int S = cn_sched_s(D);
+  static_assert(S == 2 || S == 4, "parity groups of 2 or 4 codewords");
+  cn_group_fold_ct<D, FC, word_k0<S, 8>(GI), kWordST<8>>(lane4, in, fbase, lane4c, ch0, ch1, outw);
+  if constexpr ((GI + 1) * S < 8) {
+    __builtin_amdgcn_sched_barrier(0);
+    cn_word_fold<D, FC, GI + 1>(lane4, in, fbase, lane4c, ch0, ch1, outw);
   }
 }
 // the fold of a finished output word (the keeping passes, which need the unfolded word too): nibble out,
@@ -506,30 +438,23 @@ __device__ __forceinline__ uint32_t fold_word(uint32_t w, uint32_t ch, uint32_t 
   return r;
 }
 
-// column-image addresses of the column-fetched inputs of a degree-D node (cb of colf)
-__device__ __forceinline__ void col_bases(const int8_t (&cc)[4], uint32_t lane8c, uint32_t (&cb)[4]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) cb[i] = lane8c + ((uint32_t)cc[i] << 12);
-}
-
 // FC / KEEP (folding check pass, D >= 3): bit 0 / 1 of FC = the degree-2 variable at input D-2 / D-1 is folded.
-// Its update F2(channel, this check's output) is one more link of that output's chain (cn_group_fold), and the
+// Its update F2(channel, this check's output) is one more link of that output's chain (cn_group_fold_ct), and the
 // result goes straight to the row of the variable's other edge in the NEXT iteration's check inbox (fout).
 // With KEEP the unfolded output is also written to the variable inbox (early stop: any pass may be the last
 // and the decision reads every row): the body is the plain one and the fold runs over the finished words
 // (fold_word; both values in registers through the chains would spill). The channel words are loaded here, for the current item (pass 0 gathers
 // them as inputs anyway): they are first used after the output chains, so they need no one-item-ahead buffer.
 template <int D, bool GATHER, class Buf, int FC = 0, bool KEEP = false>
-__device__ __forceinline__ void cn_compute(const IbFastArgs& a, uint32_t lane4, uint32_t lane8c, const Buf& b,
+__device__ __forceinline__ void cn_compute(const IbFastArgs& a, uint32_t lane4, const Buf& b,
                                            int fslot, bool do_par, bool& unsat, uint8_t* fout = nullptr) {
   constexpr int W = Buf::W;
-  uint32_t outw[D][W], trow[D], cb[4];
+  uint32_t outw[D][W], trow[D];
   uint32_t chf[2][W] = {};
   if constexpr (FC != 0 && !GATHER) {
     if constexpr ((FC & 1) != 0) load_row<W>(a.ch8 + (size_t)b.fv0 * (uint32_t)a.ldb + b.off, chf[0]);
     if constexpr ((FC & 2) != 0) load_row<W>(a.ch8 + (size_t)b.fv1 * (uint32_t)a.ldb + b.off, chf[1]);
   }
-  col_bases(a.ccol[D], lane8c, cb);
 #pragma unroll
   for (int w = 0; w < D; ++w) trow[w] = __builtin_amdgcn_readlane(b.tgv, w);
   const uint32_t fbase = slot_off(fslot);
@@ -582,9 +507,9 @@ __device__ __forceinline__ void cn_compute(const IbFastArgs& a, uint32_t lane4, 
       }
     } else if constexpr (FC != 0 && !KEEP) {
       const uint32_t c0 = GATHER ? in[D - 2] : chf[0][i], c1 = GATHER ? in[D - 1] : chf[1][i];
-      cn_word_fold<D, FC>(lane4, in, fbase, cb, lane4 + slot_off(a.fold_slot), c0, c1, o);
+      cn_word_fold<D, FC>(lane4, in, fbase, lane4 + slot_off(a.fold_slot), c0, c1, o);
     } else {
-      cn_word<D, 8, kWordCT<D, Buf::kMax>>(lane4, in, fbase, cb, o);
+      cn_word<D, 8, kWordCT<D, Buf::kMax>>(lane4, in, fbase, o);
     }
 #pragma unroll
     for (int w = 0; w < D; ++w) outw[w][i] = o[w];
@@ -623,7 +548,7 @@ __device__ __forceinline__ void cn_compute(const IbFastArgs& a, uint32_t lane4, 
 
 // folding check pass: the item's class is wave-uniform (one check per item)
 template <int D, bool GATHER, bool KEEP, class Buf>
-__device__ __forceinline__ void cn_compute_fold(const IbFastArgs& a, uint32_t lane4, uint32_t lane8c, const Buf& b,
+__device__ __forceinline__ void cn_compute_fold(const IbFastArgs& a, uint32_t lane4, const Buf& b,
                                                 int fslot, bool do_par, bool& unsat) {
   if constexpr (D >= 3 && D <= 8) {
     // the next check inbox as an opaque scalar: the classes' store sequences differ only in their base
@@ -631,13 +556,13 @@ __device__ __forceinline__ void cn_compute_fold(const IbFastArgs& a, uint32_t la
     uint8_t* fout = a.fout;
     asm volatile("" : "+s"(fout));
     switch (b.fc) {
-      case 1: cn_compute<D, GATHER, Buf, 1, KEEP>(a, lane4, lane8c, b, fslot, do_par, unsat, fout); return;
-      case 2: cn_compute<D, GATHER, Buf, 2, KEEP>(a, lane4, lane8c, b, fslot, do_par, unsat, fout); return;
-      case 3: cn_compute<D, GATHER, Buf, 3, KEEP>(a, lane4, lane8c, b, fslot, do_par, unsat, fout); return;
+      case 1: cn_compute<D, GATHER, Buf, 1, KEEP>(a, lane4, b, fslot, do_par, unsat, fout); return;
+      case 2: cn_compute<D, GATHER, Buf, 2, KEEP>(a, lane4, b, fslot, do_par, unsat, fout); return;
+      case 3: cn_compute<D, GATHER, Buf, 3, KEEP>(a, lane4, b, fslot, do_par, unsat, fout); return;
       default: break;
     }
   }
-  cn_compute<D, GATHER>(a, lane4, lane8c, b, fslot, do_par, unsat);
+  cn_compute<D, GATHER>(a, lane4, b, fslot, do_par, unsat);
 }
 
 // ---------------------------------------------------------------- variable node
@@ -658,21 +583,20 @@ __device__ __forceinline__ void vn_word_ct(uint32_t lane4, const uint32_t (&in)[
 }
 template <int D, int NCW = 8, bool CT = false>
 __device__ __forceinline__ void vn_word(uint32_t lane4, const uint32_t (&in)[D], uint32_t chw,
-                                        uint32_t fbase, const uint32_t (&cb)[4], uint32_t (&outw)[D]) {
+                                        uint32_t fbase, uint32_t (&outw)[D]) {
   if constexpr (CT) {
     vn_word_ct<D, 0, NCW>(lane4, in, chw, fbase, outw);
   } else {
 #pragma unroll 1
-    for (int k0 = 0; k0 < NCW; k0 += vn_sched_s(D)) vn_group<D>(lane4, in, chw, fbase, cb, outw, k0);
+    for (int k0 = 0; k0 < NCW; k0 += vn_sched_s(D)) vn_group<D>(lane4, in, chw, fbase, outw, k0);
   }
 }
 
 template <int D, class Buf>
-__device__ __forceinline__ void vn_compute(const IbFastArgs& a, uint32_t lane4, uint32_t lane8c, const Buf& b,
+__device__ __forceinline__ void vn_compute(const IbFastArgs& a, uint32_t lane4, const Buf& b,
                                            int fslot) {
   constexpr int W = Buf::W;
-  uint32_t outw[D][W], trow[D], cb[4];
-  col_bases(a.ccol[D], lane8c, cb);
+  uint32_t outw[D][W], trow[D];
 #pragma unroll
   for (int w = 0; w < D; ++w) trow[w] = __builtin_amdgcn_readlane(b.tgv, w);
   const uint32_t fbase = slot_off(fslot);
@@ -688,7 +612,7 @@ __device__ __forceinline__ void vn_compute(const IbFastArgs& a, uint32_t lane4, 
         o[j] = 0;
       }
       // (the loop bodies: unrolled, the variable pass issued 12 % fewer VALU per lookup and was no faster)
-      vn_word<D>(lane4, in, b.chw[i], fbase, cb, o);
+      vn_word<D>(lane4, in, b.chw[i], fbase, o);
 #pragma unroll
       for (int w = 0; w < D; ++w) outw[w][i] = o[w];
     }
@@ -754,14 +678,13 @@ __device__ __forceinline__ void dec_item(const IbDecArgs& a, uint32_t lane4, int
 // light-first quarters of the block 0: VN 0.4825 ms / 170.4k cw/s, 1: 0.4709 / 171.5k, 2: 0.4703 / 171.8k,
 // 3: 0.4782 / 171.1k; round 5 (quad layout): 1 quarter best (IBL_MIX16 = 4).
 
-// LDS of the CN / VN kernels: [nt table quads (common.h layout)][ncs column images][2 work counters]
+// LDS of the CN / VN kernels: [nt table quads (common.h layout)][2 work counters]
 __device__ __forceinline__ int* lds_counters(const uint8_t* lds, const IbFastArgs& a) {
-  return reinterpret_cast<int*>(const_cast<uint8_t*>(lds) + lds_of_quads(a.nt) + (size_t)a.ncs * kColImg);
+  return reinterpret_cast<int*>(const_cast<uint8_t*>(lds) + lds_of_quads(a.nt));
 }
 __device__ __forceinline__ void stage_pass(uint8_t* lds, const IbFastArgs& a) {
   if (threadIdx.x < 2) lds_counters(lds, a)[threadIdx.x] = 0;
   stage_tables(lds, a.img, a.nt);
-  stage_cols(lds + lds_of_quads(a.nt), a.cimg, a.ncs);
 }
 
 // Persistent wave loop shared by the CN and VN passes: items (position, chunk) are dealt
@@ -777,7 +700,7 @@ __device__ __forceinline__ void stage_pass(uint8_t* lds, const IbFastArgs& a) {
 #define IBL_LIGHT_DEPTH 2
 #endif
 template <class Buf, bool VN, bool GATHER, int DLO, int DEPTH = 2, int FOLD = 0>
-__device__ __forceinline__ void ib_phase(const IbFastArgs& a, uint32_t lane4, uint32_t lane8c, int lane, int first,
+__device__ __forceinline__ void ib_phase(const IbFastArgs& a, uint32_t lane4, int lane, int first,
                                          int end, int nw, int wpb, int* ctr, bool do_par, bool& unsat,
                                          uint64_t* trace_items, const PhaseItems pi) {
   // always inlined: an out-of-line body would take the item by reference through scratch
@@ -785,8 +708,8 @@ __device__ __forceinline__ void ib_phase(const IbFastArgs& a, uint32_t lane4, ui
     settle<VN>(cur);
     if constexpr (VN) {
       switch (cur.d) {
-        case 1: if constexpr (DLO < 1) vn_compute<1>(a, lane4, lane8c, cur, 0); break;
-#define X(D) case D: if constexpr (D > DLO && D <= Buf::kMax) vn_compute<D>(a, lane4, lane8c, cur, a.fslot[D]); break;
+        case 1: if constexpr (DLO < 1) vn_compute<1>(a, lane4, cur, 0); break;
+#define X(D) case D: if constexpr (D > DLO && D <= Buf::kMax) vn_compute<D>(a, lane4, cur, a.fslot[D]); break;
         IBL_DEG_CASES(X)
 #undef X
         default: break;
@@ -794,8 +717,8 @@ __device__ __forceinline__ void ib_phase(const IbFastArgs& a, uint32_t lane4, ui
     } else {
       switch (cur.d) {
 #define X(D) case D: if constexpr (D > DLO && D <= Buf::kMax) { \
-          if constexpr (FOLD != 0) cn_compute_fold<D, GATHER, FOLD == 2>(a, lane4, lane8c, cur, a.fslot[D], do_par, unsat); \
-          else cn_compute<D, GATHER>(a, lane4, lane8c, cur, a.fslot[D], do_par, unsat); } break;
+          if constexpr (FOLD != 0) cn_compute_fold<D, GATHER, FOLD == 2>(a, lane4, cur, a.fslot[D], do_par, unsat); \
+          else cn_compute<D, GATHER>(a, lane4, cur, a.fslot[D], do_par, unsat); } break;
         IBL_DEG_CASES(X)
 #undef X
         default: break;
@@ -870,66 +793,6 @@ __device__ __forceinline__ void ib_phase(const IbFastArgs& a, uint32_t lane4, ui
   if (trace_items && lane == 0) *trace_items += (uint64_t)done;
 }
 
-// Variable pass, interleaved heavy / light items (IBL_VN_MIX3): every wave runs one heavy item
-// (degree > kLightD: LDS-lookup-bound) and two light items (HBM-bound) in turn, so each SIMD always holds both
-// kinds. Three buffers in rotation (one heavy, two light — DVB-S2 has 2 light items per heavy one: 51,840 light
-// nodes x 4 chunks of 2048 codewords against 12,960 heavy nodes x 8 chunks of 1024): the item computed next is
-// always the oldest in flight, so its wait leaves the other two buffers' loads outstanding. When one stream runs
-// out the wave computes the buffers it holds and finishes the other stream with the ping-pong phase.
-#ifndef IBL_VN_MIX3
-#define IBL_VN_MIX3 0
-#endif
-template <class BufH, class BufL>
-__device__ __forceinline__ void ib_phase_mix3(const IbFastArgs& a, uint32_t lane4, uint32_t lane8c, int lane, int hend,
-                                              int lend, int nw, int wpb, int* ctr, uint64_t* trace_items,
-                                              const PhaseItems pih, const PhaseItems pil) {
-  auto compute = [&](const auto& cur) __attribute__((always_inline)) {
-    using B = std::decay_t<decltype(cur)>;
-    settle<true>(cur);
-    switch (cur.d) {
-      case 1: if constexpr (B::kMax == kLightD) vn_compute<1>(a, lane4, lane8c, cur, 0); break;
-#define X(D) case D: if constexpr (D <= B::kMax && (B::kMax == kLightD || D > kLightD)) vn_compute<D>(a, lane4, lane8c, cur, a.fslot[D]); break;
-      IBL_DEG_CASES(X)
-#undef X
-      default: break;
-    }
-  };
-  const int hbase = (int)blockIdx.x * wpb, lbase = hend + (int)blockIdx.x * wpb;
-  auto hitem = [&](int k) { return hbase + (k % wpb) + nw * (k / wpb); };
-  auto litem = [&](int k) { return lbase + (k % wpb) + nw * (k / wpb); };
-  BufH h;
-  BufL l1, l2;
-  int ih = hitem(take_ticket(ctr, lane));
-  fetch_item<BufH, true, false>(a, min(ih, hend - 1), lane, h, pih);
-  int i1 = litem(take_ticket(ctr + 1, lane));
-  fetch_item<BufL, true, false>(a, min(i1, lend - 1), lane, l1, pil);
-  int i2 = litem(take_ticket(ctr + 1, lane));
-  fetch_item<BufL, true, false>(a, min(i2, lend - 1), lane, l2, pil);
-  int done = 0;
-  for (;;) {
-    if (ih >= hend || i1 >= lend || i2 >= lend) break;
-    compute(h);
-    ih = hitem(take_ticket(ctr, lane));
-    fetch_item<BufH, true, false>(a, min(ih, hend - 1), lane, h, pih);
-    compute(l1);
-    i1 = litem(take_ticket(ctr + 1, lane));
-    fetch_item<BufL, true, false>(a, min(i1, lend - 1), lane, l1, pil);
-    compute(l2);
-    i2 = litem(take_ticket(ctr + 1, lane));
-    fetch_item<BufL, true, false>(a, min(i2, lend - 1), lane, l2, pil);
-    done += 3;
-  }
-  // the valid items still held, then whatever is left of either stream
-  if (ih < hend) { compute(h); ++done; }
-  if (i1 < lend) { compute(l1); ++done; }
-  if (i2 < lend) { compute(l2); ++done; }
-  if (trace_items && lane == 0) *trace_items += (uint64_t)done;
-  bool unsat = false;
-  ib_phase<BufH, true, false, kLightD, 2>(a, lane4, lane8c, lane, 0, hend, nw, wpb, ctr, false, unsat, trace_items, pih);
-  ib_phase<BufL, true, false, 0, (IBL_LIGHT_DEPTH)>(a, lane4, lane8c, lane, hend, lend, nw, wpb, ctr + 1, false, unsat,
-                                                   trace_items, pil);
-}
-
 template <int MAXD, bool VN, bool GATHER, int FOLD = 0>
 __device__ __forceinline__ void ib_pass(const IbFastArgs& a, const uint8_t* lds) {
   const int lane = threadIdx.x & 63;
@@ -952,8 +815,6 @@ __device__ __forceinline__ void ib_pass(const IbFastArgs& a, const uint8_t* lds)
     *trace_items = (uint64_t)__smid() << 32;
   }
   int* ctr = lds_counters(lds, a);  // 2 phase counters
-  // column images follow the table quads (colf: cb = 8*(lane&31) + their base + 4 KiB per image)
-  const uint32_t lane8c = ((uint32_t)(lane & 31) << 3) + (uint32_t)lds_of_quads(a.nt);
   // Variable passes: heavy items (degree > kLightD) are bound by the LDS array, light ones (DVB-S2's
   // degree-2/3 variables, few lookups per byte moved) by HBM. The first IBL_MIX16 sixteenths of the
   // block's waves take the light share first, so both kinds run side by side on every CU; a wave that
@@ -966,22 +827,13 @@ __device__ __forceinline__ void ib_pass(const IbFastArgs& a, const uint8_t* lds)
 #define IBL_MIX16 6
 #endif
   const bool light_first = VN && (int)(threadIdx.x >> 6) * 16 < wpb * IBL_MIX16;
-  if constexpr (VN && MAXD <= 8 && IBL_VN_MIX3) {
-    if (a.n_heavy > 0 && a.n_heavy < a.n_nodes) {
-      ib_phase_mix3<ItemBuf<MAXD, W>, ItemBuf<kLightD, LW>>(a, lane4, lane8c, lane, heavy_end, nitems, nw, wpb, ctr,
-                                                            trace_items, PhaseItems{0, 0, a.nchunks},
-                                                            PhaseItems{heavy_end, a.n_heavy, nch_l});
-      if (a.trace && lane == 0) a.trace[3 * gw + 1] = __builtin_readcyclecounter();
-      return;
-    }
-  }
 #pragma unroll 1
   for (int r = 0; r < 2; ++r) {
     if ((r == 0) != light_first)
-      ib_phase<ItemBuf<MAXD, W>, VN, GATHER, kLightD, 2, FOLD>(a, lane4, lane8c, lane, 0, heavy_end, nw, wpb, ctr, do_par, unsat,
+      ib_phase<ItemBuf<MAXD, W>, VN, GATHER, kLightD, 2, FOLD>(a, lane4, lane, 0, heavy_end, nw, wpb, ctr, do_par, unsat,
                                                       trace_items, PhaseItems{0, 0, a.nchunks});
     else
-      ib_phase<ItemBuf<kLightD, LW>, VN, GATHER, 0, (VN ? IBL_LIGHT_DEPTH : 2), FOLD>(a, lane4, lane8c, lane, heavy_end, nitems, nw, wpb, ctr + 1, do_par,
+      ib_phase<ItemBuf<kLightD, LW>, VN, GATHER, 0, (VN ? IBL_LIGHT_DEPTH : 2), FOLD>(a, lane4, lane, heavy_end, nitems, nw, wpb, ctr + 1, do_par,
                                                    unsat, trace_items, PhaseItems{heavy_end, a.n_heavy, nch_l});
   }
   if (a.trace && lane == 0) {
@@ -1110,10 +962,9 @@ __device__ __forceinline__ void cn_small_item(const IbFastArgs& a, uint32_t lane
       o[1] = in[0];
     }
   } else {
-    const uint32_t cb[4] = {0, 0, 0, 0};   // no column-fetched inputs (the host requires ncs == 0)
     // a word with at most 4 codewords of the batch left (B = 2: every word) computes nibbles 0..3 only
-    if (a.B - 8 * c <= 4) cn_word<D, 4>(lane4, in, fbase, cb, o);
-    else cn_word<D>(lane4, in, fbase, cb, o);
+    if (a.B - 8 * c <= 4) cn_word<D, 4>(lane4, in, fbase, o);
+    else cn_word<D>(lane4, in, fbase, o);
   }
 #pragma unroll
   for (int w = 0; w < D; ++w) *reinterpret_cast<uint32_t*>(a.out + (size_t)tg[w] * a.ldb + off) = o[w];
@@ -1134,9 +985,8 @@ __device__ __forceinline__ void vn_small_item(const IbFastArgs& a, uint32_t lane
   if constexpr (D == 1) {
     o[0] = chw;   // degree 1 forwards the channel value (kernels_template_irreg.cl:131-136)
   } else {
-    const uint32_t cb[4] = {0, 0, 0, 0};
-    if (a.B - 8 * c <= 4) vn_word<D, 4>(lane4, in, chw, slot_off(a.fslot[D]), cb, o);
-    else vn_word<D>(lane4, in, chw, slot_off(a.fslot[D]), cb, o);
+    if (a.B - 8 * c <= 4) vn_word<D, 4>(lane4, in, chw, slot_off(a.fslot[D]), o);
+    else vn_word<D>(lane4, in, chw, slot_off(a.fslot[D]), o);
   }
 #pragma unroll
   for (int w = 0; w < D; ++w) *reinterpret_cast<uint32_t*>(a.out + (size_t)tg[w] * a.ldb + off) = o[w];
@@ -1147,9 +997,6 @@ __device__ __forceinline__ void vn_small_item(const IbFastArgs& a, uint32_t lane
 // record {first position, count, degree, contiguous} with contiguous = st0 + 1 says its nodes are
 // consecutive with edges st0 + k·d (every DVB-S2 task): the edge then needs no load, and the node (NODE:
 // variable passes) one scalar load per task instead of a vector load per lane after the record's.
-#ifndef IBL_SMALL_CONTIG
-#define IBL_SMALL_CONTIG 1   // 0: every lane loads its node record (A/B, tools/variants.py contig0)
-#endif
 template <bool NODE, class Args, class Body>
 __device__ __forceinline__ void small_items(const Args& a, int lane, Body&& body) {
   const int wpb = blockDim.x >> 6;
@@ -1159,7 +1006,7 @@ __device__ __forceinline__ void small_items(const Args& a, int lane, Body&& body
     const int t = __builtin_amdgcn_readfirstlane(item / a.nwords);
     const int c = __builtin_amdgcn_readfirstlane(item - t * a.nwords);
     const int p0 = sload(a.task, 4 * t), cnt = sload(a.task, 4 * t + 1), d = sload(a.task, 4 * t + 2);
-    const int st1 = IBL_SMALL_CONTIG ? sload(a.task, 4 * t + 3) : 0;
+    const int st1 = sload(a.task, 4 * t + 3);
     if (lane < cnt) {
       int node = 0, st;
       if (st1 != 0) {   // wave-uniform
@@ -1258,32 +1105,15 @@ __global__ __launch_bounds__(kSmallBlock) void ib_dec_small(IbDecArgs a) {
 // dword's 8 codewords unrolled (the per-pass kernels keep `unroll 1` for their register budget; the
 // heavier bodies would spill): 2-4x the independent lookup chains per wave,
 // which the phase-separated fused schedule needs to keep the LDS busy with 16 waves per CU.
-#ifndef IBL_FUSED_UNROLL
-#define IBL_FUSED_UNROLL 1
-#endif
 template <int D, int NCW>
 __device__ __forceinline__ void fused_cn_word(uint32_t lane4, const uint32_t (&in)[D], uint32_t fbase,
-                                              const uint32_t (&cb)[4], uint32_t (&o)[D]) {
-  if constexpr (IBL_FUSED_UNROLL && IBL_WORD_CT && D <= 6) {
-    cn_word<D, NCW, true>(lane4, in, fbase, cb, o);
-  } else if constexpr (IBL_FUSED_UNROLL && D <= 6) {
-#pragma unroll
-    for (int k0 = 0; k0 < NCW; k0 += cn_sched_s(D)) cn_group<D>(lane4, in, fbase, cb, o, k0);
-  } else {
-    cn_word<D, NCW>(lane4, in, fbase, cb, o);
-  }
+                                              uint32_t (&o)[D]) {
+  cn_word<D, NCW, D <= 6>(lane4, in, fbase, o);
 }
 template <int D, int NCW>
 __device__ __forceinline__ void fused_vn_word(uint32_t lane4, const uint32_t (&in)[D], uint32_t chw, uint32_t fbase,
-                                              const uint32_t (&cb)[4], uint32_t (&o)[D]) {
-  if constexpr (IBL_FUSED_UNROLL && IBL_WORD_CT && D <= 4) {
-    vn_word<D, NCW, true>(lane4, in, chw, fbase, cb, o);
-  } else if constexpr (IBL_FUSED_UNROLL && D <= 4) {
-#pragma unroll
-    for (int k0 = 0; k0 < NCW; k0 += vn_sched_s(D)) vn_group<D>(lane4, in, chw, fbase, cb, o, k0);
-  } else {
-    vn_word<D, NCW>(lane4, in, chw, fbase, cb, o);
-  }
+                                              uint32_t (&o)[D]) {
+  vn_word<D, NCW, D <= 4>(lane4, in, chw, fbase, o);
 }
 
 template <int D, int NCW>
@@ -1321,8 +1151,7 @@ __device__ __forceinline__ void fused_cn_dword(uint32_t* msg, int first, int cnt
       o[1] = in[0];
     }
   } else {
-    const uint32_t cb[4] = {0, 0, 0, 0};   // no column-fetched inputs (checked on the host: ncs == 0)
-    fused_cn_word<D, NCW>(lane4, in, fbase, cb, o);
+    fused_cn_word<D, NCW>(lane4, in, fbase, o);
   }
 #pragma unroll
   for (int j = 0; j < D; ++j) msg[first + j * cnt + lane] = o[j];
@@ -1377,8 +1206,7 @@ __device__ __forceinline__ void fused_vn_dword(uint32_t* msg, const VnTask<MAXD>
   if constexpr (D == 1) {
     o[0] = v.chw;     // degree 1 forwards the channel value (:131-136)
   } else {
-    const uint32_t cb[4] = {0, 0, 0, 0};
-    fused_vn_word<D, NCW>(lane4, in, v.chw, slot_off(a.vn_fslot[D]), cb, o);
+    fused_vn_word<D, NCW>(lane4, in, v.chw, slot_off(a.vn_fslot[D]), o);
   }
 #pragma unroll
   for (int k = 0; k < D; ++k) msg[v.sl[k]] = o[k];

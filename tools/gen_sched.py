@@ -14,31 +14,19 @@ after another. This script list-schedules the chains onto L concurrent lanes (cr
 and emits straight-line code with one SSA name per value (no register copies): each time step
 issues the lookups of every running lane for all S sub-slots back to back.
 
-Degree-2 variable fold (cn_group_fold<D, FC>, check degrees 3..8). The message of a degree-2 variable to
-one of its checks is F2(channel, message from its other check): one lookup on a value the check pass has
-just computed. The folding bodies append it to the chains of outputs D-2 / D-1 (bit 0 / 1 of the class
-FC) as one more link, t' = luc(t, q_ch, 0) with q_ch the v_perm_b32 column term of the variable's channel
-word (lane term = lane4c, which holds the slot of the transposed degree-2 table) - the price of any
-other lookup, taken while t is still alone in a register. The plain bodies are emitted unchanged.
+Degree-2 variable fold (the folding unrolled bodies cn_group_fold_ct, check degrees 3..8). The message of a
+degree-2 variable to one of its checks is F2(channel, message from its other check): one lookup on a value the
+check pass has just computed. The folding bodies append it to the chains of outputs D-2 / D-1 (bit 0 / 1 of the
+class FC) as one more link, t' = luc(t, q_ch, 0) with q_ch the v_perm_b32 column term of the variable's channel
+word (lane term = lane4c, which holds the slot of the transposed degree-2 table) - the price of any other lookup,
+taken while t is still alone in a register.
 
-Column fetches. Input in_j meets the SAME table in every chain that did not fold it into its
-prefix: B_{j-2}(., in_j) in the out0 chain and in chains w = 1..j-1 of a check node (j uses),
-V_{j-1}(., in_j) likewise for a variable node. For the last NC inputs of a node (cn_ncols(D) /
-vn_ncols(D) in common.h) the kernel reads that table's whole column T(., m = in_j) once - 16
-nibbles, one conflict-free ds_read_b64 of a bank-replicated column image - and selects entry t
-with a 64-bit shift by 4t (csel). Those j lookups then cost one LDS read instead of j (DVB-S2
-degree-7 check: 25 LDS reads -> 16; degree-8 variable: 35 -> 20), paid with one extra VALU per
-lookup; the LDS array, not VALU issue, is what bounds the byte-lookup kernels. Column steps come
-last in every chain (the NC inputs are the last ones folded), so a byte lookup never follows one.
+Column fetches (one ds_read_b64 of a table's whole column for the inputs that meet the same table in every chain)
+were measured on DVB-S2, B=8192, i_max=50, and lost: 170.9k -> 140.9k cw/s (CN 0.464 -> 0.622 ms, VN 0.478 -> 0.526
+ms). The code last stood in the parent of the commit that removed it (DESIGN.md "Retired experiment arms").
 
-Measured (tools/variants.py nc23/nc22/nc33/s2, DVB-S2 B=8192 i_max=50): column fetches LOSE - CN
-0.464 -> 0.622 ms, VN 0.478 -> 0.526 ms at NC = 2/3 (170.9k -> 140.9k cw/s). The 64-bit shift and the
-nibble masks cost more VALU issue than the saved LDS reads return, so the default is NC = 0 (no
-column images, the byte-lookup schedules of before); the option stays for other code profiles.
-
-usage: python tools/gen_sched.py [S_cn L_cn S_vn L_vn [NC_cn NC_vn]] > informationbottleneckdecodingldpc_amd/csrc/ib_sched.inc
-(measured on DVB-S2: CN S=4 L=2, VN S=2 L=4, NC 0 0; NC_cn / NC_vn must equal IBL_NC_CN / IBL_NC_VN
-of the build that includes the file - the file static_asserts it)
+usage: python tools/gen_sched.py [S_cn L_cn S_vn L_vn] > informationbottleneckdecodingldpc_amd/csrc/ib_sched.inc
+(measured on DVB-S2: CN S=4 L=2, VN S=2 L=4)
        python tools/gen_sched.py --unrolled [S_cn L_cn S_vn L_vn] > informationbottleneckdecodingldpc_amd/csrc/ib_unrolled.inc
 (the unrolled bodies of the degree <= 8 kernels, see "Unrolled bodies" below)
 """
@@ -49,14 +37,6 @@ KMAXD = 16
 
 def slot_off(l):   # csrc/common.h: quad l >> 2 in super-region l >> 3, half (l >> 2) & 1, byte l & 3
     return (l >> 3) * 65536 + ((l >> 2) & 1) * 128 + (l & 3)
-
-
-def cn_ncols(D, nc):
-    return nc if 5 <= D <= 8 else 0
-
-
-def vn_ncols(D, nc):
-    return nc if 6 <= D <= 8 else 0
 
 
 def cn_chains(D):
@@ -121,35 +101,17 @@ def schedule(chains, L):
     return out
 
 
-def emit_body(kind, D, S, L, NC, fold=False):
+def emit_body(kind, D, S, L):
     chains = cn_chains(D) if kind == "cn" else vn_chains(D)
     by_id = {c["id"]: c for c in chains}
     sched = schedule(chains, L)
-    back = 2 if kind == "cn" else 1          # input j meets table j-back in every non-prefix chain
-
-    def is_col(step):
-        op, j, _, l = step
-        return op == "q" and j >= D - NC and l == j - back
-
-    for c in chains:   # column steps are the tail of every chain
-        cols = [is_col(s) for s in c["steps"]]
-        assert cols == sorted(cols), (kind, D, c["id"])
-    lines = []
-    u8_in = sorted({s[1] for c in chains for s in c["steps"] if not is_col(s)})
-    col_in = sorted({s[1] for c in chains for s in c["steps"] if is_col(s)})
-    if D - 1 in u8_in:   # column base of the last input: final-table slot added once, not per codeword
-        lines.append("  const uint32_t lane4f = lane4 + fbase;")
+    # column base of the last input: final-table slot added once, not per codeword
+    lines = ["  const uint32_t lane4f = lane4 + fbase;"]
+    u8_in = sorted({s[1] for c in chains for s in c["steps"]})
     for j in u8_in:
         for s in range(S):
             base = "lane4f" if j == D - 1 else "lane4"
             lines.append(f"  const uint32_t q{j}_{s} = colq(in[{j}], k0 + {s}, {base});")
-    for j in col_in:
-        for s in range(S):
-            lines.append(f"  const uint64_t C{j}_{s} = colf(nib(in[{j}], k0 + {s}), cb[{j - (D - NC)}]);")
-    if fold:   # column terms of the two trailing variables' channel words (fold table slot in the lane term)
-        for a in range(2):
-            for s in range(S):
-                lines.append(f"  const uint32_t qc{a}_{s} = (FC & {1 << a}) ? colq(ch{a}, k0 + {s}, lane4c) : 0u;")
     if kind == "vn":   # channel nibble as a row term: luc merges it with a column term in one v_lshl_or
         for s in range(S):
             lines.append(f"  const uint32_t c_{s} = nib(chw, k0 + {s});")
@@ -169,84 +131,55 @@ def emit_body(kind, D, S, L, NC, fold=False):
         lines.append(f"  // step {t}: " + ", ".join(f"{cid}[{k}]" for cid, k in issued))
         for cid, k in issued:
             c = by_id[cid]
-            step = c["steps"][k]
-            op, j, sl, _ = step
+            op, j, sl, _ = c["steps"][k]
             for s in range(S):
                 if op == "c":
                     expr = f"luc(c_{s}, q{j}_{s}, {sl})"
                 else:
                     prev = start_val(c, s) if k == 0 else name(cid, k - 1, s)
-                    expr = f"csel(C{j}_{s}, {prev} << 2)" if is_col(step) else f"luc({prev}, q{j}_{s}, {sl})"
+                    expr = f"luc({prev}, q{j}_{s}, {sl})"
                 lines.append(f"  const uint32_t {name(cid, k, s)} = {expr};")
         for cid, k in issued:
             c = by_id[cid]
             if k == len(c["steps"]) - 1:
-                col = is_col(c["steps"][k])
-                vals = [f"({name(cid, k, s)} & 15u)" if col else name(cid, k, s) for s in range(S)]
-                a = c["out"] - (D - 2)
-                if fold and a >= 0:   # fold link: the degree-2 variable's update, F2(channel, this output)
-                    for s in range(S):
-                        lines.append(f"  const uint32_t f_{cid}_{s} = (FC & {1 << a}) ? luc({vals[s]}, qc{a}_{s}, 0u) : {vals[s]};")
-                    vals = [f"f_{cid}_{s}" for s in range(S)]
-                pk = vals[0]
+                pk = name(cid, k, 0)
                 for s in range(1, S):
-                    pk = f"{pk} | ({vals[s]} << {4 * s})"
+                    pk = f"{pk} | ({name(cid, k, s)} << {4 * s})"
                 lines.append(f"  o[{c['out']}] |= ({pk}) << (4 * k0);")
     return lines
 
 
 def main():
-    """args: S_cn L_cn [S_vn L_vn [NC_cn NC_vn]] (group size and chain lanes per kernel, for degrees
-    <= 8; larger degrees use S = 2, L = 4 so the MAXD = 16 bodies keep their occupancy; column-fetched
-    trailing inputs per check / variable node)."""
+    """args: S_cn L_cn [S_vn L_vn] (group size and chain lanes per kernel, for degrees <= 8; larger degrees
+    use S = 2, L = 4 so the MAXD = 16 bodies keep their occupancy)."""
     a = [int(x) for x in sys.argv[1:]] or [4, 2, 2, 4]
     Sc, Lc = a[0], a[1]
     Sv, Lv = (a[2], a[3]) if len(a) >= 4 else (Sc, Lc)
-    NCc, NCv = (a[4], a[5]) if len(a) >= 6 else (0, 0)
 
     def cfg(S, L, D):
         return (S, L) if D <= 8 else (2, 4)
     print(f"// GENERATED by tools/gen_sched.py {' '.join(sys.argv[1:])} -- do not edit.")
     print(f"// Fold schedules of the IB fast path (degrees <= 8): CN groups of {Sc} codewords with up to {Lc}")
     print(f"// chains in flight, VN groups of {Sv} codewords with up to {Lv}; degrees > 8: 2 codewords, 4 chains.")
-    print(f"// Column fetches: the last {NCc} inputs of checks of degree 5..8, the last {NCv} of variables of degree 6..8.")
-    print(f"static_assert(cn_ncols(7) == {cn_ncols(7, NCc)} && vn_ncols(8) == {vn_ncols(8, NCv)},")
-    print("              \"ib_sched.inc was generated for other IBL_NC_CN / IBL_NC_VN\");")
     print(f"__host__ __device__ constexpr int cn_sched_s(int D) {{ return D <= 8 ? {Sc} : 2; }}")
     print(f"__host__ __device__ constexpr int vn_sched_s(int D) {{ return D <= 8 ? {Sv} : 2; }}")
     print("template <int D> __device__ __forceinline__ void cn_group(uint32_t lane4, const uint32_t (&in)[D],")
-    print("                                                         uint32_t fbase, const uint32_t (&cb)[4],")
+    print("                                                         uint32_t fbase,")
     print("                                                         uint32_t (&o)[D], int k0);")
     print("template <int D> __device__ __forceinline__ void vn_group(uint32_t lane4, const uint32_t (&in)[D],")
-    print("                                                         uint32_t chw, uint32_t fbase, const uint32_t (&cb)[4],")
+    print("                                                         uint32_t chw, uint32_t fbase,")
     print("                                                         uint32_t (&o)[D], int k0);")
     for D in range(3, KMAXD + 1):
         print(f"template <> __device__ __forceinline__ void cn_group<{D}>(uint32_t lane4, const uint32_t (&in)[{D}],")
-        print("                                                         uint32_t fbase, const uint32_t (&cb)[4],")
+        print("                                                         uint32_t fbase,")
         print(f"                                                         uint32_t (&o)[{D}], int k0) {{")
-        print("\n".join(emit_body("cn", D, *cfg(Sc, Lc, D), cn_ncols(D, NCc))))
+        print("\n".join(emit_body("cn", D, *cfg(Sc, Lc, D))))
         print("}")
-    # Degree-2 variable fold (degrees 3..8): outputs D-2 / D-1 take one more link when bit 0 / 1 of FC is set,
-    # t' = T(t, channel) against the transposed degree-2 variable table at the slot held in lane4c.
-    fargs = ("uint32_t fbase, const uint32_t (&cb)[4], uint32_t lane4c, uint32_t ch0, uint32_t ch1,")
-    for D in range(3, 9):
-        print(f"template <int FC> __device__ __forceinline__ void cn_group_fold{D}(uint32_t lane4, const uint32_t (&in)[{D}],")
-        print(f"    {fargs}")
-        print(f"    uint32_t (&o)[{D}], int k0) {{")
-        print("\n".join(emit_body("cn", D, *cfg(Sc, Lc, D), cn_ncols(D, NCc), fold=True)))
-        print("}")
-    print("template <int D, int FC> __device__ __forceinline__ void cn_group_fold(uint32_t lane4, const uint32_t (&in)[D],")
-    print(f"    {fargs}")
-    print("    uint32_t (&o)[D], int k0) {")
-    print("  static_assert(D >= 3 && D <= 8, \"the fold exists for the degree <= 8 bodies\");")
-    for D in range(3, 9):
-        print(f"  if constexpr (D == {D}) cn_group_fold{D}<FC>(lane4, in, fbase, cb, lane4c, ch0, ch1, o, k0);")
-    print("}")
     for D in range(2, KMAXD + 1):
         print(f"template <> __device__ __forceinline__ void vn_group<{D}>(uint32_t lane4, const uint32_t (&in)[{D}],")
-        print("                                                         uint32_t chw, uint32_t fbase, const uint32_t (&cb)[4],")
+        print("                                                         uint32_t chw, uint32_t fbase,")
         print(f"                                                         uint32_t (&o)[{D}], int k0) {{")
-        print("\n".join(emit_body("vn", D, *cfg(Sv, Lv, D), vn_ncols(D, NCv))))
+        print("\n".join(emit_body("vn", D, *cfg(Sv, Lv, D))))
         print("}")
 
 
@@ -344,7 +277,7 @@ def main_unrolled(a):
     print(f"// GENERATED by tools/gen_sched.py {' '.join(['--unrolled', *map(str, a)])} -- do not edit.")
     print(f"// Unrolled fold schedules of the IB fast path, degrees <= 8 (see tools/gen_sched.py): CN groups of {Sc}")
     print(f"// codewords, {Lc} chains; VN groups of {Sv}, {Lv} chains. K0 = first codeword, ST = stride of the group.")
-    print(f"static_assert(cn_sched_s(8) == {Sc} && vn_sched_s(8) == {Sv} && cn_ncols(7) == 0 && vn_ncols(8) == 0,")
+    print(f"static_assert(cn_sched_s(8) == {Sc} && vn_sched_s(8) == {Sv},")
     print("              \"the unrolled bodies were generated for another schedule (IBL_UNROLLED_FILE)\");")
     cargs = "uint32_t lane4, const uint32_t (&in)[D], uint32_t fbase"
     # (the plain check bodies are the folding ones at FC = 0: cn_group_ct in ib_kernels.hip)
