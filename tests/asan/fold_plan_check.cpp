@@ -4,10 +4,12 @@
 //
 //   fold_plan_check <graph.bin>
 // graph.bin: int32 n_v, n_c, indptr[n_c + 1], cols[E] (canonical CSR of H). Checks the plan's invariants and
-// prints one JSON line {n_v, n_c, n_e, folded, rest, classes: [c0, c1, c2, c3], failures}. Exit status 0 = every
-// invariant held.
+// prints one JSON line {n_v, n_c, n_e, folded, rest, classes: [c0, c1, c2, c3], by_degree: {"D": [c0, c1, c2, c3],
+// ...} (the class counts of every check degree present), failures}. Exit status 0 = every invariant held.
+#include <array>
 #include <cstdio>
 #include <cstdlib>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -65,12 +67,14 @@ int main(int argc, char** argv) {
   // edge is folded in its own check with this edge as ITS other edge
   std::vector<int32_t> times((size_t)n_v, 0);
   long classes[4] = {0, 0, 0, 0};
+  std::map<int32_t, std::array<long, 4>> by_degree;
   for (int32_t c = 0; c < n_c; ++c) {
     const int32_t* r = &rec[(size_t)kIbFoldRec * c];
     const int32_t d = g.h_cn_deg[c], st = g.h_cn_start[c];
     CHECK(r[0] >= 0 && r[0] <= 3, "class range");
     if (r[0] < 0 || r[0] > 3) continue;
     ++classes[r[0]];
+    ++by_degree.try_emplace(d, std::array<long, 4>{0, 0, 0, 0}).first->second[r[0]];
     if (r[0]) CHECK(d >= 3, "a folding check has degree >= 3");
     for (int a = 0; a < 2; ++a) {
       if (d >= 2) CHECK(r[1 + a] == cols[(size_t)st + d - 2 + a], "channel row = the input's variable");
@@ -148,7 +152,14 @@ int main(int argc, char** argv) {
   CHECK(h == heavy, "heavy variables of the rest");
 
   std::printf("{\"n_v\": %d, \"n_c\": %d, \"n_e\": %lld, \"folded\": %d, \"rest\": %zu, "
-              "\"classes\": [%ld, %ld, %ld, %ld], \"failures\": %d}\n",
-              n_v, n_c, (long long)E, n, rest.size(), classes[0], classes[1], classes[2], classes[3], g_fail);
+              "\"classes\": [%ld, %ld, %ld, %ld], \"by_degree\": {",
+              n_v, n_c, (long long)E, n, rest.size(), classes[0], classes[1], classes[2], classes[3]);
+  const char* sep = "";
+  for (const auto& kv : by_degree) {
+    std::printf("%s\"%d\": [%ld, %ld, %ld, %ld]", sep, kv.first, kv.second[0], kv.second[1], kv.second[2],
+                kv.second[3]);
+    sep = ", ";
+  }
+  std::printf("}, \"failures\": %d}\n", g_fail);
   return g_fail ? 1 : 0;
 }
