@@ -253,6 +253,38 @@ int ibl_float_small_batch(const ibl_float* h, int32_t* max_b);
 int ibl_float_input_check(ibl_float* h, int32_t* violations, void* stream);
 int ibl_float_timing(ibl_float* h, int32_t enable);
 int ibl_float_timing_read(ibl_float* h, double* cn_ms, int32_t* cn_launches, double* vn_ms, int32_t* vn_launches);
+/*
+ * Corrected min-sum: normalised / offset min-sum on the flooding float decoder (no reference counterpart: the
+ * reference's min-sum is uncorrected).  A third arithmetic of ibl_float beside plain min-sum and BP, fixed when
+ * the decoder is created.  Let F be the decoder's precision (fp32 or fp64), a = (F)alpha and b = (F)beta, each
+ * converted once from the double arguments by round-to-nearest-even.  For check c and output edge w, over the
+ * inputs m_j of the other edges:
+ *   M   = min over j != w of |m_j|
+ *   s   = XOR over j != w of (m_j < 0)
+ *   t   = a * M          one rounded multiplication in F
+ *   u   = t - b          one rounded subtraction in F   (no fused multiply-add)
+ *   r   = max(u, 0)
+ *   out = s ? -r : r
+ * The sign of a zero result is not specified: a zero magnitude makes every sign that depends on it immaterial to
+ * any later value (sums take it as 0, minima as magnitude 0, and the syndrome is taken on < 0), and all
+ * comparisons are by value.  This closed form is the definition; the underflow caveat of plain min-sum's fold
+ * does not apply.  Everything else is the min-sum decoder above, operation for operation: the first send is the
+ * raw channel value; the variable update adds the channel first, then the ascending edges, and is clamped to
+ * +-llr_max; the APP output is unclamped; the syndrome is taken on < 0 of the variable-to-check messages;
+ * imax - 1 iterations run; the early stop is batch-global and d_iters is one word; the NaN precondition and
+ * +-inf channel values are handled as for min-sum (ibl_float_decode, ibl_float_input_check).
+ * Parameter domain: alpha finite with 0 < alpha <= 1, beta finite with beta >= 0, and the same of the converted
+ * values a and b (an alpha that rounds to 0 or a beta that rounds to infinity in an fp32 decoder is refused; beta =
+ * -0.0 is taken, and reported, as +0); anything else is IBL_EINVAL, reported (like imax, max_batch and precision
+ * errors) before a NULL graph is.  (1, 0) is plain min-sum: it
+ * creates the decoder ibl_float_create(IBL_MINSUM) creates, with the same kernels.  The handle is an ibl_float in
+ * every other respect (decode, paths, small batches, fold, input check, timing); two decoders with different
+ * corrections may coexist on one device.
+ * ibl_float_correction reports the pair: (1, 0) on plain min-sum handles, IBL_EINVAL on BP handles.
+ */
+int ibl_float_create_corrected(const ibl_graph* g, double alpha, double beta, int32_t imax, double llr_max,
+                               int32_t precision, int32_t max_batch, ibl_float** out);
+int ibl_float_correction(const ibl_float* h, double* alpha, double* beta);
 
 /*
  * Layered min-sum: layered (row-serial) normalised / offset min-sum decoding, fp32 (no reference counterpart:

@@ -33,6 +33,7 @@ EXPORTS = [
     "ibl_float_set_path", "ibl_float_path_in_use", "ibl_float_fused_geometry", "ibl_float_folded",
     "ibl_float_input_check",
     "ibl_float_set_small_batch", "ibl_float_small_batch",
+    "ibl_float_create_corrected", "ibl_float_correction",
     "ibl_ib_timing", "ibl_ib_timing_read", "ibl_float_timing", "ibl_float_timing_read",
     "ibl_channel_sample",
     "ibl_encoder_create",
@@ -102,6 +103,9 @@ def load():
     L.ibl_float_set_small_batch.argtypes = [_vp, _i32]
     L.ibl_float_small_batch.argtypes = [_vp, ctypes.POINTER(_i32)]
     L.ibl_float_input_check.argtypes = [_vp, ctypes.POINTER(_i32), _vp]
+    L.ibl_float_create_corrected.argtypes = [_vp, ctypes.c_double, ctypes.c_double, _i32, ctypes.c_double, _i32, _i32,
+                                             ctypes.POINTER(_vp)]
+    L.ibl_float_correction.argtypes = [_vp, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
     for nm in ("ibl_ib_timing", "ibl_float_timing"):
         getattr(L, nm).argtypes = [_vp, _i32]
     for nm in ("ibl_ib_timing_read", "ibl_float_timing_read"):

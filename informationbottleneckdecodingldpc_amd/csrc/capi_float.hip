@@ -7,6 +7,8 @@
 // iteration; the launches of the next iteration read those words and exit at once when they
 // are all zero, and a one-wave kernel turns the flags into the iteration index the output
 // pass uses.  The host only enqueues.
+#include <cmath>
+
 #include "host.h"
 
 using namespace ibl;
@@ -15,6 +17,10 @@ struct ibl_float {
   const ibl_graph* g = nullptr;
   int32_t kind = 0, imax = 0, prec = kF32, max_batch = 0, ldb = 0;
   double llr_max = 150.0;
+  // corrected min-sum (ibl_float_create_corrected): `kind` stays the public IBL_MINSUM (staging rule, messages);
+  // kkind is the check-body kind every launch, occupancy and private-segment query takes (0, 1 or 2)
+  int32_t kkind = 0;
+  double alpha = 1.0, beta = 0.0;
   DevBuf<uint8_t> cin, vbuf0, vbuf1, chf;   // inboxes and staged channel, fp32 or fp64 elements
   DevBuf<int32_t> flags, dL;
   int grid_cn = 0, grid_vn = 0;
@@ -59,7 +65,7 @@ int fused_setup(ibl_float* h) {
   const size_t lds = (size_t)(E + g->n_v) * 16 + 16 + ft.vn_slot.size() * 2;
   if (lds > (size_t)kLdsBytes) return IBL_OK;
   int bpc = 0, block = 0;
-  if (fl_fused_occupancy(h->kind, h->prec, g->dcm, g->dvm, lds, &bpc, &block) != hipSuccess || bpc < 1) {
+  if (fl_fused_occupancy(h->kkind, h->prec, g->dcm, g->dvm, lds, &bpc, &block) != hipSuccess || bpc < 1) {
     (void)hipGetLastError();
     return IBL_OK;
   }
@@ -109,11 +115,12 @@ int float_decode_fused(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32
   fa.ch = h->chf; fa.cn_task = h->ft.cn_task; fa.vn_task = h->ft.vn_task; fa.vn_node = h->ft.vn_node;
   fa.vn_slot = h->ft.vn_slot; fa.out = d_out; fa.unsat = flag_row(h->flags, early, 0); fa.dL = nullptr;
   fa.llr_max = h->llr_max; fa.n_e = (int32_t)g->n_e; fa.n_v = g->n_v; fa.n_cn_tasks = h->ft.n_cn;
+  fa.cor_a = h->alpha; fa.cor_b = h->beta;
   fa.n_vn_tasks = h->ft.n_vn; fa.n_vs = h->ft.n_vs; fa.ldb = h->ldb; fa.B = B; fa.imax = I; fa.out_dtype = out_dtype;
   int grid = 0;
   float_fused_geometry(h, B, &fa.ngroups, &grid);
   fa.aligned = out_aligned(B, d_out, cwl, out_dtype == kF32 ? 4 : 8);
-  auto launch = [&] { return launch_fl_fused(fa, h->kind, h->prec, g->dcm, g->dvm, grid, h->f_lds, s); };
+  auto launch = [&] { return launch_fl_fused(fa, h->kkind, h->prec, g->dcm, g->dvm, grid, h->f_lds, s); };
 #if IBL_DIAG
   const char* ftrace = getenv("IBL_TRACE_FUSED");   // diagnostic builds: phase clocks of block 0's first group
   TraceBuf tr;
@@ -159,6 +166,7 @@ int float_decode_small(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32
   cn.info = g->cn_info; cn.task = g->cn_task; cn.n_tasks = g->n_cn_task;
   vn.info = g->vn_info; vn.task = g->vn_task; vn.n_tasks = g->n_vn_task;
   cn.llr_max = vn.llr_max = h->llr_max;
+  cn.cor_a = h->alpha; cn.cor_b = h->beta;
   cn.n_nodes = g->n_c; vn.n_nodes = g->n_v;
   cn.nwords = vn.nwords = nwords;
   cn.ldb = vn.ldb = ldbs;
@@ -174,7 +182,7 @@ int float_decode_small(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32
       c.out = vb;
       c.gate = flag_row(h->flags, early && j >= 3, j - 2);
       c.unsat = flag_row(h->flags, early, j - 1);
-      if ((e = h->timer.timed(0, st, [&] { return launch_fl_cn_small(c, h->kind, h->prec, g->dcm, gcn, st); })) != hipSuccess)
+      if ((e = h->timer.timed(0, st, [&] { return launch_fl_cn_small(c, h->kkind, h->prec, g->dcm, gcn, st); })) != hipSuccess)
         return e;
       if (j == I - 1) break;   // the last variable pass feeds no output (as in float_decode_passes)
       v.in = vb;
@@ -220,6 +228,7 @@ int float_decode_passes(ibl_float* h, const void* d_llr, int32_t llr_dtype, int3
   vn.ch = h->chf; vn.start = g->vn_start; vn.deg = g->vn_deg; vn.tgt = g->tgt_vn;
   vn.nodes = fold ? h->vn_nodes.get() : nullptr;
   cn.llr_max = vn.llr_max = h->llr_max;
+  cn.cor_a = h->alpha; cn.cor_b = h->beta;
   cn.n_nodes = g->n_c; vn.n_nodes = fold ? h->n_vn_nodes : g->n_v;
   cn.nchunks = nchunks;
   vn.nchunks = (B + fl_vn_chunk(h->prec, g->dvm) - 1) / fl_vn_chunk(h->prec, g->dvm);
@@ -234,7 +243,7 @@ int float_decode_passes(ibl_float* h, const void* d_llr, int32_t llr_dtype, int3
     cn.fold_mode = (fold && !last) ? (early ? 2 : 1) : 0;
     cn.gate = flag_row(h->flags, early && j >= 3, j - 2);
     cn.unsat = flag_row(h->flags, early, j - 1);
-    HIPCHK(h->timer.timed(0, s, [&] { return launch_fl_cn(cn, h->kind, h->prec, g->dcm, h->grid_cn, s); }));
+    HIPCHK(h->timer.timed(0, s, [&] { return launch_fl_cn(cn, h->kkind, h->prec, g->dcm, h->grid_cn, s); }));
     if (last) break;
     vn.in = vb;
     vn.out = cb[(j + 1) & 1];
@@ -249,6 +258,59 @@ int float_decode_passes(ibl_float* h, const void* d_llr, int32_t llr_dtype, int3
   dc.aligned = out_aligned(B, d_out, cwl, out_dtype == kF32 ? 4 : 8);
   const size_t items = (size_t)g->n_v * nchunks;
   HIPCHK(launch_fl_dec(dc, h->prec, (int)std::min<size_t>((items + 3) / 4, 65536), s));
+  return IBL_OK;
+}
+
+// The decoder behind ibl_float_create and ibl_float_create_corrected (parameters checked by the callers). kkind is
+// the check-body kind of the kernels: `kind`, or 2 for corrected min-sum with (alpha, beta) != (1, 0).
+int float_create(const ibl_graph* g, int32_t kind, int32_t kkind, double alpha, double beta, int32_t imax,
+                 double llr_max, int32_t precision, int32_t max_batch, ibl_float** out) {
+  if (g->dcm > kMaxD || g->dvm > kMaxD) return fail(IBL_EUNSUPPORTED, "float decoders support node degrees <= 16");
+  HIPCHK(hipSetDevice(g->device));
+  std::unique_ptr<ibl_float> h(new ibl_float());
+  h->g = g; h->kind = kind; h->imax = imax; h->prec = precision; h->max_batch = max_batch; h->llr_max = llr_max;
+  h->kkind = kkind; h->alpha = alpha; h->beta = beta;
+  // rows padded to the wave item of the per-pass kernels (fp32 256 / fp64 128 codewords), not beyond: the
+  // reference's DVB-S2 driver decodes msg_at_time = 2 in fp64
+  const int pad = fl_vn_chunk(precision, g->dvm);
+  h->ldb = (max_batch + pad - 1) / pad * pad;
+  const size_t es = precision == kF32 ? 4 : 8;
+  const size_t inbox = (size_t)g->n_e * h->ldb * es;
+  int rc;
+  if ((rc = h->cin.alloc_zero(inbox)) || (rc = h->vbuf0.alloc_zero(inbox)) || (rc = h->vbuf1.alloc_zero(inbox)) ||
+      (rc = h->chf.alloc((size_t)g->n_v * h->ldb * es)) || (rc = h->flags.alloc((size_t)imax * kShards)) ||
+      (rc = h->dL.alloc(1)) || (rc = h->bad.alloc_zero(1)))
+    return rc;
+  int bpc = 0;
+  // at most 16 waves per CU: with a second block per CU its waves issue behind the first block's
+  // (oldest-first) and the per-block work counters cannot rebalance across blocks
+  if (fl_occupancy(0, kkind, precision, g->dcm, &bpc) != hipSuccess || bpc < 1) bpc = 1;
+  // (A/B knob, read once here: IBL_FL_WAVES = waves per CU the per-pass grids may fill, default 16)
+  const char* fw = getenv("IBL_FL_WAVES");
+  const int wcap = std::max(16, fw ? atoi(fw) : 16) * 64;
+  h->grid_cn = std::min(bpc, wcap / fl_block(0, kkind, precision, g->dcm)) * g->num_cus;
+  if (fl_occupancy(1, kkind, precision, g->dvm, &bpc) != hipSuccess || bpc < 1) bpc = 1;
+  h->grid_vn = std::min(bpc, wcap / fl_block(1, kkind, precision, g->dvm)) * g->num_cus;
+  if ((rc = fused_setup(h.get()))) return rc;
+  // degree-2 variable fold of the per-pass path (IBL_FL_FOLD=0 at create turns it off: A/B); its second check
+  // inbox is allocated only once some batch can reach the per-pass kernels (max_batch > small_b, fold_alloc)
+  if (env_on("IBL_FL_FOLD") && (h->n_folded = plan_fold(*g, &h->fold_rec, &h->fold_rest)) > 0)
+    h->n_vn_nodes = (int32_t)h->fold_rest.size();
+  else
+    h->n_folded = 0;
+  // same guard as the IB fast path: the float kernels are built to run without scratch
+  size_t priv = 0;
+  const char* kname = "";
+  HIPCHK(fl_private_bytes(kkind, precision, g->dcm, g->dvm, h->fused_ok, &priv, &kname));
+  if ((rc = refuse_private(priv, std::string("float kernel ") + kname + " has a ",
+                           "-byte private segment (register spill): rebuild required")))
+    return rc;
+  // small-batch kernels (IBL_SMALL_B at create overrides the default; off if they would need scratch)
+  HIPCHK(fl_small_private_bytes(kkind, precision, g->dcm, g->dvm, &priv, &kname));
+  h->s_ok = priv == 0;
+  small_batch_env(h->s_ok, kFlSmallBatchDefault, &h->small_b, &h->s_graphs);
+  if ((rc = fold_alloc(h.get()))) return rc;
+  *out = h.release();
   return IBL_OK;
 }
 }  // namespace
@@ -336,51 +398,35 @@ int ibl_float_create(const ibl_graph* g, int32_t kind, int32_t imax, double llr_
   if (kind != IBL_MINSUM && kind != IBL_BP) return fail(IBL_EINVAL, "kind must be IBL_MINSUM or IBL_BP");
   if (precision != kF32 && precision != kF64) return fail(IBL_EINVAL, "precision must be IBL_F32 or IBL_F64");
   if (imax < 1 || max_batch < 1) return fail(IBL_EINVAL, "imax and max_batch must be >= 1");
-  if (g->dcm > kMaxD || g->dvm > kMaxD) return fail(IBL_EUNSUPPORTED, "float decoders support node degrees <= 16");
-  HIPCHK(hipSetDevice(g->device));
-  std::unique_ptr<ibl_float> h(new ibl_float());
-  h->g = g; h->kind = kind; h->imax = imax; h->prec = precision; h->max_batch = max_batch; h->llr_max = llr_max;
-  // rows padded to the wave item of the per-pass kernels (fp32 256 / fp64 128 codewords), not beyond: the
-  // reference's DVB-S2 driver decodes msg_at_time = 2 in fp64
-  const int pad = fl_vn_chunk(precision, g->dvm);
-  h->ldb = (max_batch + pad - 1) / pad * pad;
-  const size_t es = precision == kF32 ? 4 : 8;
-  const size_t inbox = (size_t)g->n_e * h->ldb * es;
-  int rc;
-  if ((rc = h->cin.alloc_zero(inbox)) || (rc = h->vbuf0.alloc_zero(inbox)) || (rc = h->vbuf1.alloc_zero(inbox)) ||
-      (rc = h->chf.alloc((size_t)g->n_v * h->ldb * es)) || (rc = h->flags.alloc((size_t)imax * kShards)) ||
-      (rc = h->dL.alloc(1)) || (rc = h->bad.alloc_zero(1)))
-    return rc;
-  int bpc = 0;
-  // at most 16 waves per CU: with a second block per CU its waves issue behind the first block's
-  // (oldest-first) and the per-block work counters cannot rebalance across blocks
-  if (fl_occupancy(0, kind, precision, g->dcm, &bpc) != hipSuccess || bpc < 1) bpc = 1;
-  // (A/B knob, read once here: IBL_FL_WAVES = waves per CU the per-pass grids may fill, default 16)
-  const char* fw = getenv("IBL_FL_WAVES");
-  const int wcap = std::max(16, fw ? atoi(fw) : 16) * 64;
-  h->grid_cn = std::min(bpc, wcap / fl_block(0, kind, precision, g->dcm)) * g->num_cus;
-  if (fl_occupancy(1, kind, precision, g->dvm, &bpc) != hipSuccess || bpc < 1) bpc = 1;
-  h->grid_vn = std::min(bpc, wcap / fl_block(1, kind, precision, g->dvm)) * g->num_cus;
-  if ((rc = fused_setup(h.get()))) return rc;
-  // degree-2 variable fold of the per-pass path (IBL_FL_FOLD=0 at create turns it off: A/B); its second check
-  // inbox is allocated only once some batch can reach the per-pass kernels (max_batch > small_b, fold_alloc)
-  if (env_on("IBL_FL_FOLD") && (h->n_folded = plan_fold(*g, &h->fold_rec, &h->fold_rest)) > 0)
-    h->n_vn_nodes = (int32_t)h->fold_rest.size();
-  else
-    h->n_folded = 0;
-  // same guard as the IB fast path: the float kernels are built to run without scratch
-  size_t priv = 0;
-  const char* kname = "";
-  HIPCHK(fl_private_bytes(kind, precision, g->dcm, g->dvm, h->fused_ok, &priv, &kname));
-  if ((rc = refuse_private(priv, std::string("float kernel ") + kname + " has a ",
-                           "-byte private segment (register spill): rebuild required")))
-    return rc;
-  // small-batch kernels (IBL_SMALL_B at create overrides the default; off if they would need scratch)
-  HIPCHK(fl_small_private_bytes(kind, precision, g->dcm, g->dvm, &priv, &kname));
-  h->s_ok = priv == 0;
-  small_batch_env(h->s_ok, kFlSmallBatchDefault, &h->small_b, &h->s_graphs);
-  if ((rc = fold_alloc(h.get()))) return rc;
-  *out = h.release();
+  return float_create(g, kind, kind, 1.0, 0.0, imax, llr_max, precision, max_batch, out);
+}
+
+int ibl_float_create_corrected(const ibl_graph* g, double alpha, double beta, int32_t imax, double llr_max,
+                               int32_t precision, int32_t max_batch, ibl_float** out) {
+  if (!out) return fail(IBL_EINVAL, "out is NULL");
+  *out = nullptr;
+  // parameter errors before the NULL graph (as ibl_layered_create_fixed): they need no device
+  if (!std::isfinite(alpha) || !(alpha > 0.0) || alpha > 1.0) return fail(IBL_EINVAL, "alpha must be finite with 0 < alpha <= 1");
+  if (!std::isfinite(beta) || beta < 0.0) return fail(IBL_EINVAL, "beta must be finite and >= 0");
+  if (precision != kF32 && precision != kF64) return fail(IBL_EINVAL, "precision must be IBL_F32 or IBL_F64");
+  // the domain holds for a = (F)alpha and b = (F)beta, the values the kernels compute with: an alpha that rounds
+  // to 0 in fp32 would zero every check message, a beta that rounds to inf every nonzero one
+  if (precision == kF32 && (!((float)alpha > 0.f) || !std::isfinite((float)beta)))
+    return fail(IBL_EINVAL, !((float)alpha > 0.f) ? "alpha rounds to 0 in fp32: (float)alpha must be > 0"
+                                                  : "beta rounds to infinity in fp32: (float)beta must be finite");
+  beta += 0.0;   // -0.0 is 0: stored, used and reported as +0
+  if (imax < 1 || max_batch < 1) return fail(IBL_EINVAL, "imax and max_batch must be >= 1");
+  if (!g) return fail(IBL_EINVAL, "graph is NULL");
+  // (1, 0) is plain min-sum: the decoder ibl_float_create(IBL_MINSUM) makes, with its kernels
+  const bool plain = alpha == 1.0 && beta == 0.0;
+  return float_create(g, IBL_MINSUM, plain ? 0 : 2, alpha, beta, imax, llr_max, precision, max_batch, out);
+}
+
+int ibl_float_correction(const ibl_float* h, double* alpha, double* beta) {
+  if (!h || !alpha || !beta) return fail(IBL_EINVAL, "NULL argument");
+  if (h->kind != IBL_MINSUM) return fail(IBL_EINVAL, "a BP decoder has no min-sum correction");
+  *alpha = h->alpha;
+  *beta = h->beta;
   return IBL_OK;
 }
 

@@ -203,6 +203,9 @@ struct FlArgs {
   const int32_t* info;
   const int32_t* task;
   int32_t n_tasks, nwords;
+  // corrected min-sum (check-body kind 2, ibldpc.h "Corrected min-sum"): alpha and beta, converted to F by the
+  // kernel; the other kinds never read them. Last, so that no earlier member's offset moves.
+  double cor_a, cor_b;
 };
 
 // Fused float decoder: a workgroup keeps Vec<F>::N codewords (one 16-byte slot per edge) entirely
@@ -227,6 +230,7 @@ struct FlFusedArgs {
   int32_t n_vs;             // variable-edge slot indices (vn_slot), each task's rows padded to 64 lanes
   uint64_t* trace;          // diagnostics (IBL_TRACE_FUSED, -DIBL_FUSED_TRACE=1 builds): block 0's clock at
                             // every phase end of its first group, else nullptr
+  double cor_a, cor_b;      // corrected min-sum (kind 2): alpha and beta, as FlArgs'
 };
 
 struct FlDecArgs {

@@ -228,13 +228,77 @@ __device__ __forceinline__ bool syndrome_bit(const F (&m)[D][NC], int s) {
   }
 }
 
-// Check-node body on the inputs m of NC codewords (min-sum or BP); put(w, o) receives output w (any
-// order of w).
+// Check-body kinds: the public IBL_MINSUM (0) and IBL_BP (1), and the library's own corrected min-sum.
+constexpr int kFlCorrected = 2;
+
+// Corrected min-sum magnitude (ibldpc.h "Corrected min-sum"): r = max(a * M - b, 0) as one rounded
+// multiplication and one rounded subtraction. HIP contracts a * M - b into a fused multiply-add by default,
+// which rounds once: contraction is off for these two operations only (the rest of this source keeps it).
+template <typename F>
+__device__ __forceinline__ F fl_corrected(F M, F a, F b) {
+#pragma clang fp contract(off)
+  const F t = a * M;
+  const F u = t - b;
+  return fmax(u, F(0));
+}
+
+// alpha and beta of the corrected kind from the kernel arguments (FlArgs / FlFusedArgs); the other kinds
+// read neither
+template <int KIND, typename F, class Args>
+__device__ __forceinline__ void fl_correction(const Args& a, F& ca, F& cb) {
+  if constexpr (KIND == kFlCorrected) {
+    ca = (F)a.cor_a;
+    cb = (F)a.cor_b;
+  } else {
+    ca = F(1);
+    cb = F(0);
+  }
+}
+
+// Check-node body on the inputs m of NC codewords (min-sum, BP or corrected min-sum with alpha ca and
+// beta cb); put(w, o) receives output w (any order of w).
 template <int KIND, typename F, int D, int NC, class Put>
-__device__ __forceinline__ void fl_cn_body(const F (&m)[D][NC], F lm, Put&& put) {
+__device__ __forceinline__ void fl_cn_body(const F (&m)[D][NC], F lm, F ca, F cb, Put&& put) {
   constexpr int N = NC;
   F o[N];
-  if constexpr (KIND == 0 && D <= 8) {
+  if constexpr (KIND == kFlCorrected) {
+    // corrected min-sum: the running (min, second min) pair of |m| as the degree > 8 body below, then the
+    // correction on those two values only (2 x {mul, sub, max} per check and codeword, whatever the degree;
+    // correcting the prefix / suffix form's outputs would cost 3 per edge). Output w takes the corrected
+    // second minimum where |m_w| is the minimum (on a tie both are equal) and the corrected minimum
+    // elsewhere: the closed form of the specification, since the correction is a function of the magnitude
+    // alone. r >= +0, so OR-ing the sign bit negates it; the sign of a zero is not specified. Per edge:
+    // 2 (running pair) + 1 (sign XOR) + 4 (compare, select, XOR, and-or), plus 6 per check (2 x {mul, sub, max}).
+    using Bt = Bits<F>;
+    using U = typename Bt::U;
+    F mn1[N], r1[N], r2[N];
+    U sg[N];
+    const U ks = Bt::sign_mask();
+#pragma unroll
+    for (int s = 0; s < N; ++s) {
+      F mn2 = Bt::hi_aa(m[0][s], m[1][s]);
+      mn1[s] = Bt::lo_aa(m[0][s], m[1][s]);
+      sg[s] = sign_xor<F, D>(m, s);
+#pragma unroll
+      for (int j = 2; j < D; ++j) {
+        mn2 = Bt::med3_a(mn1[s], mn2, m[j][s]);
+        mn1[s] = Bt::lo_a(mn1[s], m[j][s]);
+      }
+      r1[s] = fl_corrected(mn1[s], ca, cb);
+      r2[s] = fl_corrected(mn2, ca, cb);
+    }
+#pragma unroll
+    for (int w = 0; w < D; ++w) {
+#pragma unroll
+      for (int s = 0; s < N; ++s) {
+        const F mag = (fabs(m[w][s]) == mn1[s]) ? r2[s] : r1[s];
+        const U sx = sg[s] ^ Bt::of(m[w][s]);
+        // one v_and_or_b32 for degrees <= 8, the compiler's form above (as the plain degree > 8 body)
+        o[s] = Bt::from(D <= 8 ? Bt::and_or(sx, ks, Bt::of(mag)) : (sx & Bt::kSign) | Bt::of(mag));
+      }
+      put(w, o);
+    }
+  } else if constexpr (KIND == 0 && D <= 8) {
     // min-sum (kernels_min_and_BP.cl:156-162) with prefix / suffix minima: |out_w| = min over the others =
     // min(P_w, S_{w+1}), P_w = min |m_0..m_{w-1}|, S_j = min |m_j..m_{D-1}| — 3(D-2) v_min (|x| as an input
     // modifier) instead of the running (min, second min) pair plus a compare and a select per output
@@ -432,7 +496,10 @@ __device__ __forceinline__ void fl_cn_item(const FlArgs& a, int node, int st, in
     else fl_store<F>(a, tg[w], cw0, o);
   };
   FlOut<F, D> ob;
-  fl_cn_body<KIND, F, D>(m, lm, [&](int w, const F (&o)[N]) __attribute__((always_inline)) { ob.put(w, o, sink); });
+  F ca, cb;
+  fl_correction<KIND, F>(a, ca, cb);
+  fl_cn_body<KIND, F, D>(m, lm, ca, cb,
+                         [&](int w, const F (&o)[N]) __attribute__((always_inline)) { ob.put(w, o, sink); });
   ob.flush(sink);
 }
 
@@ -508,10 +575,11 @@ int fl_vn_chunk(int prec, int maxd) { return 64 * (prec == kF32 ? 4 : 2); }
 // 1024-thread blocks so a CU's waves share one work counter, except where the body needs more than
 // the 128 VGPRs such a block allows: the box-plus check node at MAXD=16 or in fp64, and the per-pass
 // fp32 min-sum check node at MAXD=16 (512 threads). The fused kernel keeps 1024 threads (its min-sum
-// MAXD=16 body fits in 128 VGPRs; 16 waves share the phases).
+// MAXD=16 body fits in 128 VGPRs; 16 waves share the phases). Corrected min-sum (kind 2) takes plain
+// min-sum's block sizes here and in the fused kernel: its bodies need no private segment at either.
 template <int WHICH, int MAXD, int KIND = 0, typename F = float>
 constexpr int fl_block_of() {
-  return (WHICH == 0 && ((KIND == 1 && (MAXD > 8 || sizeof(F) == 8)) || (KIND == 0 && MAXD > 8 && sizeof(F) == 4)))
+  return (WHICH == 0 && ((KIND == 1 && (MAXD > 8 || sizeof(F) == 8)) || (KIND != 1 && MAXD > 8 && sizeof(F) == 4)))
              ? 512 : 1024;
 }
 // fused kernel: 1024 threads (16 waves share the phases) unless the check bodies need more than 128 VGPRs
@@ -851,7 +919,9 @@ __device__ __forceinline__ void fl_cn_small_item(const FlArgs& a, int st, int cw
 #pragma unroll
     for (int s = 0; s < Vec<F>::N; ++s) unsat |= syndrome_bit<F, D>(m, s) && s < valid;
   }
-  fl_cn_body<KIND, F, D>(m, lm, [&](int w, const F (&o)[Vec<F>::N]) __attribute__((always_inline)) {
+  F ca, cb;
+  fl_correction<KIND, F>(a, ca, cb);
+  fl_cn_body<KIND, F, D>(m, lm, ca, cb, [&](int w, const F (&o)[Vec<F>::N]) __attribute__((always_inline)) {
     fl_store_to<F>(a.out, a.ldb, tg[w], cw0, o);
   });
 }
@@ -974,7 +1044,7 @@ __device__ __forceinline__ void slice_store(void* base, int slot, int h, const F
 }
 
 template <int KIND, typename F, int D, int NC, int CNT = 0>
-__device__ __forceinline__ void fused_cn_item(void* msg, int first, int cnt_, int lane, int h, F lm,
+__device__ __forceinline__ void fused_cn_item(void* msg, int first, int cnt_, int lane, int h, F lm, F ca, F cb,
                                               bool do_par, int valid, bool& unsat) {
   // CNT > 0: a full task (CNT nodes) — the edge stride is a constant, so one address register serves all
   // D loads and stores through their immediate offsets
@@ -986,7 +1056,7 @@ __device__ __forceinline__ void fused_cn_item(void* msg, int first, int cnt_, in
 #pragma unroll
     for (int s = 0; s < NC; ++s) unsat |= syndrome_bit<F, D>(m, s) && h * NC + s < valid;
   }
-  fl_cn_body<KIND, F, D>(m, lm, [&](int w, const F (&o)[NC]) __attribute__((always_inline)) {
+  fl_cn_body<KIND, F, D>(m, lm, ca, cb, [&](int w, const F (&o)[NC]) __attribute__((always_inline)) {
     slice_store<F, NC>(msg, first + w * cnt + lane, h, o);
   });
 }
@@ -1025,6 +1095,8 @@ __global__ __launch_bounds__((fl_fused_block_of<CMAX, KIND, F>())) void fl_fused
   int* ctr = reinterpret_cast<int*>(chL + a.n_v);
   const int lane = fl_tid() & 63;
   const F lm = (F)a.llr_max;
+  F ca, cb;
+  fl_correction<KIND, F>(a, ca, cb);
   int L = a.imax - 1;
   if (a.dL) {
     L = __builtin_amdgcn_readfirstlane(*a.dL);
@@ -1064,14 +1136,14 @@ __global__ __launch_bounds__((fl_fused_block_of<CMAX, KIND, F>())) void fl_fused
     // tasks of larger degrees take the general branch below (every lane < cnt = 64)
     if (cnt == 64 && d <= 8) {
       switch (d) {
-#define X(D) case D: if constexpr (D <= CMAX && D <= 8) fused_cn_item<KIND, F, D, NCs, 64>(msg, first, cnt, lane, h, lm, do_par, valid, unsat); break;
+#define X(D) case D: if constexpr (D <= CMAX && D <= 8) fused_cn_item<KIND, F, D, NCs, 64>(msg, first, cnt, lane, h, lm, ca, cb, do_par, valid, unsat); break;
         FL_DEG_CASES(X)
 #undef X
         default: break;
       }
     } else if (lane < cnt) {
       switch (d) {
-#define X(D) case D: if constexpr (D <= CMAX) fused_cn_item<KIND, F, D, NCs>(msg, first, cnt, lane, h, lm, do_par, valid, unsat); break;
+#define X(D) case D: if constexpr (D <= CMAX) fused_cn_item<KIND, F, D, NCs>(msg, first, cnt, lane, h, lm, ca, cb, do_par, valid, unsat); break;
         FL_DEG_CASES(X)
 #undef X
         default: break;
@@ -1226,6 +1298,9 @@ hipError_t launch_fl_send(const FlArgs& a, int prec, hipStream_t s) {
 static const void* fl_kernel(int which, int kind, int prec, int maxd) {
   const bool f32 = prec == kF32, small = maxd <= 8;
   if (which == 0) {
+    if (kind == kFlCorrected)
+      return f32 ? (small ? (const void*)fl_cn<2, float, 8> : (const void*)fl_cn<2, float, 16>)
+                 : (small ? (const void*)fl_cn<2, double, 8> : (const void*)fl_cn<2, double, 16>);
     if (kind == 0)
       return f32 ? (small ? (const void*)fl_cn<0, float, 8> : (const void*)fl_cn<0, float, 16>)
                  : (small ? (const void*)fl_cn<0, double, 8> : (const void*)fl_cn<0, double, 16>);
@@ -1238,7 +1313,7 @@ static const void* fl_kernel(int which, int kind, int prec, int maxd) {
 
 int fl_block(int which, int kind, int prec, int maxd) {
   if (which == 0 && kind == 1 && (maxd > 8 || prec == kF64)) return fl_block_of<0, 16, 1, float>();
-  if (which == 0 && kind == 0 && maxd > 8 && prec == kF32) return fl_block_of<0, 16, 0, float>();
+  if (which == 0 && kind != 1 && maxd > 8 && prec == kF32) return fl_block_of<0, 16, 0, float>();
   return fl_block_of<1, 8>();
 }
 
@@ -1263,6 +1338,8 @@ static const void* fl_fused_kernel_t(int cmax, int vmax) {
 }
 static const void* fl_fused_kernel(int kind, int prec, int cmax, int vmax) {
   if (kind == 0) return prec == kF32 ? fl_fused_kernel_t<0, float>(cmax, vmax) : fl_fused_kernel_t<0, double>(cmax, vmax);
+  if (kind == kFlCorrected)
+    return prec == kF32 ? fl_fused_kernel_t<2, float>(cmax, vmax) : fl_fused_kernel_t<2, double>(cmax, vmax);
   return prec == kF32 ? fl_fused_kernel_t<1, float>(cmax, vmax) : fl_fused_kernel_t<1, double>(cmax, vmax);
 }
 
@@ -1291,7 +1368,9 @@ static const void* fl_cn_small_kernel(int prec, int maxd) {
   return maxd <= 8 ? (const void*)fl_cn_small<KIND, double, 8> : (const void*)fl_cn_small<KIND, double, 16>;
 }
 static const void* fl_small_kernel(int which, int kind, int prec, int maxd) {
-  if (which == 0) return kind == 0 ? fl_cn_small_kernel<0>(prec, maxd) : fl_cn_small_kernel<1>(prec, maxd);
+  if (which == 0)
+    return kind == 0 ? fl_cn_small_kernel<0>(prec, maxd)
+                     : kind == kFlCorrected ? fl_cn_small_kernel<2>(prec, maxd) : fl_cn_small_kernel<1>(prec, maxd);
   if (which == 1)
     return prec == kF32 ? (maxd <= 8 ? (const void*)fl_vn_small<float, 8> : (const void*)fl_vn_small<float, 16>)
                         : (maxd <= 8 ? (const void*)fl_vn_small<double, 8> : (const void*)fl_vn_small<double, 16>);

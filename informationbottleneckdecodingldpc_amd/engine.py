@@ -189,26 +189,46 @@ class FloatDecoder:
 
     ``path``: "auto" (the fused on-chip kernel when the code fits in LDS), "passes" (one launch per
     check / variable pass) or "fused" (raises when the code does not fit); both give identical
-    results (``ibl_float_set_path``). ``fused`` tells which one decodes run."""
+    results (``ibl_float_set_path``). ``fused`` tells which one decodes run.
+
+    ``alpha`` / ``beta`` (min-sum only): normalised / offset min-sum, every check magnitude becomes
+    ``max(alpha * m - beta, 0)`` as two rounded operations (include/ibldpc.h "Corrected min-sum"); 0 < alpha <= 1,
+    beta >= 0. The default (1, 0) is plain min-sum; ``correction`` returns the pair. ``kind=1`` with any other
+    value raises ``ValueError``."""
 
     _PATHS = {"auto": _lib.IBL_PATH_AUTO, "passes": _lib.IBL_PATH_PASSES, "fused": _lib.IBL_PATH_FUSED}
 
     def __init__(self, graph: Graph, kind: int, imax: int, max_batch: int, precision=torch.float32,
-                 llr_max: float = 150.0, path: str = "auto"):
+                 llr_max: float = 150.0, path: str = "auto", alpha: float = 1.0, beta: float = 0.0):
         self.graph = graph
         self.kind = int(kind)
         self.imax = int(imax)
         self.max_batch = int(max_batch)
         self.precision = precision
         self.device = graph.device
+        corrected = not (float(alpha) == 1.0 and float(beta) == 0.0)
+        if corrected and self.kind != _lib.IBL_MINSUM:
+            raise ValueError("alpha / beta correct min-sum (kind=0) only")
         h = ctypes.c_void_p()
-        _lib.check(_lib.load().ibl_float_create(graph.handle, self.kind, self.imax, float(llr_max),
-                                                _DT_FL[precision], self.max_batch, ctypes.byref(h)),
-                   "ibl_float_create")
+        if corrected:
+            _lib.check(_lib.load().ibl_float_create_corrected(graph.handle, float(alpha), float(beta), self.imax,
+                                                              float(llr_max), _DT_FL[precision], self.max_batch,
+                                                              ctypes.byref(h)), "ibl_float_create_corrected")
+        else:
+            _lib.check(_lib.load().ibl_float_create(graph.handle, self.kind, self.imax, float(llr_max),
+                                                    _DT_FL[precision], self.max_batch, ctypes.byref(h)),
+                       "ibl_float_create")
         self._h = h
         if path not in self._PATHS:
             raise ValueError(f"path must be one of {sorted(self._PATHS)}")
         _lib.check(_lib.load().ibl_float_set_path(h, self._PATHS[path]), "ibl_float_set_path")
+
+    @property
+    def correction(self):
+        """``(alpha, beta)`` of a min-sum decoder (``ibl_float_correction``; (1.0, 0.0) is plain min-sum)."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        _lib.check(_lib.load().ibl_float_correction(self._h, ctypes.byref(a), ctypes.byref(b)), "ibl_float_correction")
+        return float(a.value), float(b.value)
 
     @property
     def fused(self) -> bool:

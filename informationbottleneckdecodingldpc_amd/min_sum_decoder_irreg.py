@@ -5,6 +5,10 @@
 ``precision`` (extension, keyword-only) selects float32 (default, the BASELINE build) or
 float64 (the reference's double precision, bit-identical min-sum). Output buffers carry that
 dtype.
+
+``alpha`` / ``beta`` (extension, keyword-only) select normalised / offset min-sum: every check magnitude
+becomes ``max(alpha * m - beta, 0)`` (include/ibldpc.h "Corrected min-sum"). The default (1, 0) is the
+reference's plain min-sum; ``correction`` returns the pair.
 """
 from __future__ import annotations
 
@@ -24,7 +28,10 @@ class Min_Sum_Decoder_class_irregular(CodeMixin):
     _kind = _KIND
 
     def __init__(self, filename, imax_, cardinality_T_channel_, msg_at_time_, *, precision=torch.float32,
-                 llr_max: float = 150.0):
+                 llr_max: float = 150.0, alpha: float = 1.0, beta: float = 0.0):
+        self.alpha, self.beta = float(alpha), float(beta)
+        if self._kind != _lib.IBL_MINSUM and (self.alpha, self.beta) != (1.0, 0.0):
+            raise ValueError("alpha / beta correct min-sum only: belief propagation takes neither")
         self._init_code(filename)
         self.imax = int(imax_)
         self.cardinality_T_channel = int(cardinality_T_channel_)
@@ -44,7 +51,12 @@ class Min_Sum_Decoder_class_irregular(CodeMixin):
         self.context = dev
         self.msg_at_time = int(msg_at_time_)
         self._dec = FloatDecoder(self._graph_on(dev), self._kind, self.imax, self.msg_at_time,
-                                 precision=self.precision, llr_max=self.llr_max)
+                                 precision=self.precision, llr_max=self.llr_max, alpha=self.alpha, beta=self.beta)
+
+    @property
+    def correction(self):
+        """``(alpha, beta)`` of the min-sum correction; (1.0, 0.0) is plain min-sum."""
+        return self.alpha, self.beta
 
     def _decode(self, received_blocks, buffer_in, return_buffer, early_stop=True):
         if self._dec is None:
