@@ -6,10 +6,13 @@ import numpy as np
 import scipy.sparse as sp
 
 
-def layered_decode(H, layers, llr, imax, alpha=1.0, beta=0.0, llr_max=150.0, early_stop=True, hook=None):
+def layered_decode(H, layers, llr, imax, alpha=1.0, beta=0.0, llr_max=150.0, early_stop=True, hook=None,
+                   stop_rule=None):
     """-> (out [N][B] float32, iters [B] int32). `hook` (tests/_layered_census.py) observes every update of the
     checks of one degree of a layer and changes nothing: hook(it, checks [n], D = P - R before the clamp, Q, pos,
-    m1, m2, mag, R_new (all [n][d][B] or [n][B]), done [B])."""
+    m1, m2, mag, R_new (all [n][d][B] or [n][B]), done [B]). `stop_rule(A, P) -> bool [B]` replaces the
+    specification's stop test ("every check's decisions have even parity") by a wrong one, on purpose
+    (tests/test_cpu_codewords.py: what an all-zero input cannot tell apart)."""
     A = sp.csr_matrix(H)
     A.sort_indices()
     indptr, cols = A.indptr.astype(np.int64), A.indices.astype(np.int64)
@@ -51,8 +54,11 @@ def layered_decode(H, layers, llr, imax, alpha=1.0, beta=0.0, llr_max=150.0, ear
             if hook is not None:
                 hook(it, cs, D, Q, pos, m1, m2, mag, Rn, done)
         if early_stop:
-            x = (P < 0).astype(np.int32)
-            ok = ((A @ x) % 2 == 0).all(axis=0) & ~done
+            if stop_rule is None:
+                x = (P < 0).astype(np.int32)
+                ok = ((A @ x) % 2 == 0).all(axis=0) & ~done
+            else:
+                ok = np.asarray(stop_rule(A, P), dtype=bool) & ~done
             out[:, ok] = P[:, ok]
             iters[ok] = it
             done |= ok

@@ -219,3 +219,129 @@ def test_pipelined_driver_equals_sync_driver(case, side, wlan_H, dvb_H):
     np.testing.assert_array_equal(a.BER_vector, b.BER_vector)
     np.testing.assert_array_equal(a.EbN0_dB_vector, b.EbN0_dB_vector)
     assert len(b.blocks) >= 3 and b.blocks[0] < kw["max_blocks"] and b.blocks[-1] == kw["max_blocks"]
+
+
+# ------------------------------------------------------------------ encoded mode: random codewords, mirrored channel
+def _replay_encoded(cfg, H, n_v, err_rows, R_c, decode, ones_of):
+    """_replay for ``cfg.encoded=True``, keyed on the global batch index g as ``ber._rank_sweep`` documents: bits =
+    ``oracle.random_bits(seed, g * philox_blocks(K, B), K, B)``, codeword = the encoder oracle's, channel =
+    ``oracle.channel_sample(cdf, seed, g * philox_blocks(N, B), N, B, codeword)``; ``decode(cl, q)`` -> (output, stop
+    iterations), errors = decided bits that differ from the codeword over the first ``err_rows`` rows. Also returns
+    the stop iterations of every batch, per point."""
+    from oracle import encoder_oracle
+    plan = encoder_oracle.EncoderPlan(H)
+    B = cfg.msg_at_time
+    pb_ch, pb_bits = engine.philox_blocks(n_v, B), engine.philox_blocks(plan.K, B)
+    ebn0, ber, errs, blks, stops = [float(cfg.EbN0_dB_start)], [0.0], [], [], []
+    g = 0
+    while True:
+        s2 = 10 ** (-ebn0[-1] / 10) / (2 * R_c)
+        q = _quanti(cfg, s2)
+        errors, blocks = 0.0, 0
+        stops.append([])
+        while errors < cfg.min_errors and (cfg.max_blocks is None or blocks < cfg.max_blocks):
+            code = encoder_oracle.encode(plan, oracle.random_bits(cfg.seed, g * pb_bits, plan.K, B))
+            cl = oracle.channel_sample(q.cdf_t_given_x_equals_zero, cfg.seed, g * pb_ch, n_v, B, code)
+            out, it = decode(cl, q)
+            errors += float((ones_of(out) != (code == 1))[:err_rows].sum())
+            stops[-1].append(it)
+            blocks += B
+            g += 1
+        ber[-1] = errors / (R_c * blocks * n_v)
+        errs.append(errors)
+        blks.append(blocks)
+        if ber[-1] > cfg.target_error_rate and ebn0[-1] < cfg.EbN0_dB_max_value:
+            step = cfg.EbN0_dB_small_stepwidth if ber[-1] < cfg.BER_go_on_in_smaller_steps \
+                else cfg.EbN0_dB_normal_stepwidth
+            ebn0.append(ebn0[-1] + step)
+            ber.append(0.0)
+        else:
+            break
+    return (np.asarray(ebn0), np.asarray(ber), errs, blks), stops
+
+
+ENC_IMAX, ENC_B, ENC_BATCHES = 10, 64, 3
+
+
+def _encoded_cfg(**kw):
+    """Two points, 1 dB (errors are counted) and 6 dB (every batch stops early with no error), three batches each."""
+    return BERConfig(EbN0_dB_start=1.0, EbN0_dB_max_value=6.0, EbN0_dB_normal_stepwidth=5.0,
+                     EbN0_dB_small_stepwidth=5.0, target_error_rate=1e-9, min_errors=10 ** 9, msg_at_time=ENC_B,
+                     max_blocks=ENC_BATCHES * ENC_B, seed=29, encoded=True, **kw)
+
+
+def _encoded_decoder(kind):
+    """-> (H, decoder class instance, oracle decode(cl, q) -> (out, stops), ones_of(out), loop's last iteration)."""
+    from informationbottleneckdecodingldpc_amd.discrete_LDPC_decoder_irreg import \
+        Discrete_LDPC_Decoder_class_irregular
+    from informationbottleneckdecodingldpc_amd.min_sum_decoder_irreg import Min_Sum_Decoder_class_irregular
+    import informationbottleneckdecodingldpc_amd as pkg
+    from tests._layered_ref import layered_decode
+    H = codes.wlan_80211n(27)
+    g = graph.build_graph(H)
+    if kind == "ib":
+        design = _quanti(BERConfig(), 10 ** (-1.5 / 10) / (2 * g.R_c))
+        tb = tables.llr_tables(design.output_LLRs, g.d_c_max, g.d_v_max, ENC_IMAX)
+        dec = Discrete_LDPC_Decoder_class_irregular(H, ENC_IMAX, 16, 16, tb.cn, tb.vn, tb.match_cn, tb.match_vn, ENC_B,
+                                                    match="true")
+        return H, dec, (lambda cl, q: oracle.ib_decode(g, tb, cl, match=True, early_stop=True, return_iters=True)), \
+            (lambda out: out < 8), ENC_IMAX - 1
+    if kind == "minsum32":
+        dec = Min_Sum_Decoder_class_irregular(H, ENC_IMAX, 16, ENC_B)
+        return H, dec, (lambda cl, q: oracle.float32_decode(g, ENC_IMAX, q.output_LLRs.astype(np.float32)[cl],
+                                                            early_stop=True, return_iters=True)), \
+            (lambda out: out < 0), ENC_IMAX - 1
+    dec = pkg.Min_Sum_Layered_Decoder_class_irregular(H, 8, 16, ENC_B, Z=27, alpha=0.8125)
+    layers = codes.qc_layers(H, 27)
+    return H, dec, (lambda cl, q: layered_decode(H, layers, q.output_LLRs.astype(np.float32)[cl], 8, 0.8125, 0.0)), \
+        (lambda out: out < 0), 8
+
+
+_encoded_refs = {}
+
+
+def _encoded_ref(kind):
+    """The oracle replay of one decoder family (shared by the pipelined, synchronous and lockstep runs)."""
+    if kind not in _encoded_refs:
+        H, dec, decode, ones_of, last = _encoded_decoder(kind)
+        ref, stops = _replay_encoded(_encoded_cfg(), H, H.shape[1], dec.data_len, float(dec.R_c), decode, ones_of)
+        ebn0, ber, errs, blks = ref
+        print(f"encoded {kind}: points {list(ebn0)} errors {errs} blocks {blks}, last stop of each batch "
+              f"{[[int(np.max(it)) for it in s] for s in stops]}")
+        assert list(ebn0) == [1.0, 6.0] and blks == [ENC_BATCHES * ENC_B] * 2
+        assert errs[0] > 0 and errs[1] == 0
+        # the last point: every batch stops inside the loop (layered: every codeword), on nonzero codewords
+        assert all(0 < int(np.max(it)) < last for it in stops[1])
+        _encoded_refs[kind] = ref
+    return _encoded_refs[kind]
+
+
+def _assert_same_encoded(r, ref):
+    ebn0, ber, errs, blks = ref
+    np.testing.assert_allclose(r.EbN0_dB_vector, ebn0, rtol=0, atol=1e-12)
+    assert [int(e) for e in r.errors] == [int(e) for e in errs]
+    assert r.blocks == blks
+    np.testing.assert_array_equal(r.BER_vector, ber)
+
+
+@pytest.mark.parametrize("pipeline", [True, False])
+@pytest.mark.parametrize("kind", ["ib", "minsum32", "layered"])
+def test_encoded_ber_equals_oracle_replay(kind, pipeline):
+    """``BERConfig.encoded=True`` (random bits -> device encoder -> mirrored channel -> decode -> ``count_errors``)
+    against the same chain on the CPU: identical errors, blocks and BER at a point where errors are counted and at
+    one where every batch of nonzero codewords stops early without an error, pipelined and batch by batch."""
+    ref = _encoded_ref(kind)
+    _, dec, _, _, _ = _encoded_decoder(kind)
+    kw = {} if kind == "ib" else {"llr_dtype": torch.float32}
+    r = run_ber(dec, _encoded_cfg(pipeline=pipeline, **kw))
+    print(f"encoded {kind} pipeline={pipeline}: errors {r.errors} blocks {r.blocks}")
+    _assert_same_encoded(r, ref)
+
+
+def test_encoded_ber_lockstep_two_ranks():
+    """Two emulated ranks (global batches 2j and 2j + 1; three batches a point, so the second round's last batch is
+    discarded) count what the oracle replay counts."""
+    from informationbottleneckdecodingldpc_amd.ber import run_ber_lockstep
+    ref = _encoded_ref("ib")
+    _, dec, _, _, _ = _encoded_decoder("ib")
+    _assert_same_encoded(run_ber_lockstep(dec, _encoded_cfg(), 2), ref)
