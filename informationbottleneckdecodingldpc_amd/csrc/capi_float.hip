@@ -65,7 +65,7 @@ int fused_setup(ibl_float* h) {
   const size_t lds = (size_t)(E + g->n_v) * 16 + 16 + ft.vn_slot.size() * 2;
   if (lds > (size_t)kLdsBytes) return IBL_OK;
   int bpc = 0, block = 0;
-  if (fl_fused_occupancy(h->kkind, h->prec, g->dcm, g->dvm, lds, &bpc, &block) != hipSuccess || bpc < 1) {
+  if (fl_occupancy(kFlFused, kFlCheck, h->kkind, h->prec, g->dcm, g->dvm, lds, &bpc, &block) != hipSuccess || bpc < 1) {
     (void)hipGetLastError();
     return IBL_OK;
   }
@@ -79,7 +79,7 @@ int fused_setup(ibl_float* h) {
 // Launch geometry of the fused float kernel for a batch of B: groups of 4 fp32 / 2 fp64 codewords, one per
 // workgroup round (fl_fused's group loop); the decode and ibl_float_fused_geometry both take it from here.
 void float_fused_geometry(const ibl_float* h, int B, int32_t* ngroups, int32_t* grid) {
-  const int cwl = h->prec == kF32 ? 4 : 2;
+  const int cwl = fl_cw_per_lane(h->prec);
   *ngroups = (B + cwl - 1) / cwl;
   *grid = std::min(*ngroups, h->f_grid);
 }
@@ -93,7 +93,7 @@ int fold_alloc(ibl_float* h) {
   DevBuf<uint8_t> c2;
   DevBuf<int32_t> fold, nodes;
   int rc;
-  if ((rc = c2.alloc_zero((size_t)h->g->n_e * h->ldb * (h->prec == kF32 ? 4 : 8))) || (rc = fold.upload(h->fold_rec)) ||
+  if ((rc = c2.alloc_zero((size_t)h->g->n_e * h->ldb * fl_elem_size(h->prec))) || (rc = fold.upload(h->fold_rec)) ||
       (rc = nodes.upload(h->fold_rest)))
     return rc;
   h->fold = std::move(fold);
@@ -106,10 +106,36 @@ int fold_alloc(ibl_float* h) {
 // the fp64 decoder, |x| > 709.089 (just under ln(DBL_MAX / 2)), for the fp32 decoder +-inf
 int stage_rule(const ibl_float* h) { return h->kind == IBL_BP ? (h->prec == kF64 ? 2 : 3) : 1; }
 
+// The send, check, variable and decision arguments that the small-batch and the per-pass schedule share, for a
+// batch of B in rows of ldb codewords. The schedules add their tasks or chunks and the fold, and set the buffers
+// and gates of each pass.
+struct FlPassArgs {
+  FlArgs send{}, cn{}, vn{};
+  FlDecArgs dec{};
+};
+FlPassArgs float_pass_args(const ibl_float* h, int B, int ldb, void* d_out, int32_t out_dtype) {
+  const ibl_graph* g = h->g;
+  FlPassArgs p;
+  p.send.ch = p.cn.ch = p.vn.ch = p.dec.ch = h->chf;
+  p.send.out = h->cin;
+  p.send.start = p.vn.start = p.dec.start = g->vn_start;
+  p.send.deg = p.vn.deg = p.dec.deg = g->vn_deg;
+  p.send.tgt = p.vn.tgt = g->tgt_vn;
+  p.cn.start = g->cn_start; p.cn.deg = g->cn_deg; p.cn.tgt = g->tgt_cn;
+  p.cn.llr_max = p.vn.llr_max = h->llr_max;
+  p.cn.cor_a = h->alpha; p.cn.cor_b = h->beta;
+  p.cn.n_nodes = g->n_c;
+  p.send.n_nodes = p.vn.n_nodes = p.dec.n_nodes = g->n_v;
+  p.send.ldb = p.cn.ldb = p.vn.ldb = p.dec.ldb = ldb;
+  p.send.B = p.cn.B = p.vn.B = p.dec.B = B;
+  p.dec.vin0 = h->vbuf0; p.dec.vin1 = h->vbuf1; p.dec.iters = h->dL; p.dec.out = d_out; p.dec.out_dtype = out_dtype;
+  return p;
+}
+
 int float_decode_fused(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out, int32_t out_dtype,
                        bool early, int32_t* d_iters, hipStream_t s) {
   const ibl_graph* g = h->g;
-  const int I = h->imax, cwl = h->prec == kF32 ? 4 : 2;
+  const int I = h->imax, cwl = fl_cw_per_lane(h->prec);
   HIPCHK(launch_fl_stage_t(d_llr, llr_dtype, g->n_v, B, h->ft.vn_node, h->chf, h->prec, stage_rule(h), h->bad, s));
   FlFusedArgs fa{};
   fa.ch = h->chf; fa.cn_task = h->ft.cn_task; fa.vn_task = h->ft.vn_task; fa.vn_node = h->ft.vn_node;
@@ -119,7 +145,7 @@ int float_decode_fused(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32
   fa.n_vn_tasks = h->ft.n_vn; fa.n_vs = h->ft.n_vs; fa.ldb = h->ldb; fa.B = B; fa.imax = I; fa.out_dtype = out_dtype;
   int grid = 0;
   float_fused_geometry(h, B, &fa.ngroups, &grid);
-  fa.aligned = out_aligned(B, d_out, cwl, out_dtype == kF32 ? 4 : 8);
+  fa.aligned = out_aligned(B, d_out, cwl, fl_elem_size(out_dtype));
   auto launch = [&] { return launch_fl_fused(fa, h->kkind, h->prec, g->dcm, g->dvm, grid, h->f_lds, s); };
 #if IBL_DIAG
   const char* ftrace = getenv("IBL_TRACE_FUSED");   // diagnostic builds: phase clocks of block 0's first group
@@ -150,27 +176,22 @@ int float_decode_fused(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32
 int float_decode_small(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out, int32_t out_dtype,
                        bool early, int32_t* d_iters, hipStream_t s) {
   const ibl_graph* g = h->g;
-  const int I = h->imax, cwl = h->prec == kF32 ? 4 : 2;
+  const int I = h->imax, cwl = fl_cw_per_lane(h->prec);
   const int nwords = (B + cwl - 1) / cwl, ldbs = (B + 3) / 4 * 4;
   HIPCHK(launch_fl_stage(d_llr, llr_dtype, g->n_v, B, h->chf, h->prec, ldbs, stage_rule(h), h->bad, s));
   auto grid_of = [&](int ntask) {
     const int need = (ntask * nwords + kFlSmallBlock / 64 - 1) / (kFlSmallBlock / 64);
     return std::max(1, std::min(need, 4 * g->num_cus));
   };
-  FlArgs send{};
-  send.ch = h->chf; send.out = h->cin; send.start = g->vn_start; send.deg = g->vn_deg; send.tgt = g->tgt_vn;
-  send.n_nodes = g->n_v; send.ldb = ldbs; send.B = B;
-  FlArgs cn{}, vn{};
-  cn.in = h->cin; cn.start = g->cn_start; cn.deg = g->cn_deg; cn.tgt = g->tgt_cn; cn.ch = h->chf;
-  vn.out = h->cin; vn.ch = h->chf; vn.start = g->vn_start; vn.deg = g->vn_deg; vn.tgt = g->tgt_vn;
+  FlPassArgs pa = float_pass_args(h, B, ldbs, d_out, out_dtype);
+  const FlArgs& send = pa.send;
+  FlArgs &cn = pa.cn, &vn = pa.vn;
+  FlDecArgs& dc = pa.dec;
+  cn.in = h->cin;
+  vn.out = h->cin;
   cn.info = g->cn_info; cn.task = g->cn_task; cn.n_tasks = g->n_cn_task;
-  vn.info = g->vn_info; vn.task = g->vn_task; vn.n_tasks = g->n_vn_task;
-  cn.llr_max = vn.llr_max = h->llr_max;
-  cn.cor_a = h->alpha; cn.cor_b = h->beta;
-  cn.n_nodes = g->n_c; vn.n_nodes = g->n_v;
-  cn.nwords = vn.nwords = nwords;
-  cn.ldb = vn.ldb = ldbs;
-  cn.B = vn.B = B;
+  vn.info = dc.info = g->vn_info; vn.task = dc.task = g->vn_task; vn.n_tasks = dc.n_tasks = g->n_vn_task;
+  cn.nwords = vn.nwords = dc.nwords = nwords;
   const int gcn = grid_of(g->n_cn_task), gvn = grid_of(g->n_vn_task);
   // the pass chain (decoder buffers only): send, then {CN j, VN j} — replayed from a captured graph (ChainGraphs)
   auto chain = [&](hipStream_t st) -> hipError_t {
@@ -182,12 +203,12 @@ int float_decode_small(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32
       c.out = vb;
       c.gate = flag_row(h->flags, early && j >= 3, j - 2);
       c.unsat = flag_row(h->flags, early, j - 1);
-      if ((e = h->timer.timed(0, st, [&] { return launch_fl_cn_small(c, h->kkind, h->prec, g->dcm, gcn, st); })) != hipSuccess)
+      if ((e = h->timer.timed(0, st, [&] { return launch_fl_pass(kFlSmall, kFlCheck, c, h->kkind, h->prec, g->dcm, gcn, st); })) != hipSuccess)
         return e;
       if (j == I - 1) break;   // the last variable pass feeds no output (as in float_decode_passes)
       v.in = vb;
       v.gate = flag_row(h->flags, early && j >= 2, j - 1);
-      if ((e = h->timer.timed(1, st, [&] { return launch_fl_vn_small(v, h->prec, g->dvm, gvn, st); })) != hipSuccess)
+      if ((e = h->timer.timed(1, st, [&] { return launch_fl_pass(kFlSmall, kFlVariable, v, 0, h->prec, g->dvm, gvn, st); })) != hipSuccess)
         return e;
     }
     return hipSuccess;
@@ -195,25 +216,20 @@ int float_decode_small(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32
   if (h->s_graphs.on && !h->timer.on) HIPCHK(h->s_graphs.run(B, early ? 1 : 0, s, chain));
   else HIPCHK(chain(s));
   HIPCHK(launch_finalize(h->flags, I, early ? 1 : 0, h->dL, d_iters, s));
-  FlDecArgs dc{};
-  dc.vin0 = h->vbuf0; dc.vin1 = h->vbuf1; dc.ch = h->chf; dc.start = g->vn_start; dc.deg = g->vn_deg;
-  dc.iters = h->dL; dc.out = d_out; dc.out_dtype = out_dtype; dc.n_nodes = g->n_v; dc.ldb = ldbs; dc.B = B;
-  dc.info = g->vn_info; dc.task = g->vn_task; dc.n_tasks = g->n_vn_task; dc.nwords = nwords;
-  HIPCHK(launch_fl_dec_small(dc, h->prec, grid_of(g->n_vn_task), s));
+  HIPCHK(launch_fl_dec(kFlSmall, dc, h->prec, gvn, s));
   return IBL_OK;
 }
 
 int float_decode_passes(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out, int32_t out_dtype,
                         bool early, int32_t* d_iters, hipStream_t s) {
   const ibl_graph* g = h->g;
-  const int I = h->imax, cwl = h->prec == kF32 ? 4 : 2;   // cwl: codewords per lane
-  const int nchunks = (B + 64 * cwl - 1) / (64 * cwl);
+  const int I = h->imax, cwl = fl_cw_per_lane(h->prec);
+  const int nchunks = (B + fl_vn_chunk(h->prec) - 1) / fl_vn_chunk(h->prec);
   HIPCHK(launch_fl_stage(d_llr, llr_dtype, g->n_v, B, h->chf, h->prec, h->ldb, stage_rule(h), h->bad, s));
-  FlArgs send{};
-  send.ch = h->chf; send.out = h->cin;   // = cb[1] below
-  send.start = g->vn_start; send.deg = g->vn_deg; send.tgt = g->tgt_vn;
-  send.n_nodes = g->n_v; send.ldb = h->ldb; send.B = B;
-  HIPCHK(launch_fl_send(send, h->prec, s));
+  FlPassArgs pa = float_pass_args(h, B, h->ldb, d_out, out_dtype);
+  FlArgs &cn = pa.cn, &vn = pa.vn;
+  FlDecArgs& dc = pa.dec;
+  HIPCHK(launch_fl_send(pa.send, h->prec, s));
   // Check pass j reads check inbox cb[j & 1] (send fills cb[1]) and writes the variable inbox vbuf[j & 1];
   // variable pass j writes cb[(j + 1) & 1]. With the fold, check pass j also writes its folded variables'
   // messages into cb[(j + 1) & 1], and the variable pass skips them; the last check pass writes every
@@ -223,17 +239,12 @@ int float_decode_passes(ibl_float* h, const void* d_llr, int32_t llr_dtype, int3
   if (h->n_folded > 0 && !h->cin2) return fail(IBL_EHIP, "fold inbox missing (fold_alloc)");
   const bool fold = h->n_folded > 0;
   void* cb[2] = {fold ? h->cin2 : h->cin, h->cin};
-  FlArgs cn{}, vn{};
-  cn.start = g->cn_start; cn.deg = g->cn_deg; cn.tgt = g->tgt_cn; cn.ch = h->chf; cn.fold = h->fold;
-  vn.ch = h->chf; vn.start = g->vn_start; vn.deg = g->vn_deg; vn.tgt = g->tgt_vn;
-  vn.nodes = fold ? h->vn_nodes.get() : nullptr;
-  cn.llr_max = vn.llr_max = h->llr_max;
-  cn.cor_a = h->alpha; cn.cor_b = h->beta;
-  cn.n_nodes = g->n_c; vn.n_nodes = fold ? h->n_vn_nodes : g->n_v;
-  cn.nchunks = nchunks;
-  vn.nchunks = (B + fl_vn_chunk(h->prec, g->dvm) - 1) / fl_vn_chunk(h->prec, g->dvm);
-  cn.ldb = vn.ldb = h->ldb;
-  cn.B = vn.B = B;
+  cn.fold = h->fold;
+  if (fold) {   // the variable pass updates the variables that are not folded
+    vn.nodes = h->vn_nodes.get();
+    vn.n_nodes = h->n_vn_nodes;
+  }
+  cn.nchunks = vn.nchunks = dc.nchunks = nchunks;
   for (int j = 1; j < I; ++j) {
     void* vb = (j & 1) ? h->vbuf1 : h->vbuf0;
     const bool last = j == I - 1;
@@ -243,21 +254,17 @@ int float_decode_passes(ibl_float* h, const void* d_llr, int32_t llr_dtype, int3
     cn.fold_mode = (fold && !last) ? (early ? 2 : 1) : 0;
     cn.gate = flag_row(h->flags, early && j >= 3, j - 2);
     cn.unsat = flag_row(h->flags, early, j - 1);
-    HIPCHK(h->timer.timed(0, s, [&] { return launch_fl_cn(cn, h->kkind, h->prec, g->dcm, h->grid_cn, s); }));
+    HIPCHK(h->timer.timed(0, s, [&] { return launch_fl_pass(kFlPerPass, kFlCheck, cn, h->kkind, h->prec, g->dcm, h->grid_cn, s); }));
     if (last) break;
     vn.in = vb;
     vn.out = cb[(j + 1) & 1];
     vn.gate = flag_row(h->flags, early && j >= 2, j - 1);
-    HIPCHK(h->timer.timed(1, s, [&] { return launch_fl_vn(vn, h->prec, g->dvm, h->grid_vn, s); }));
+    HIPCHK(h->timer.timed(1, s, [&] { return launch_fl_pass(kFlPerPass, kFlVariable, vn, 0, h->prec, g->dvm, h->grid_vn, s); }));
   }
   HIPCHK(launch_finalize(h->flags, I, early ? 1 : 0, h->dL, d_iters, s));
-  FlDecArgs dc{};
-  dc.vin0 = h->vbuf0; dc.vin1 = h->vbuf1; dc.ch = h->chf; dc.start = g->vn_start; dc.deg = g->vn_deg;
-  dc.iters = h->dL; dc.out = d_out; dc.out_dtype = out_dtype; dc.n_nodes = g->n_v; dc.nchunks = nchunks;
-  dc.ldb = h->ldb; dc.B = B;
-  dc.aligned = out_aligned(B, d_out, cwl, out_dtype == kF32 ? 4 : 8);
+  dc.aligned = out_aligned(B, d_out, cwl, fl_elem_size(out_dtype));
   const size_t items = (size_t)g->n_v * nchunks;
-  HIPCHK(launch_fl_dec(dc, h->prec, (int)std::min<size_t>((items + 3) / 4, 65536), s));
+  HIPCHK(launch_fl_dec(kFlPerPass, dc, h->prec, (int)std::min<size_t>((items + 3) / 4, 65536), s));
   return IBL_OK;
 }
 
@@ -272,25 +279,25 @@ int float_create(const ibl_graph* g, int32_t kind, int32_t kkind, double alpha, 
   h->kkind = kkind; h->alpha = alpha; h->beta = beta;
   // rows padded to the wave item of the per-pass kernels (fp32 256 / fp64 128 codewords), not beyond: the
   // reference's DVB-S2 driver decodes msg_at_time = 2 in fp64
-  const int pad = fl_vn_chunk(precision, g->dvm);
+  const int pad = fl_vn_chunk(precision);
   h->ldb = (max_batch + pad - 1) / pad * pad;
-  const size_t es = precision == kF32 ? 4 : 8;
+  const size_t es = fl_elem_size(precision);
   const size_t inbox = (size_t)g->n_e * h->ldb * es;
   int rc;
   if ((rc = h->cin.alloc_zero(inbox)) || (rc = h->vbuf0.alloc_zero(inbox)) || (rc = h->vbuf1.alloc_zero(inbox)) ||
       (rc = h->chf.alloc((size_t)g->n_v * h->ldb * es)) || (rc = h->flags.alloc((size_t)imax * kShards)) ||
       (rc = h->dL.alloc(1)) || (rc = h->bad.alloc_zero(1)))
     return rc;
-  int bpc = 0;
+  int bpc = 0, block = 0;
   // at most 16 waves per CU: with a second block per CU its waves issue behind the first block's
   // (oldest-first) and the per-block work counters cannot rebalance across blocks
-  if (fl_occupancy(0, kkind, precision, g->dcm, &bpc) != hipSuccess || bpc < 1) bpc = 1;
+  if (fl_occupancy(kFlPerPass, kFlCheck, kkind, precision, g->dcm, g->dvm, 0, &bpc, &block) != hipSuccess || bpc < 1) bpc = 1;
   // (A/B knob, read once here: IBL_FL_WAVES = waves per CU the per-pass grids may fill, default 16)
   const char* fw = getenv("IBL_FL_WAVES");
   const int wcap = std::max(16, fw ? atoi(fw) : 16) * 64;
-  h->grid_cn = std::min(bpc, wcap / fl_block(0, kkind, precision, g->dcm)) * g->num_cus;
-  if (fl_occupancy(1, kkind, precision, g->dvm, &bpc) != hipSuccess || bpc < 1) bpc = 1;
-  h->grid_vn = std::min(bpc, wcap / fl_block(1, kkind, precision, g->dvm)) * g->num_cus;
+  h->grid_cn = std::min(bpc, wcap / block) * g->num_cus;
+  if (fl_occupancy(kFlPerPass, kFlVariable, kkind, precision, g->dcm, g->dvm, 0, &bpc, &block) != hipSuccess || bpc < 1) bpc = 1;
+  h->grid_vn = std::min(bpc, wcap / block) * g->num_cus;
   if ((rc = fused_setup(h.get()))) return rc;
   // degree-2 variable fold of the per-pass path (IBL_FL_FOLD=0 at create turns it off: A/B); its second check
   // inbox is allocated only once some batch can reach the per-pass kernels (max_batch > small_b, fold_alloc)
@@ -301,12 +308,12 @@ int float_create(const ibl_graph* g, int32_t kind, int32_t kkind, double alpha, 
   // same guard as the IB fast path: the float kernels are built to run without scratch
   size_t priv = 0;
   const char* kname = "";
-  HIPCHK(fl_private_bytes(kkind, precision, g->dcm, g->dvm, h->fused_ok, &priv, &kname));
+  HIPCHK(fl_private_bytes(kFlPerPass, kkind, precision, g->dcm, g->dvm, h->fused_ok, &priv, &kname));
   if ((rc = refuse_private(priv, std::string("float kernel ") + kname + " has a ",
                            "-byte private segment (register spill): rebuild required")))
     return rc;
   // small-batch kernels (IBL_SMALL_B at create overrides the default; off if they would need scratch)
-  HIPCHK(fl_small_private_bytes(kkind, precision, g->dcm, g->dvm, &priv, &kname));
+  HIPCHK(fl_private_bytes(kFlSmall, kkind, precision, g->dcm, g->dvm, false, &priv, &kname));
   h->s_ok = priv == 0;
   small_batch_env(h->s_ok, kFlSmallBatchDefault, &h->small_b, &h->s_graphs);
   if ((rc = fold_alloc(h.get()))) return rc;

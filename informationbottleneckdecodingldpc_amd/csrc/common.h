@@ -179,6 +179,15 @@ struct IbGenDecArgs {
 };
 
 // ------------------------------------------------------------------- float path
+// The float kernels come in three families — per-pass, small-batch (B <= a few words; lane = node) and fused
+// on-chip — with a check, a variable and a decision (APP output) pass each; the fused kernel is all of them.
+enum FlFamily : int { kFlPerPass = 0, kFlSmall = 1, kFlFused = 2 };
+enum FlPass : int { kFlCheck = 0, kFlVariable = 1, kFlDecision = 2, kFlSend = 3 };
+// by decoder precision (or buffer dtype): codewords in a lane's 16 bytes, bytes per element
+constexpr int fl_cw_per_lane(int prec) { return prec == kF32 ? 4 : 2; }
+constexpr size_t fl_elem_size(int dtype) { return dtype == kF32 ? 4 : 8; }
+// codewords per wave item of the per-pass kernels: inbox rows are padded to a multiple of it
+constexpr int fl_vn_chunk(int prec) { return 64 * fl_cw_per_lane(prec); }
 struct FlArgs {
   const void* in;           // own-order inbox (F)
   void* out;                // other-order inbox (F)
@@ -323,24 +332,19 @@ hipError_t launch_fl_stage(const void* x, int in_dtype, int n, int B, void* dst,
                            int32_t* bad, hipStream_t s);
 hipError_t launch_fl_stage_t(const void* x, int in_dtype, int n, int B, const int32_t* perm, void* dst, int prec,
                              int rule, int32_t* bad, hipStream_t s);
-hipError_t launch_fl_cn(const FlArgs& a, int kind, int prec, int maxd, int grid, hipStream_t s);
-hipError_t launch_fl_vn(const FlArgs& a, int prec, int maxd, int grid, hipStream_t s);
-int fl_vn_chunk(int prec, int maxd);   // codewords per wave item of the per-pass variable kernel
-constexpr int kFlRowPad = 512;   // float inbox rows are padded to this many codewords (every item shape fits)
-hipError_t launch_fl_dec(const FlDecArgs& a, int prec, int grid, hipStream_t s);
-// small-batch float kernels (B <= a few words; lane = node): kFlSmallBlock threads per block
-hipError_t launch_fl_cn_small(const FlArgs& a, int kind, int prec, int maxd, int grid, hipStream_t s);
-hipError_t launch_fl_vn_small(const FlArgs& a, int prec, int maxd, int grid, hipStream_t s);
-hipError_t launch_fl_dec_small(const FlDecArgs& a, int prec, int grid, hipStream_t s);
-hipError_t fl_small_private_bytes(int kind, int prec, int cn_maxd, int vn_maxd, size_t* bytes, const char** name);
-hipError_t fl_occupancy(int which, int kind, int prec, int maxd, int* blocks_per_cu);
-// Largest private segment over the float kernels of (kind, prec, degrees); fused included when asked.
-hipError_t fl_private_bytes(int kind, int prec, int cn_maxd, int vn_maxd, bool fused, size_t* bytes,
-                            const char** name);
-int fl_block(int which, int kind, int prec, int maxd);  // threads per block of the float CN (0) / VN (1) kernels
+// check or variable pass of the per-pass or small-batch family (maxd: the largest check / variable degree)
+hipError_t launch_fl_pass(FlFamily fam, FlPass pass, const FlArgs& a, int kind, int prec, int maxd, int grid,
+                          hipStream_t s);
+hipError_t launch_fl_dec(FlFamily fam, const FlDecArgs& a, int prec, int grid, hipStream_t s);
 hipError_t launch_fl_fused(const FlFusedArgs& a, int kind, int prec, int cmax, int vmax, int grid, size_t lds,
                            hipStream_t s);
-hipError_t fl_fused_occupancy(int kind, int prec, int cmax, int vmax, size_t lds, int* blocks_per_cu, int* block);
+// blocks per CU and threads per block of a kernel (the fused kernel with lds bytes of dynamic LDS)
+hipError_t fl_occupancy(FlFamily fam, FlPass pass, int kind, int prec, int cmax, int vmax, size_t lds,
+                        int* blocks_per_cu, int* block);
+// Largest private segment over the check, variable and decision kernels of the small-batch family, or over the
+// per-pass check and variable kernels and, when asked, the fused kernel; *name receives that kernel's name.
+hipError_t fl_private_bytes(FlFamily fam, int kind, int prec, int cn_maxd, int vn_maxd, bool fused, size_t* bytes,
+                            const char** name);
 
 // ------------------------------------------------------------ layered min-sum (layered_kernels.hip)
 // One wave per codeword, cw_per_group waves per workgroup; the plan's arrays as in layered_plan.h.

@@ -22,6 +22,7 @@
 // Each wave item is one node x kChunk codewords; a lane holds 16 bytes of every edge row
 // (4 fp32 or 2 fp64 codewords; fp64 items cover 128 codewords).
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 
@@ -141,11 +142,16 @@ template <typename F> struct NtVec;
 template <> struct NtVec<float> { typedef float T __attribute__((ext_vector_type(4))); };
 template <> struct NtVec<double> { typedef double T __attribute__((ext_vector_type(2))); };
 
-// one lane's piece (Vec<F>::N codewords) of a row
-template <typename F>
-__device__ __forceinline__ void fl_row_load(const F* p, F (&v)[Vec<F>::N]) {
+// One lane's 16 bytes (Vec<F>::N codewords): codewords cw0.. of row `row` of the [.][ldb] message or channel array
+// at `base`, or the LDS slot at `base` itself (no row: the fused items pass the slot's address, which keeps their
+// addresses 32-bit). NT: a nontemporal access (kFlNt) — the per-pass kernels' row loads and stores and the
+// small-batch kernels' row stores; the small-batch and decision kernels' loads and every LDS access are plain.
+constexpr bool kFlNt = IBL_FL_NT != 0;
+template <bool NT, typename F>
+__device__ __forceinline__ void fl_load16(const void* base, F (&v)[Vec<F>::N], int ldb = 0, int row = 0, int cw0 = 0) {
   using V = Vec<F>;
-  if constexpr (IBL_FL_NT) {
+  const F* p = reinterpret_cast<const F*>(base) + (size_t)row * ldb + cw0;
+  if constexpr (NT) {
     const typename NtVec<F>::T r = __builtin_nontemporal_load(reinterpret_cast<const typename NtVec<F>::T*>(p));
 #pragma unroll
     for (int s = 0; s < V::N; ++s) v[s] = r[s];
@@ -155,12 +161,11 @@ __device__ __forceinline__ void fl_row_load(const F* p, F (&v)[Vec<F>::N]) {
     for (int s = 0; s < V::N; ++s) v[s] = V::get(r, s);
   }
 }
-
-template <typename F>
-__device__ __forceinline__ void fl_store_to(void* base, int ldb, int row, int cw0, const F (&v)[Vec<F>::N]) {
+template <bool NT, typename F>
+__device__ __forceinline__ void fl_store16(void* base, const F (&v)[Vec<F>::N], int ldb = 0, int row = 0, int cw0 = 0) {
   using V = Vec<F>;
   F* p = reinterpret_cast<F*>(base) + (size_t)row * ldb + cw0;
-  if constexpr (IBL_FL_NT) {
+  if constexpr (NT) {
     typename NtVec<F>::T o;
 #pragma unroll
     for (int s = 0; s < V::N; ++s) o[s] = v[s];
@@ -171,10 +176,6 @@ __device__ __forceinline__ void fl_store_to(void* base, int ldb, int row, int cw
     for (int s = 0; s < V::N; ++s) V::set(o, s, v[s]);
     *reinterpret_cast<typename V::T*>(p) = o;
   }
-}
-template <typename F>
-__device__ __forceinline__ void fl_store(const FlArgs& a, int row, int cw0, const F (&v)[Vec<F>::N]) {
-  fl_store_to<F>(a.out, a.ldb, row, cw0, v);
 }
 
 template <typename F, int D>
@@ -205,8 +206,8 @@ struct FlOut {
 // the syndrome parity of the inputs (calc_syndrome, kernels_min_and_BP.cl:206-227: parity of m < 0):
 // a check's inputs are never -0, since the staged channel holds no -0 (fl_stage*, which turn -0 into +0:
 // equal values) and a variable's output clamp(ch + sum) is -0 only if every addend is.
-template <typename F, int D, int NC>
-__device__ __forceinline__ typename Bits<F>::U sign_xor(const F (&m)[D][NC], int s) {
+template <typename F, int D>
+__device__ __forceinline__ typename Bits<F>::U sign_xor(const F (&m)[D][Vec<F>::N], int s) {
   using Bt = Bits<F>;
   typename Bt::U x = Bt::of(m[0][s]);
 #pragma unroll
@@ -216,8 +217,8 @@ __device__ __forceinline__ typename Bits<F>::U sign_xor(const F (&m)[D][NC], int
 
 // Syndrome parity of codeword s's inputs: the sign bit of sign_xor (degrees <= 8); larger degrees keep
 // the compare-and-mask form (lane masks in SGPRs), which needs no VGPR beside the 16 inputs.
-template <typename F, int D, int NC>
-__device__ __forceinline__ bool syndrome_bit(const F (&m)[D][NC], int s) {
+template <typename F, int D>
+__device__ __forceinline__ bool syndrome_bit(const F (&m)[D][Vec<F>::N], int s) {
   if constexpr (D <= 8) {
     return (sign_xor<F, D>(m, s) >> (8 * sizeof(F) - 1)) != 0;
   } else {
@@ -255,50 +256,13 @@ __device__ __forceinline__ void fl_correction(const Args& a, F& ca, F& cb) {
   }
 }
 
-// Check-node body on the inputs m of NC codewords (min-sum, BP or corrected min-sum with alpha ca and
+// Check-node body on the inputs m of the lane's codewords (min-sum, BP or corrected min-sum with alpha ca and
 // beta cb); put(w, o) receives output w (any order of w).
-template <int KIND, typename F, int D, int NC, class Put>
-__device__ __forceinline__ void fl_cn_body(const F (&m)[D][NC], F lm, F ca, F cb, Put&& put) {
-  constexpr int N = NC;
+template <int KIND, typename F, int D, class Put>
+__device__ __forceinline__ void fl_cn_body(const F (&m)[D][Vec<F>::N], F lm, F ca, F cb, Put&& put) {
+  constexpr int N = Vec<F>::N;
   F o[N];
-  if constexpr (KIND == kFlCorrected) {
-    // corrected min-sum: the running (min, second min) pair of |m| as the degree > 8 body below, then the
-    // correction on those two values only (2 x {mul, sub, max} per check and codeword, whatever the degree;
-    // correcting the prefix / suffix form's outputs would cost 3 per edge). Output w takes the corrected
-    // second minimum where |m_w| is the minimum (on a tie both are equal) and the corrected minimum
-    // elsewhere: the closed form of the specification, since the correction is a function of the magnitude
-    // alone. r >= +0, so OR-ing the sign bit negates it; the sign of a zero is not specified. Per edge:
-    // 2 (running pair) + 1 (sign XOR) + 4 (compare, select, XOR, and-or), plus 6 per check (2 x {mul, sub, max}).
-    using Bt = Bits<F>;
-    using U = typename Bt::U;
-    F mn1[N], r1[N], r2[N];
-    U sg[N];
-    const U ks = Bt::sign_mask();
-#pragma unroll
-    for (int s = 0; s < N; ++s) {
-      F mn2 = Bt::hi_aa(m[0][s], m[1][s]);
-      mn1[s] = Bt::lo_aa(m[0][s], m[1][s]);
-      sg[s] = sign_xor<F, D>(m, s);
-#pragma unroll
-      for (int j = 2; j < D; ++j) {
-        mn2 = Bt::med3_a(mn1[s], mn2, m[j][s]);
-        mn1[s] = Bt::lo_a(mn1[s], m[j][s]);
-      }
-      r1[s] = fl_corrected(mn1[s], ca, cb);
-      r2[s] = fl_corrected(mn2, ca, cb);
-    }
-#pragma unroll
-    for (int w = 0; w < D; ++w) {
-#pragma unroll
-      for (int s = 0; s < N; ++s) {
-        const F mag = (fabs(m[w][s]) == mn1[s]) ? r2[s] : r1[s];
-        const U sx = sg[s] ^ Bt::of(m[w][s]);
-        // one v_and_or_b32 for degrees <= 8, the compiler's form above (as the plain degree > 8 body)
-        o[s] = Bt::from(D <= 8 ? Bt::and_or(sx, ks, Bt::of(mag)) : (sx & Bt::kSign) | Bt::of(mag));
-      }
-      put(w, o);
-    }
-  } else if constexpr (KIND == 0 && D <= 8) {
+  if constexpr (KIND == 0 && D <= 8) {
     // min-sum (kernels_min_and_BP.cl:156-162) with prefix / suffix minima: |out_w| = min over the others =
     // min(P_w, S_{w+1}), P_w = min |m_0..m_{w-1}|, S_j = min |m_j..m_{D-1}| — 3(D-2) v_min (|x| as an input
     // modifier) instead of the running (min, second min) pair plus a compare and a select per output
@@ -343,7 +307,8 @@ __device__ __forceinline__ void fl_cn_body(const F (&m)[D][NC], F lm, F ca, F cb
       }
       emit(D - 1, P);
     }
-  } else if constexpr (KIND == 0) {
+  } else if constexpr (KIND != 1) {
+    // min-sum at degrees > 8 and corrected min-sum at every degree, on the running (min, second min) pair.
     // min-sum (kernels_min_and_BP.cl:156-162): the fold t = sgn(m t) min(|t|, |m|) over the others of
     // output w only selects values, so |out_w| = min over the others = mn1, or mn2 where |m_w| is the
     // minimum (on a tie mn2 == mn1), and its sign is the XOR of the others' sign bits. A zero input
@@ -355,9 +320,16 @@ __device__ __forceinline__ void fl_cn_body(const F (&m)[D][NC], F lm, F ca, F cb
     // LLRs and selected messages, so each nonzero one is a multiple of the ulp q of the smallest nonzero
     // |channel LLR|; with that LLR >= 2^-50 (fp32; 2^-450 fp64) every product is >= 2^-146 and none
     // underflows (tests/test_gpu_float.py::test_float32_minsum_tiny_llrs runs that boundary bit-exactly).
+    // Corrected min-sum (kind 2): the correction on those two values only (2 x {mul, sub, max} per check and
+    // codeword, whatever the degree; correcting the prefix / suffix form's outputs would cost 3 per edge).
+    // Output w takes the corrected second minimum where |m_w| is the minimum (on a tie both are equal) and the
+    // corrected minimum elsewhere — the compare stays against the uncorrected mn1: the closed form of the
+    // specification, since the correction is a function of the magnitude alone. r >= +0, so OR-ing the sign
+    // bit negates it; the sign of a zero is not specified. Per edge: 2 (running pair) + 1 (sign XOR) +
+    // 4 (compare, select, XOR, and-or), plus 6 per check (2 x {mul, sub, max}).
     using Bt = Bits<F>;
     using U = typename Bt::U;
-    F mn1[N], mn2[N];
+    F mn1[N], mn2[N], r1[N], r2[N];   // r1, r2: the corrected pair (kind 2 only)
     U sg[N];
     const U ks = Bt::sign_mask();
 #pragma unroll
@@ -370,15 +342,22 @@ __device__ __forceinline__ void fl_cn_body(const F (&m)[D][NC], F lm, F ca, F cb
         mn2[s] = Bt::med3_a(mn1[s], mn2[s], m[j][s]);
         mn1[s] = Bt::lo_a(mn1[s], m[j][s]);
       }
+      if constexpr (KIND == kFlCorrected) {
+        r1[s] = fl_corrected(mn1[s], ca, cb);
+        r2[s] = fl_corrected(mn2[s], ca, cb);
+      }
     }
+    // the pair an output selects from: references, so the plain kind's code holds no copy of it
+    const F (&o1)[N] = KIND == kFlCorrected ? r1 : mn1;
+    const F (&o2)[N] = KIND == kFlCorrected ? r2 : mn2;
 #pragma unroll
     for (int w = 0; w < D; ++w) {
 #pragma unroll
       for (int s = 0; s < N; ++s) {
-        const F mag = (fabs(m[w][s]) == mn1[s]) ? mn2[s] : mn1[s];
+        const F mag = (fabs(m[w][s]) == mn1[s]) ? o2[s] : o1[s];
         const U sx = sg[s] ^ Bt::of(m[w][s]);
-        // degrees > 8 keep the compiler's form: the asm operand copies would push the 16-input body past
-        // the 128 VGPRs of a 1024-thread block
+        // one v_and_or_b32 for degrees <= 8; degrees > 8 keep the compiler's and / or form: the asm operand
+        // copies would push the 16-input body past the 128 VGPRs of a 1024-thread block
         o[s] = Bt::from(D <= 8 ? Bt::and_or(sx, ks, Bt::of(mag)) : (sx & Bt::kSign) | Bt::of(mag));
       }
       put(w, o);
@@ -458,14 +437,13 @@ __device__ __forceinline__ void fl_cn_item(const FlArgs& a, int node, int st, in
                                            bool& unsat) {
   using V = Vec<F>;
   constexpr int N = V::N;
-  const F* src = reinterpret_cast<const F*>(a.in);
   const F lm = (F)a.llr_max;
   int tg[D];   // output rows, loaded up front as scalars (the stores follow each output)
 #pragma unroll
   for (int w = 0; w < D; ++w) tg[w] = sload(a.tgt, st + w);
   F m[D][N];
 #pragma unroll
-  for (int j = 0; j < D; ++j) fl_row_load<F>(src + (size_t)(st + j) * a.ldb + cw0, m[j]);
+  for (int j = 0; j < D; ++j) fl_load16<kFlNt, F>(a.in, m[j], a.ldb, st + j, cw0);
   // fold record: wave-uniform (scalar) positions, rows and variables; the channel rows load with the inputs
   int fp0 = -1, fp1 = -1, fd0 = 0, fd1 = 0;
   F c0[N], c1[N];
@@ -475,9 +453,8 @@ __device__ __forceinline__ void fl_cn_item(const FlArgs& a, int node, int st, in
     fp1 = sload(fr, 1);
     fd0 = sload(fr, 2);
     fd1 = sload(fr, 3);
-    const F* ch = reinterpret_cast<const F*>(a.ch);
-    if (fp0 >= 0) fl_row_load<F>(ch + (size_t)sload(fr, 4) * a.ldb + cw0, c0);
-    if (fp1 >= 0) fl_row_load<F>(ch + (size_t)sload(fr, 5) * a.ldb + cw0, c1);
+    if (fp0 >= 0) fl_load16<kFlNt, F>(a.ch, c0, a.ldb, sload(fr, 4), cw0);
+    if (fp1 >= 0) fl_load16<kFlNt, F>(a.ch, c1, a.ldb, sload(fr, 5), cw0);
   }
   if (do_par) {
 #pragma unroll
@@ -487,13 +464,13 @@ __device__ __forceinline__ void fl_cn_item(const FlArgs& a, int node, int st, in
     F f[N];
 #pragma unroll
     for (int s = 0; s < N; ++s) f[s] = clampllr(c[s] + o[s], lm);
-    fl_store_to<F>(a.fout, a.ldb, row, cw0, f);
-    if (a.fold_mode == 2) fl_store<F>(a, tg[w], cw0, o);
+    fl_store16<kFlNt, F>(a.fout, f, a.ldb, row, cw0);
+    if (a.fold_mode == 2) fl_store16<kFlNt, F>(a.out, o, a.ldb, tg[w], cw0);
   };
   auto sink = [&](int w, const F (&o)[N]) __attribute__((always_inline)) {
     if (w == fp0) fold_put(w, c0, fd0, o);
     else if (w == fp1) fold_put(w, c1, fd1, o);
-    else fl_store<F>(a, tg[w], cw0, o);
+    else fl_store16<kFlNt, F>(a.out, o, a.ldb, tg[w], cw0);
   };
   FlOut<F, D> ob;
   F ca, cb;
@@ -504,9 +481,9 @@ __device__ __forceinline__ void fl_cn_item(const FlArgs& a, int node, int st, in
 }
 
 // Variable-node body on channel c and inputs m; put(w, o) receives extrinsic output w.
-template <typename F, int D, int NC, class Put>
-__device__ __forceinline__ void fl_vn_body(const F (&c)[NC], const F (&m)[D][NC], F lm, Put&& put) {
-  constexpr int N = NC;
+template <typename F, int D, class Put>
+__device__ __forceinline__ void fl_vn_body(const F (&c)[Vec<F>::N], const F (&m)[D][Vec<F>::N], F lm, Put&& put) {
+  constexpr int N = Vec<F>::N;
   F o[N];
   if constexpr (D == 1) {
 #pragma unroll
@@ -551,45 +528,51 @@ template <typename F, int D>
 __device__ __forceinline__ void fl_vn_item(const FlArgs& a, int node, int st, int cw0) {
   using V = Vec<F>;
   constexpr int N = V::N;
-  const F* src = reinterpret_cast<const F*>(a.in);
   const F lm = (F)a.llr_max;
   int tg[D];   // output rows, loaded up front as scalars (the stores follow each output)
 #pragma unroll
   for (int w = 0; w < D; ++w) tg[w] = sload(a.tgt, st + w);
   F c[N], m[D][N];
-  fl_row_load<F>(reinterpret_cast<const F*>(a.ch) + (size_t)node * a.ldb + cw0, c);
+  fl_load16<kFlNt, F>(a.ch, c, a.ldb, node, cw0);
 #pragma unroll
-  for (int j = 0; j < D; ++j) fl_row_load<F>(src + (size_t)(st + j) * a.ldb + cw0, m[j]);
-  auto sink = [&](int w, const F (&o)[N]) __attribute__((always_inline)) { fl_store<F>(a, tg[w], cw0, o); };
+  for (int j = 0; j < D; ++j) fl_load16<kFlNt, F>(a.in, m[j], a.ldb, st + j, cw0);
+  auto sink = [&](int w, const F (&o)[N]) __attribute__((always_inline)) {
+    fl_store16<kFlNt, F>(a.out, o, a.ldb, tg[w], cw0);
+  };
   FlOut<F, D> ob;
   fl_vn_body<F, D>(c, m, lm, [&](int w, const F (&o)[N]) __attribute__((always_inline)) { ob.put(w, o, sink); });
   ob.flush(sink);
 }
 
-int fl_vn_chunk(int prec, int maxd) { return 64 * (prec == kF32 ? 4 : 2); }
-
-#define FL_DEG_CASES(X) X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
-
+// Threads per block of every float node kernel: the one statement of the rule, read by the kernels'
+// __launch_bounds__ and by the host's launches (fl_kernel). maxd: the largest degree the kernel has a body
+// for (the check degree for the fused kernel).
 // MAXD = largest degree with a body in the switch (8 or 16): the registers of the degree-16 bodies
 // would cap every launch's occupancy, so codes with degrees <= 8 get their own instantiation.
 // 1024-thread blocks so a CU's waves share one work counter, except where the body needs more than
 // the 128 VGPRs such a block allows: the box-plus check node at MAXD=16 or in fp64, and the per-pass
-// fp32 min-sum check node at MAXD=16 (512 threads). The fused kernel keeps 1024 threads (its min-sum
-// MAXD=16 body fits in 128 VGPRs; 16 waves share the phases). Corrected min-sum (kind 2) takes plain
-// min-sum's block sizes here and in the fused kernel: its bodies need no private segment at either.
-template <int WHICH, int MAXD, int KIND = 0, typename F = float>
-constexpr int fl_block_of() {
-  return (WHICH == 0 && ((KIND == 1 && (MAXD > 8 || sizeof(F) == 8)) || (KIND != 1 && MAXD > 8 && sizeof(F) == 4)))
-             ? 512 : 1024;
+// fp32 min-sum check node at MAXD=16 (512 threads). The fused kernel: 1024 threads (16 waves share the
+// phases) unless the check bodies need more than 128 VGPRs (check degree > 8, or fp64 box-plus). Corrected
+// min-sum (kind 2) takes plain min-sum's block sizes here and in the fused kernel: its bodies need no private
+// segment at either. The small-batch kernels run kFlSmallBlock threads, the per-pass decision 256.
+constexpr int fl_block(FlFamily fam, FlPass pass, int kind, bool f64, int maxd) {
+  if (fam == kFlSmall) return kFlSmallBlock;
+  if (fam == kFlFused) return (maxd > 8 || (kind == 1 && f64)) ? 512 : 1024;
+  if (pass == kFlDecision) return 256;
+  return (pass == kFlCheck && ((kind == 1 && (maxd > 8 || f64)) || (kind != 1 && maxd > 8 && !f64))) ? 512 : 1024;
 }
-// fused kernel: 1024 threads (16 waves share the phases) unless the check bodies need more than 128 VGPRs
-// (check degree > 8, or fp64 box-plus)
-template <int CMAX, int KIND, typename F>
-constexpr int fl_fused_block_of() {
-  return (CMAX > 8 || (KIND == 1 && sizeof(F) == 8)) ? 512 : 1024;
-}
-static int fl_fused_block(int kind, int prec, int cmax) {
-  return (cmax > 8 || (kind == 1 && prec == kF64)) ? 512 : 1024;
+
+// The degree switch of every node kernel: calls f(std::integral_constant<int, D>{}) for the degree d of a node,
+// 2 <= D <= MAXD, and for D = 1 when ONE (variable nodes); other degrees have no body and do nothing.
+template <int MAXD, bool ONE, class Fn>
+__device__ __forceinline__ void fl_by_degree(int d, Fn&& f) {
+  switch (d) {
+    case 1: if constexpr (ONE) f(std::integral_constant<int, 1>{}); break;
+#define X(D) case D: if constexpr (D <= MAXD) f(std::integral_constant<int, D>{}); break;
+    X(2) X(3) X(4) X(5) X(6) X(7) X(8) X(9) X(10) X(11) X(12) X(13) X(14) X(15) X(16)
+#undef X
+    default: break;
+  }
 }
 
 // Items (node, chunk) are dealt to blocks round-robin ({b*wpb + w + nw*i}) and handed to the
@@ -600,7 +583,7 @@ __device__ __forceinline__ int fl_next_item(int* ctr, int lane, int wpb, int nw)
 }
 
 template <int KIND, typename F, int MAXD>
-__global__ __launch_bounds__((fl_block_of<0, MAXD, KIND, F>())) void fl_cn(FlArgs a) {
+__global__ __launch_bounds__(fl_block(kFlPerPass, kFlCheck, KIND, sizeof(F) == 8, MAXD)) void fl_cn(FlArgs a) {
   const int lane = fl_tid() & 63;
   if (!fl_gate(a.gate, lane)) return;
   constexpr int CWL = Vec<F>::N;
@@ -619,19 +602,16 @@ __global__ __launch_bounds__((fl_block_of<0, MAXD, KIND, F>())) void fl_cn(FlArg
     const int d = sload(a.deg, node), st = sload(a.start, node);
     const int cw0 = chunk * CH + lane * CWL;
     const int valid = a.B - cw0;
-    switch (d) {
-#define X(D) case D: if constexpr (D <= MAXD) fl_cn_item<KIND, F, D>(a, node, st, cw0, do_par, valid, unsat); break;
-      FL_DEG_CASES(X)
-#undef X
-      default: break;
-    }
+    fl_by_degree<MAXD, false>(d, [&](auto D) __attribute__((always_inline)) {
+      fl_cn_item<KIND, F, decltype(D)::value>(a, node, st, cw0, do_par, valid, unsat);
+    });
   }
   if (do_par && __ballot(unsat) != 0ull && lane == 0)
     atomicOr(&a.unsat[(fl_bid() * wpb + (fl_tid() >> 6)) & (kShards - 1)], 1);
 }
 
 template <typename F, int MAXD>
-__global__ __launch_bounds__((fl_block_of<1, MAXD>())) void fl_vn(FlArgs a) {
+__global__ __launch_bounds__(fl_block(kFlPerPass, kFlVariable, 0, sizeof(F) == 8, MAXD)) void fl_vn(FlArgs a) {
   const int lane = fl_tid() & 63;
   if (!fl_gate(a.gate, lane)) return;
   constexpr int CWL = Vec<F>::N;
@@ -648,26 +628,66 @@ __global__ __launch_bounds__((fl_block_of<1, MAXD>())) void fl_vn(FlArgs a) {
     const int node = a.nodes ? sload(a.nodes, pos) : pos;   // the fold's variable list skips folded nodes
     const int d = sload(a.deg, node), st = sload(a.start, node);
     const int cw0 = chunk * CH + lane * CWL;
-    switch (d) {
-      case 1: fl_vn_item<F, 1>(a, node, st, cw0); break;
-#define X(D) case D: if constexpr (D <= MAXD) fl_vn_item<F, D>(a, node, st, cw0); break;
-      FL_DEG_CASES(X)
-#undef X
-      default: break;
-    }
+    fl_by_degree<MAXD, true>(d, [&](auto D) __attribute__((always_inline)) {
+      fl_vn_item<F, decltype(D)::value>(a, node, st, cw0);
+    });
   }
 }
 
-// APP LLR = ch + sum of all inputs in ascending order, unclamped (kernels_min_and_BP.cl:196-202).
-// Wave item = (node, chunk of 64*N codewords); vector loads of every edge row, vector stores when the
-// user buffer is aligned (scalar tail otherwise).
+// APP LLR = ch + sum of all inputs in ascending order, unclamped (kernels_min_and_BP.cl:196-202): x holds the
+// channel values, load(k, r) fetches input k of the node's d. Before the first check pass (L == 0) there are no
+// inputs: the callers run this under `if (L > 0)` (inside this helper, the test cost every fused kernel a VGPR).
+template <typename F, class Load>
+__device__ __forceinline__ void fl_app_sum(F (&x)[Vec<F>::N], int d, Load&& load) {
+  for (int k = 0; k < d; ++k) {
+    F r[Vec<F>::N];
+    load(k, r);
+#pragma unroll
+    for (int s = 0; s < Vec<F>::N; ++s) x[s] = x[s] + r[s];
+  }
+}
+
+// The lane's APP LLRs x to the user's [N][B] output at element o = node * B + cw0; `valid` = B - cw0 of them
+// exist. One vector store where the output may vectorise (vec: out_aligned of the batch and the pointer) and
+// all Vec<F>::N exist, else element by element. The fp64 decoders' fp32 output takes an 8-byte float2:
+// vec is then out_aligned(B, out, 2, 4), B even and out % 8 == 0, and cw0 is a multiple of 2 (fused: 2 grp),
+// so o is even. The fp32 decoders' fp64 output (32 bytes) always goes element by element.
+template <typename F>
+__device__ __forceinline__ void fl_app_store(void* out, int out_dtype, size_t o, const F (&x)[Vec<F>::N], int vec,
+                                             int valid) {
+  constexpr int N = Vec<F>::N;
+  if (out_dtype == kF32) {
+    float* p = reinterpret_cast<float*>(out) + o;
+    if (vec && valid >= N) {
+      if constexpr (N == 4) *reinterpret_cast<float4*>(p) = make_float4((float)x[0], (float)x[1], (float)x[2], (float)x[3]);
+      else *reinterpret_cast<float2*>(p) = make_float2((float)x[0], (float)x[1]);
+      return;
+    }
+#pragma unroll
+    for (int s = 0; s < N; ++s)
+      if (s < valid) p[s] = (float)x[s];
+  } else {
+    double* p = reinterpret_cast<double*>(out) + o;
+    if constexpr (N == 2) {
+      if (vec && valid >= 2) {
+        *reinterpret_cast<double2*>(p) = make_double2((double)x[0], (double)x[1]);
+        return;
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < N; ++s)
+      if (s < valid) p[s] = (double)x[s];
+  }
+}
+
+// Decision of the per-pass path. Wave item = (node, chunk of 64*N codewords); vector loads of every edge row,
+// vector stores when the user buffer is aligned (scalar tail otherwise).
 template <typename F>
 __global__ __launch_bounds__(256) void fl_dec(FlDecArgs a) {
   using V = Vec<F>;
   constexpr int N = V::N, CH = 64 * N;
   const int L = __builtin_amdgcn_readfirstlane(*a.iters);
-  const F* vin = reinterpret_cast<const F*>((L & 1) ? a.vin1 : a.vin0);
-  const F* ch = reinterpret_cast<const F*>(a.ch);
+  const void* vin = (L & 1) ? a.vin1 : a.vin0;
   const int lane = fl_tid() & 63;
   const int gw = fl_bid() * (fl_bdim() >> 6) + (fl_tid() >> 6), nw = fl_gdim() * (fl_bdim() >> 6);
   const int nitems = a.n_nodes * a.nchunks;
@@ -678,38 +698,12 @@ __global__ __launch_bounds__(256) void fl_dec(FlDecArgs a) {
     if (cw0 >= a.B) continue;
     const int d = sload(a.deg, n), st = sload(a.start, n);
     F x[N];
-    {
-      const typename V::T r = *reinterpret_cast<const typename V::T*>(ch + (size_t)n * a.ldb + cw0);
-#pragma unroll
-      for (int s = 0; s < N; ++s) x[s] = V::get(r, s);
-    }
+    fl_load16<false, F>(a.ch, x, a.ldb, n, cw0);
     if (L > 0)
-      for (int v = 0; v < d; ++v) {
-        const typename V::T r = *reinterpret_cast<const typename V::T*>(vin + (size_t)(st + v) * a.ldb + cw0);
-#pragma unroll
-        for (int s = 0; s < N; ++s) x[s] = x[s] + V::get(r, s);
-      }
-    const size_t o = (size_t)n * a.B + cw0;
-    if (a.out_dtype == kF32) {
-      float* p = reinterpret_cast<float*>(a.out) + o;
-      if (a.aligned && cw0 + N <= a.B) {
-        if constexpr (N == 4) *reinterpret_cast<float4*>(p) = make_float4(x[0], x[1], x[2], x[3]);
-        else *reinterpret_cast<float2*>(p) = make_float2((float)x[0], (float)x[1]);
-      } else {
-#pragma unroll
-        for (int s = 0; s < N; ++s)
-          if (cw0 + s < a.B) p[s] = (float)x[s];
-      }
-    } else {
-      double* p = reinterpret_cast<double*>(a.out) + o;
-      if (a.aligned && cw0 + N <= a.B && N == 2) {
-        *reinterpret_cast<double2*>(p) = make_double2((double)x[0], (double)x[1]);
-      } else {
-#pragma unroll
-        for (int s = 0; s < N; ++s)
-          if (cw0 + s < a.B) p[s] = (double)x[s];
-      }
-    }
+      fl_app_sum<F>(x, d, [&](int v, F (&r)[N]) __attribute__((always_inline)) {
+        fl_load16<false, F>(vin, r, a.ldb, st + v, cw0);
+      });
+    fl_app_store<F>(a.out, a.out_dtype, (size_t)n * a.B + cw0, x, a.aligned, a.B - cw0);
   }
 }
 
@@ -896,14 +890,6 @@ __device__ __forceinline__ void fl_small_items(const Args& a, int lane, Body&& b
   }
 }
 
-template <typename F>
-__device__ __forceinline__ void fl_load_piece(const void* base, int ldb, int row, int cw0, F (&v)[Vec<F>::N]) {
-  using V = Vec<F>;
-  const typename V::T r = *reinterpret_cast<const typename V::T*>(reinterpret_cast<const F*>(base) + (size_t)row * ldb + cw0);
-#pragma unroll
-  for (int s = 0; s < V::N; ++s) v[s] = V::get(r, s);
-}
-
 template <int KIND, typename F, int D>
 __device__ __forceinline__ void fl_cn_small_item(const FlArgs& a, int st, int cw0, bool do_par, bool& unsat) {
   const F lm = (F)a.llr_max;
@@ -912,7 +898,7 @@ __device__ __forceinline__ void fl_cn_small_item(const FlArgs& a, int st, int cw
 #pragma unroll
   for (int j = 0; j < D; ++j) {
     tg[j] = a.tgt[st + j];
-    fl_load_piece<F>(a.in, a.ldb, st + j, cw0, m[j]);
+    fl_load16<false, F>(a.in, m[j], a.ldb, st + j, cw0);
   }
   if (do_par) {
     const int valid = a.B - cw0;
@@ -922,7 +908,7 @@ __device__ __forceinline__ void fl_cn_small_item(const FlArgs& a, int st, int cw
   F ca, cb;
   fl_correction<KIND, F>(a, ca, cb);
   fl_cn_body<KIND, F, D>(m, lm, ca, cb, [&](int w, const F (&o)[Vec<F>::N]) __attribute__((always_inline)) {
-    fl_store_to<F>(a.out, a.ldb, tg[w], cw0, o);
+    fl_store16<kFlNt, F>(a.out, o, a.ldb, tg[w], cw0);
   });
 }
 
@@ -931,14 +917,14 @@ __device__ __forceinline__ void fl_vn_small_item(const FlArgs& a, int node, int 
   const F lm = (F)a.llr_max;
   int tg[D];
   F c[Vec<F>::N], m[D][Vec<F>::N];
-  fl_load_piece<F>(a.ch, a.ldb, node, cw0, c);
+  fl_load16<false, F>(a.ch, c, a.ldb, node, cw0);
 #pragma unroll
   for (int j = 0; j < D; ++j) {
     tg[j] = a.tgt[st + j];
-    fl_load_piece<F>(a.in, a.ldb, st + j, cw0, m[j]);
+    fl_load16<false, F>(a.in, m[j], a.ldb, st + j, cw0);
   }
   fl_vn_body<F, D>(c, m, lm, [&](int w, const F (&o)[Vec<F>::N]) __attribute__((always_inline)) {
-    fl_store_to<F>(a.out, a.ldb, tg[w], cw0, o);
+    fl_store16<kFlNt, F>(a.out, o, a.ldb, tg[w], cw0);
   });
 }
 
@@ -950,12 +936,9 @@ __global__ __launch_bounds__(kFlSmallBlock) void fl_cn_small(FlArgs a) {
   bool unsat = false;
   fl_small_items<false>(a, lane, [&](int, int st, int c, int d) __attribute__((always_inline)) {
     const int cw0 = c * Vec<F>::N;
-    switch (d) {
-#define X(D) case D: if constexpr (D <= MAXD) fl_cn_small_item<KIND, F, D>(a, st, cw0, do_par, unsat); break;
-      FL_DEG_CASES(X)
-#undef X
-      default: break;
-    }
+    fl_by_degree<MAXD, false>(d, [&](auto D) __attribute__((always_inline)) {
+      fl_cn_small_item<KIND, F, decltype(D)::value>(a, st, cw0, do_par, unsat);
+    });
   });
   if (do_par && __ballot(unsat) != 0ull && lane == 0)
     atomicOr(&a.unsat[(fl_bid() * (fl_bdim() >> 6) + (fl_tid() >> 6)) & (kShards - 1)], 1);
@@ -967,13 +950,9 @@ __global__ __launch_bounds__(kFlSmallBlock) void fl_vn_small(FlArgs a) {
   if (!fl_gate(a.gate, lane)) return;
   fl_small_items<true>(a, lane, [&](int node, int st, int c, int d) __attribute__((always_inline)) {
     const int cw0 = c * Vec<F>::N;
-    switch (d) {
-      case 1: fl_vn_small_item<F, 1>(a, node, st, cw0); break;
-#define X(D) case D: if constexpr (D <= MAXD) fl_vn_small_item<F, D>(a, node, st, cw0); break;
-      FL_DEG_CASES(X)
-#undef X
-      default: break;
-    }
+    fl_by_degree<MAXD, true>(d, [&](auto D) __attribute__((always_inline)) {
+      fl_vn_small_item<F, decltype(D)::value>(a, node, st, cw0);
+    });
   });
 }
 
@@ -985,21 +964,14 @@ __global__ __launch_bounds__(kFlSmallBlock) void fl_dec_small(FlDecArgs a) {
   const int lane = fl_tid() & 63;
   fl_small_items<true>(a, lane, [&](int node, int st, int c, int d) __attribute__((always_inline)) {
     const int cw0 = c * Vec<F>::N;
-    F x[Vec<F>::N], r[Vec<F>::N];
-    fl_load_piece<F>(a.ch, a.ldb, node, cw0, x);
+    F x[Vec<F>::N];
+    fl_load16<false, F>(a.ch, x, a.ldb, node, cw0);
     if (L > 0)
-      for (int v = 0; v < d; ++v) {
-        fl_load_piece<F>(vin, a.ldb, st + v, cw0, r);
-#pragma unroll
-        for (int s = 0; s < Vec<F>::N; ++s) x[s] = x[s] + r[s];
-      }
-    const size_t o = (size_t)node * a.B + cw0;
-#pragma unroll
-    for (int s = 0; s < Vec<F>::N; ++s) {
-      if (cw0 + s >= a.B) break;
-      if (a.out_dtype == kF32) reinterpret_cast<float*>(a.out)[o + s] = (float)x[s];
-      else reinterpret_cast<double*>(a.out)[o + s] = (double)x[s];
-    }
+      fl_app_sum<F>(x, d, [&](int v, F (&r)[Vec<F>::N]) __attribute__((always_inline)) {
+        fl_load16<false, F>(vin, r, a.ldb, st + v, cw0);
+      });
+    // element stores only: this path never sets FlDecArgs::aligned
+    fl_app_store<F>(a.out, a.out_dtype, (size_t)node * a.B + cw0, x, 0, a.B - cw0);
   });
 }
 
@@ -1019,79 +991,55 @@ __global__ __launch_bounds__(kFlSmallBlock) void fl_dec_small(FlDecArgs a) {
 // Early stop is batch-global in the reference (stop when the WHOLE batch's syndrome is zero): pass 1
 // runs imax-1 iterations and records each CN pass's syndrome in the same flag words as the per-pass
 // path; finalize_iters turns them into L; pass 2 (dL set) re-runs the batch to L only if L < imax-1.
-// A message slot holds Vec<F>::N codewords (16 bytes); fused tasks work on a slice of NC of them (slice h:
-// codewords h*NC .. h*NC+NC-1), read and written as NC*sizeof(F) bytes at byte offset h*NC*sizeof(F).
-template <typename F, int NC> struct Slice;
-template <> struct Slice<float, 4> { using T = float4; };
-template <> struct Slice<float, 2> { using T = float2; };
-template <> struct Slice<double, 2> { using T = double2; };
-
-template <typename F, int NC>
-__device__ __forceinline__ void slice_load(const void* base, int slot, int h, F (&v)[NC]) {
-  const typename Slice<F, NC>::T r =
-      reinterpret_cast<const typename Slice<F, NC>::T*>(base)[slot * (Vec<F>::N / NC) + h];
-  const F* e = reinterpret_cast<const F*>(&r);
-#pragma unroll
-  for (int s = 0; s < NC; ++s) v[s] = e[s];
-}
-template <typename F, int NC>
-__device__ __forceinline__ void slice_store(void* base, int slot, int h, const F (&v)[NC]) {
-  typename Slice<F, NC>::T r;
-  F* e = reinterpret_cast<F*>(&r);
-#pragma unroll
-  for (int s = 0; s < NC; ++s) e[s] = v[s];
-  reinterpret_cast<typename Slice<F, NC>::T*>(base)[slot * (Vec<F>::N / NC) + h] = r;
-}
-
-template <int KIND, typename F, int D, int NC, int CNT = 0>
-__device__ __forceinline__ void fused_cn_item(void* msg, int first, int cnt_, int lane, int h, F lm, F ca, F cb,
+// A message slot holds Vec<F>::N codewords (16 bytes), and a task works on whole slots.
+template <int KIND, typename F, int D, int CNT = 0>
+__device__ __forceinline__ void fused_cn_item(typename Vec<F>::T* msg, int first, int cnt_, int lane, F lm, F ca, F cb,
                                               bool do_par, int valid, bool& unsat) {
+  constexpr int N = Vec<F>::N;
   // CNT > 0: a full task (CNT nodes) — the edge stride is a constant, so one address register serves all
   // D loads and stores through their immediate offsets
   const int cnt = CNT > 0 ? CNT : cnt_;
-  F m[D][NC];
+  F m[D][N];
 #pragma unroll
-  for (int j = 0; j < D; ++j) slice_load<F, NC>(msg, first + j * cnt + lane, h, m[j]);
+  for (int j = 0; j < D; ++j) fl_load16<false, F>(msg + (first + j * cnt + lane), m[j]);
   if (do_par) {
 #pragma unroll
-    for (int s = 0; s < NC; ++s) unsat |= syndrome_bit<F, D>(m, s) && h * NC + s < valid;
+    for (int s = 0; s < N; ++s) unsat |= syndrome_bit<F, D>(m, s) && s < valid;
   }
-  fl_cn_body<KIND, F, D>(m, lm, ca, cb, [&](int w, const F (&o)[NC]) __attribute__((always_inline)) {
-    slice_store<F, NC>(msg, first + w * cnt + lane, h, o);
+  fl_cn_body<KIND, F, D>(m, lm, ca, cb, [&](int w, const F (&o)[N]) __attribute__((always_inline)) {
+    fl_store16<false, F>(msg + (first + w * cnt + lane), o);
   });
 }
 
 // Variable-edge slot indices: staged into LDS as 16-bit values beside the messages (the fused path
 // requires the room for them, capi_float.hip fused_setup), row k of a task at sfirst + 64k: the D loads share
 // one address and take their row offsets as immediates.
-template <typename F, int D, int NC>
-__device__ __forceinline__ void fused_vn_item(void* msg, const void* chL, const uint16_t* vn_slot, int pos,
-                                              int sfirst, int lane, int h, F lm) {
+template <typename F, int D>
+__device__ __forceinline__ void fused_vn_item(typename Vec<F>::T* msg, const typename Vec<F>::T* chL,
+                                              const uint16_t* vn_slot, int pos, int sfirst, int lane, F lm) {
+  constexpr int N = Vec<F>::N;
   int sl[D];
 #pragma unroll
   for (int k = 0; k < D; ++k) sl[k] = vn_slot[sfirst + 64 * k + lane];
-  F c[NC], m[D][NC];
-  slice_load<F, NC>(chL, pos, h, c);
+  F c[N], m[D][N];
+  fl_load16<false, F>(chL + pos, c);
 #pragma unroll
-  for (int k = 0; k < D; ++k) slice_load<F, NC>(msg, sl[k], h, m[k]);
-  fl_vn_body<F, D>(c, m, lm, [&](int w, const F (&o)[NC]) __attribute__((always_inline)) {
-    slice_store<F, NC>(msg, sl[w], h, o);
+  for (int k = 0; k < D; ++k) fl_load16<false, F>(msg + sl[k], m[k]);
+  fl_vn_body<F, D>(c, m, lm, [&](int w, const F (&o)[N]) __attribute__((always_inline)) {
+    fl_store16<false, F>(msg + sl[w], o);
   });
 }
 
 // CMAX / VMAX: largest check / variable degree with a body (WLAN: checks <= 8, variables up to 11 ->
 // fl_fused<.., 8, 16>, without the 16-input check bodies' registers)
 template <int KIND, typename F, int CMAX, int VMAX>
-__global__ __launch_bounds__((fl_fused_block_of<CMAX, KIND, F>())) void fl_fused(FlFusedArgs a) {
+__global__ __launch_bounds__(fl_block(kFlFused, kFlCheck, KIND, sizeof(F) == 8, CMAX)) void fl_fused(FlFusedArgs a) {
   using V = Vec<F>;
   using VT = typename V::T;
   constexpr int N = V::N;
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   VT* msg = reinterpret_cast<VT*>(lds);
   VT* chL = msg + a.n_e;
-  // tasks take whole slots (slice 0 of N codewords): half slots (2 fp32 codewords per task, twice the
-  // tasks) measured 1.29x slower on C3 (WLAN N=1944) — the per-task latency, not the body, dominates
-  constexpr int NCs = N, h = 0;
   int* ctr = reinterpret_cast<int*>(chL + a.n_v);
   const int lane = fl_tid() & 63;
   const F lm = (F)a.llr_max;
@@ -1135,32 +1083,22 @@ __global__ __launch_bounds__((fl_fused_block_of<CMAX, KIND, F>())) void fl_fused
     // full tasks (64 nodes) run a body with the constant edge stride; it exists for degrees <= 8 only, and full
     // tasks of larger degrees take the general branch below (every lane < cnt = 64)
     if (cnt == 64 && d <= 8) {
-      switch (d) {
-#define X(D) case D: if constexpr (D <= CMAX && D <= 8) fused_cn_item<KIND, F, D, NCs, 64>(msg, first, cnt, lane, h, lm, ca, cb, do_par, valid, unsat); break;
-        FL_DEG_CASES(X)
-#undef X
-        default: break;
-      }
+      fl_by_degree<(CMAX < 8 ? CMAX : 8), false>(d, [&](auto D) __attribute__((always_inline)) {
+        fused_cn_item<KIND, F, decltype(D)::value, 64>(msg, first, cnt, lane, lm, ca, cb, do_par, valid, unsat);
+      });
     } else if (lane < cnt) {
-      switch (d) {
-#define X(D) case D: if constexpr (D <= CMAX) fused_cn_item<KIND, F, D, NCs>(msg, first, cnt, lane, h, lm, ca, cb, do_par, valid, unsat); break;
-        FL_DEG_CASES(X)
-#undef X
-        default: break;
-      }
+      fl_by_degree<CMAX, false>(d, [&](auto D) __attribute__((always_inline)) {
+        fused_cn_item<KIND, F, decltype(D)::value>(msg, first, cnt, lane, lm, ca, cb, do_par, valid, unsat);
+      });
     }
   };
   auto vn_task = [&](int t) __attribute__((always_inline)) {
     const int pos = sload(a.vn_task, 4 * t), cnt = sload(a.vn_task, 4 * t + 1);
     const int d = sload(a.vn_task, 4 * t + 2), sf = sload(a.vn_task, 4 * t + 3);
     if (lane < cnt) {
-      switch (d) {
-        case 1: fused_vn_item<F, 1, NCs>(msg, chL, vs, pos + lane, sf, lane, h, lm); break;
-#define X(D) case D: if constexpr (D <= VMAX) fused_vn_item<F, D, NCs>(msg, chL, vs, pos + lane, sf, lane, h, lm); break;
-        FL_DEG_CASES(X)
-#undef X
-        default: break;
-      }
+      fl_by_degree<VMAX, true>(d, [&](auto D) __attribute__((always_inline)) {
+        fused_vn_item<F, decltype(D)::value>(msg, chL, vs, pos + lane, sf, lane, lm);
+      });
     }
   };
   // APP output: ch + all inputs of the last CN pass in ascending edge order, unclamped
@@ -1170,41 +1108,12 @@ __global__ __launch_bounds__((fl_fused_block_of<CMAX, KIND, F>())) void fl_fused
     if (lane < cnt) {
       const int node = a.vn_node[pos + lane];
       F x[N];
-      {
-        const VT r = chL[pos + lane];
-#pragma unroll
-        for (int s = 0; s < N; ++s) x[s] = V::get(r, s);
-      }
+      fl_load16<false, F>(chL + pos + lane, x);
       if (L > 0)
-        for (int k = 0; k < d; ++k) {
-          const VT r = msg[vs[sf + 64 * k + lane]];
-#pragma unroll
-          for (int s = 0; s < N; ++s) x[s] = x[s] + V::get(r, s);
-        }
-      const size_t o = (size_t)node * a.B + cw0;
-      if (a.out_dtype == kF32) {
-        float* p = reinterpret_cast<float*>(a.out) + o;
-        if constexpr (N == 4) {
-          if (a.aligned && valid >= 4) {
-            *reinterpret_cast<float4*>(p) = make_float4((float)x[0], (float)x[1], (float)x[2], (float)x[3]);
-            return;
-          }
-        }
-#pragma unroll
-        for (int s = 0; s < N; ++s)
-          if (s < valid) p[s] = (float)x[s];
-      } else {
-        double* p = reinterpret_cast<double*>(a.out) + o;
-        if constexpr (N == 2) {
-          if (a.aligned && valid >= 2) {
-            *reinterpret_cast<double2*>(p) = make_double2((double)x[0], (double)x[1]);
-            return;
-          }
-        }
-#pragma unroll
-        for (int s = 0; s < N; ++s)
-          if (s < valid) p[s] = (double)x[s];
-      }
+        fl_app_sum<F>(x, d, [&](int k, F (&r)[N]) __attribute__((always_inline)) {
+          fl_load16<false, F>(msg + vs[sf + 64 * k + lane], r);
+        });
+      fl_app_store<F>(a.out, a.out_dtype, (size_t)node * a.B + cw0, x, a.aligned, valid);
     }
   };
 
@@ -1268,7 +1177,7 @@ hipError_t launch_fl_stage(const void* x, int in_dtype, int n, int B, void* dst,
 
 hipError_t launch_fl_stage_t(const void* x, int in_dtype, int n, int B, const int32_t* perm, void* dst, int prec,
                              int rule, int32_t* bad, hipStream_t s) {
-  const int cwl = prec == kF32 ? 4 : 2;
+  const int cwl = fl_cw_per_lane(prec);
   const size_t tiles = (size_t)((n + 63) / 64) * (size_t)((((B + cwl - 1) / cwl) + 31) / 32);
   const int grid = (int)std::max<size_t>(1, std::min<size_t>(tiles, 8192));
   if (prec == kF32)
@@ -1279,15 +1188,18 @@ hipError_t launch_fl_stage_t(const void* x, int in_dtype, int n, int B, const in
 }
 
 // Host-side operand checks before a launch: a missing array would fault the device, not fail the call.
-static bool fl_args_ok(const FlArgs& a, int which) {
+static bool fl_args_ok(FlFamily fam, FlPass pass, const FlArgs& a) {
+  if (fam == kFlSmall)
+    return a.info && a.task && a.in && a.out && a.tgt && (pass != kFlVariable || a.ch) && a.nwords >= 1 && a.ldb > 0 &&
+           a.B > 0;
   if (!a.out || !a.start || !a.deg || !a.tgt || a.ldb <= 0 || a.n_nodes < 0 || a.B <= 0 || a.B > a.ldb) return false;
-  if (which == 0) return a.in && (a.fold_mode == 0 || (a.fold && a.fout && a.ch));   // check pass
-  if (which == 1) return a.in && a.ch;                                              // variable pass
-  return a.ch != nullptr;                                                           // send
+  if (pass == kFlCheck) return a.in && (a.fold_mode == 0 || (a.fold && a.fout && a.ch));
+  if (pass == kFlVariable) return a.in && a.ch;
+  return a.ch != nullptr;   // send
 }
 
 hipError_t launch_fl_send(const FlArgs& a, int prec, hipStream_t s) {
-  if (!fl_args_ok(a, 2)) return hipErrorInvalidValue;
+  if (!fl_args_ok(kFlPerPass, kFlSend, a)) return hipErrorInvalidValue;
   const size_t total = (size_t)a.n_nodes * (a.ldb / 4);
   const int grid = (int)std::min<size_t>((total + 255) / 256, 8192);
   if (prec == kF32) hipLaunchKernelGGL(fl_send<float>, dim3(grid), dim3(256), 0, s, a);
@@ -1295,152 +1207,93 @@ hipError_t launch_fl_send(const FlArgs& a, int prec, hipStream_t s) {
   return hipGetLastError();
 }
 
-static const void* fl_kernel(int which, int kind, int prec, int maxd) {
-  const bool f32 = prec == kF32, small = maxd <= 8;
-  if (which == 0) {
-    if (kind == kFlCorrected)
-      return f32 ? (small ? (const void*)fl_cn<2, float, 8> : (const void*)fl_cn<2, float, 16>)
-                 : (small ? (const void*)fl_cn<2, double, 8> : (const void*)fl_cn<2, double, 16>);
-    if (kind == 0)
-      return f32 ? (small ? (const void*)fl_cn<0, float, 8> : (const void*)fl_cn<0, float, 16>)
-                 : (small ? (const void*)fl_cn<0, double, 8> : (const void*)fl_cn<0, double, 16>);
-    return f32 ? (small ? (const void*)fl_cn<1, float, 8> : (const void*)fl_cn<1, float, 16>)
-               : (small ? (const void*)fl_cn<1, double, 8> : (const void*)fl_cn<1, double, 16>);
-  }
-  return f32 ? (small ? (const void*)fl_vn<float, 8> : (const void*)fl_vn<float, 16>)
-             : (small ? (const void*)fl_vn<double, 8> : (const void*)fl_vn<double, 16>);
-}
-
-int fl_block(int which, int kind, int prec, int maxd) {
-  if (which == 0 && kind == 1 && (maxd > 8 || prec == kF64)) return fl_block_of<0, 16, 1, float>();
-  if (which == 0 && kind != 1 && maxd > 8 && prec == kF32) return fl_block_of<0, 16, 0, float>();
-  return fl_block_of<1, 8>();
-}
-
-hipError_t launch_fl_cn(const FlArgs& a, int kind, int prec, int maxd, int grid, hipStream_t s) {
-  if (!fl_args_ok(a, 0)) return hipErrorInvalidValue;
-  FlArgs args = a;
-  void* p[] = {&args};
-  return hipLaunchKernel(fl_kernel(0, kind, prec, maxd), dim3(grid), dim3(fl_block(0, kind, prec, maxd)), p, 0, s);
-}
-
-hipError_t launch_fl_vn(const FlArgs& a, int prec, int maxd, int grid, hipStream_t s) {
-  if (!fl_args_ok(a, 1)) return hipErrorInvalidValue;
-  FlArgs args = a;
-  void* p[] = {&args};
-  return hipLaunchKernel(fl_kernel(1, 0, prec, maxd), dim3(grid), dim3(fl_block(1, 0, prec, maxd)), p, 0, s);
-}
-
+// The one table of the node and decision kernels: entry point, threads per block (fl_block) and name of the
+// kernel of (family, pass, check-body kind, precision, largest check / variable degree). Degrees <= 8 take the
+// MAXD = 8 instantiations; the fused kernel is one kernel for every pass.
+struct FlKernel {
+  const void* fn;
+  int block;
+  const char* name;
+};
 template <int KIND, typename F>
-static const void* fl_fused_kernel_t(int cmax, int vmax) {
-  if (cmax <= 8) return vmax <= 8 ? (const void*)fl_fused<KIND, F, 8, 8> : (const void*)fl_fused<KIND, F, 8, 16>;
-  return (const void*)fl_fused<KIND, F, 16, 16>;
+static const void* fl_entry(FlFamily fam, FlPass pass, bool c8, bool v8) {
+  if (fam == kFlFused)
+    return !c8 ? (const void*)fl_fused<KIND, F, 16, 16>
+               : v8 ? (const void*)fl_fused<KIND, F, 8, 8> : (const void*)fl_fused<KIND, F, 8, 16>;
+  if (fam == kFlSmall) {
+    if (pass == kFlCheck) return c8 ? (const void*)fl_cn_small<KIND, F, 8> : (const void*)fl_cn_small<KIND, F, 16>;
+    if (pass == kFlVariable) return v8 ? (const void*)fl_vn_small<F, 8> : (const void*)fl_vn_small<F, 16>;
+    return (const void*)fl_dec_small<F>;
+  }
+  if (pass == kFlCheck) return c8 ? (const void*)fl_cn<KIND, F, 8> : (const void*)fl_cn<KIND, F, 16>;
+  if (pass == kFlVariable) return v8 ? (const void*)fl_vn<F, 8> : (const void*)fl_vn<F, 16>;
+  return (const void*)fl_dec<F>;
 }
-static const void* fl_fused_kernel(int kind, int prec, int cmax, int vmax) {
-  if (kind == 0) return prec == kF32 ? fl_fused_kernel_t<0, float>(cmax, vmax) : fl_fused_kernel_t<0, double>(cmax, vmax);
-  if (kind == kFlCorrected)
-    return prec == kF32 ? fl_fused_kernel_t<2, float>(cmax, vmax) : fl_fused_kernel_t<2, double>(cmax, vmax);
-  return prec == kF32 ? fl_fused_kernel_t<1, float>(cmax, vmax) : fl_fused_kernel_t<1, double>(cmax, vmax);
+static FlKernel fl_kernel(FlFamily fam, FlPass pass, int kind, int prec, int cmax, int vmax) {
+  static const char* const names[3][3] = {
+      {"fl_cn", "fl_vn", "fl_dec"}, {"fl_cn_small", "fl_vn_small", "fl_dec_small"}, {"fl_fused", "fl_fused", "fl_fused"}};
+  const bool f64 = prec != kF32, c8 = cmax <= 8, v8 = vmax <= 8;
+  const void* fn =
+      kind == 0 ? (f64 ? fl_entry<0, double>(fam, pass, c8, v8) : fl_entry<0, float>(fam, pass, c8, v8))
+      : kind == kFlCorrected ? (f64 ? fl_entry<2, double>(fam, pass, c8, v8) : fl_entry<2, float>(fam, pass, c8, v8))
+                             : (f64 ? fl_entry<1, double>(fam, pass, c8, v8) : fl_entry<1, float>(fam, pass, c8, v8));
+  const int maxd = (fam == kFlFused || pass == kFlCheck) ? cmax : vmax;
+  return {fn, fl_block(fam, pass, kind, f64, maxd), names[fam][pass]};
+}
+template <class Args>
+static hipError_t fl_launch(const FlKernel& k, const Args& a, int grid, size_t lds, hipStream_t s) {
+  Args args = a;
+  void* p[] = {&args};
+  return hipLaunchKernel(k.fn, dim3(grid), dim3(k.block), p, lds, s);
 }
 
-hipError_t fl_fused_occupancy(int kind, int prec, int cmax, int vmax, size_t lds, int* blocks_per_cu, int* block) {
-  const void* f = fl_fused_kernel(kind, prec, cmax, vmax);
-  *block = fl_fused_block(kind, prec, cmax);
-  hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
-  if (e != hipSuccess) return e;
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, f, *block, lds);
+hipError_t launch_fl_pass(FlFamily fam, FlPass pass, const FlArgs& a, int kind, int prec, int maxd, int grid,
+                          hipStream_t s) {
+  if (!fl_args_ok(fam, pass, a)) return hipErrorInvalidValue;
+  return fl_launch(fl_kernel(fam, pass, kind, prec, maxd, maxd), a, grid, 0, s);
+}
+
+hipError_t launch_fl_dec(FlFamily fam, const FlDecArgs& a, int prec, int grid, hipStream_t s) {
+  if (fam == kFlSmall && (!a.info || !a.task || !a.vin0 || !a.vin1 || !a.ch || !a.out || a.nwords < 1))
+    return hipErrorInvalidValue;
+  return fl_launch(fl_kernel(fam, kFlDecision, 0, prec, 0, 0), a, grid, 0, s);
 }
 
 hipError_t launch_fl_fused(const FlFusedArgs& a, int kind, int prec, int cmax, int vmax, int grid, size_t lds,
                            hipStream_t s) {
-  FlFusedArgs args = a;
-  void* p[] = {&args};
-  return hipLaunchKernel(fl_fused_kernel(kind, prec, cmax, vmax), dim3(grid),
-                         dim3(fl_fused_block(kind, prec, cmax)), p, lds, s);
+  return fl_launch(fl_kernel(kFlFused, kFlCheck, kind, prec, cmax, vmax), a, grid, lds, s);
 }
 
-static bool fl_small_ok(const FlArgs& a, bool vn) {
-  return a.info && a.task && a.in && a.out && a.tgt && (!vn || a.ch) && a.nwords >= 1 && a.ldb > 0 && a.B > 0;
-}
-template <int KIND>
-static const void* fl_cn_small_kernel(int prec, int maxd) {
-  if (prec == kF32) return maxd <= 8 ? (const void*)fl_cn_small<KIND, float, 8> : (const void*)fl_cn_small<KIND, float, 16>;
-  return maxd <= 8 ? (const void*)fl_cn_small<KIND, double, 8> : (const void*)fl_cn_small<KIND, double, 16>;
-}
-static const void* fl_small_kernel(int which, int kind, int prec, int maxd) {
-  if (which == 0)
-    return kind == 0 ? fl_cn_small_kernel<0>(prec, maxd)
-                     : kind == kFlCorrected ? fl_cn_small_kernel<2>(prec, maxd) : fl_cn_small_kernel<1>(prec, maxd);
-  if (which == 1)
-    return prec == kF32 ? (maxd <= 8 ? (const void*)fl_vn_small<float, 8> : (const void*)fl_vn_small<float, 16>)
-                        : (maxd <= 8 ? (const void*)fl_vn_small<double, 8> : (const void*)fl_vn_small<double, 16>);
-  return prec == kF32 ? (const void*)fl_dec_small<float> : (const void*)fl_dec_small<double>;
-}
-hipError_t launch_fl_cn_small(const FlArgs& a, int kind, int prec, int maxd, int grid, hipStream_t s) {
-  if (!fl_small_ok(a, false)) return hipErrorInvalidValue;
-  FlArgs args = a;
-  void* p[] = {&args};
-  return hipLaunchKernel(fl_small_kernel(0, kind, prec, maxd), dim3(grid), dim3(kFlSmallBlock), p, 0, s);
-}
-hipError_t launch_fl_vn_small(const FlArgs& a, int prec, int maxd, int grid, hipStream_t s) {
-  if (!fl_small_ok(a, true)) return hipErrorInvalidValue;
-  FlArgs args = a;
-  void* p[] = {&args};
-  return hipLaunchKernel(fl_small_kernel(1, 0, prec, maxd), dim3(grid), dim3(kFlSmallBlock), p, 0, s);
-}
-hipError_t launch_fl_dec_small(const FlDecArgs& a, int prec, int grid, hipStream_t s) {
-  if (!a.info || !a.task || !a.vin0 || !a.vin1 || !a.ch || !a.out || a.nwords < 1) return hipErrorInvalidValue;
-  FlDecArgs args = a;
-  void* p[] = {&args};
-  return hipLaunchKernel(fl_small_kernel(2, 0, prec, 0), dim3(grid), dim3(kFlSmallBlock), p, 0, s);
-}
-hipError_t fl_small_private_bytes(int kind, int prec, int cn_maxd, int vn_maxd, size_t* bytes, const char** name) {
-  const struct { const void* f; const char* n; } ks[] = {{fl_small_kernel(0, kind, prec, cn_maxd), "fl_cn_small"},
-                                                           {fl_small_kernel(1, kind, prec, vn_maxd), "fl_vn_small"},
-                                                           {fl_small_kernel(2, kind, prec, 0), "fl_dec_small"}};
-  *bytes = 0;
-  *name = "";
-  for (const auto& k : ks) {
-    hipFuncAttributes fa;
-    const hipError_t e = hipFuncGetAttributes(&fa, k.f);
+hipError_t fl_occupancy(FlFamily fam, FlPass pass, int kind, int prec, int cmax, int vmax, size_t lds,
+                        int* blocks_per_cu, int* block) {
+  const FlKernel k = fl_kernel(fam, pass, kind, prec, cmax, vmax);
+  *block = k.block;
+  if (fam == kFlFused) {
+    const hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
     if (e != hipSuccess) return e;
-    if (fa.localSizeBytes > *bytes) {
-      *bytes = fa.localSizeBytes;
-      *name = k.n;
-    }
   }
-  return hipSuccess;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, k.fn, k.block, lds);
 }
 
-hipError_t launch_fl_dec(const FlDecArgs& a, int prec, int grid, hipStream_t s) {
-  if (prec == kF32) hipLaunchKernelGGL(fl_dec<float>, dim3(grid), dim3(256), 0, s, a);
-  else hipLaunchKernelGGL(fl_dec<double>, dim3(grid), dim3(256), 0, s, a);
-  return hipGetLastError();
-}
-
-hipError_t fl_private_bytes(int kind, int prec, int cn_maxd, int vn_maxd, bool fused, size_t* bytes,
+hipError_t fl_private_bytes(FlFamily fam, int kind, int prec, int cn_maxd, int vn_maxd, bool fused, size_t* bytes,
                             const char** name) {
-  const struct { const void* f; const char* n; } ks[] = {
-      {fl_kernel(0, kind, prec, cn_maxd), "fl_cn"}, {fl_kernel(1, kind, prec, vn_maxd), "fl_vn"},
-      {fused ? fl_fused_kernel(kind, prec, cn_maxd, vn_maxd) : nullptr, "fl_fused"}};
+  FlKernel ks[3] = {fl_kernel(fam, kFlCheck, kind, prec, cn_maxd, vn_maxd),
+                    fl_kernel(fam, kFlVariable, kind, prec, cn_maxd, vn_maxd), {}};
+  if (fam == kFlSmall) ks[2] = fl_kernel(fam, kFlDecision, kind, prec, 0, 0);
+  else if (fused) ks[2] = fl_kernel(kFlFused, kFlCheck, kind, prec, cn_maxd, vn_maxd);
   *bytes = 0;
   *name = "";
-  for (const auto& k : ks) {
-    if (!k.f) continue;
+  for (const FlKernel& k : ks) {
+    if (!k.fn) continue;
     hipFuncAttributes fa;
-    const hipError_t e = hipFuncGetAttributes(&fa, k.f);
+    const hipError_t e = hipFuncGetAttributes(&fa, k.fn);
     if (e != hipSuccess) return e;
     if (fa.localSizeBytes > *bytes) {
       *bytes = fa.localSizeBytes;
-      *name = k.n;
+      *name = k.name;
     }
   }
   return hipSuccess;
-}
-
-hipError_t fl_occupancy(int which, int kind, int prec, int maxd, int* blocks_per_cu) {
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, fl_kernel(which, kind, prec, maxd),
-                                                      fl_block(which, kind, prec, maxd), 0);
 }
 
 }  // namespace ibl

@@ -417,10 +417,11 @@ FLOAT_OFFSET_CASES = [(F32, F32, 4, F32, 0), (F64, F64, 8, F64, 0), (F32, F32, 0
 @pytest.mark.parametrize("prec,in_dt,in_off,out_dt,out_off", FLOAT_OFFSET_CASES,
                          ids=[f"{str(c[0])[6:]}-{str(c[1])[6:]}+{c[2]}-{str(c[3])[6:]}+{c[4]}"
                               for c in FLOAT_OFFSET_CASES])
-@pytest.mark.parametrize("path,B", [("fused", 8), ("passes", 72)])
+@pytest.mark.parametrize("path,B", [("fused", 8), ("passes", 72), ("passes", 8)])
 def test_float_offset_buffers(eng, wlan, path, B, prec, in_dt, in_off, out_dt, out_off):
     """Min-sum (i_max = 4) with LLR and output buffers off the vector alignment, whole words (B % 4 == 0) so that
-    only the pointer decides: bit-equal to the oracle, nothing written outside the output elements."""
+    only the pointer decides: bit-equal to the oracle, nothing written outside the output elements. B = 8 on
+    path="passes" takes the small-batch kernels, B = 72 the per-pass ones."""
     g, G = wlan
     x64, refs = _mix_case(g, B, imax=4)
     ref, _ = refs[(prec == F32, in_dt == F32)]
