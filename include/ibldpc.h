@@ -409,7 +409,8 @@ void ibl_layered_destroy(ibl_layered* h);
 
 /*
  * Layered min-sum, fixed point: a second arithmetic of the layered decoder above, integer throughout — 8-bit APP
- * values, messages saturated at q_max (6 bits at most) — on the per-layer path over HBM.  Layers, the per-codeword
+ * values, messages saturated at q_max (6 bits at most) — on the per-layer path over HBM (ibl_layered_create_fixed) or fused
+ * on chip for the codes that fit (ibl_layered_create_fixed_fused).  Layers, the per-codeword
  * early stop, the handle type and ibl_layered_decode / _path_in_use / _geometry / _destroy are those above.
  *
  * Parameters:  alpha16  int 0..16   normalisation in sixteenths (13 is the project's 0.8125)
@@ -440,7 +441,8 @@ void ibl_layered_destroy(ibl_layered* h);
  * ibl_layered_create_fixed  validates as ibl_layered_create_path does.  Out-of-range parameters, imax or max_batch
  *   < 1 and an unknown path are IBL_EINVAL; IBL_PATH_FUSED is IBL_EUNSUPPORTED (the fixed-point fused kernel is not
  *   built); IBL_PATH_PASSES and IBL_PATH_AUTO give the per-layer kernels.  The parameters are judged before the
- *   graph, so these refusals need no device.
+ *   graph, so these refusals need no device.  The fused on-chip kernel of this arithmetic has an entry point of its
+ *   own, ibl_layered_create_fixed_fused (below); this function never chooses it.
  *   Layout: a lane owns 4 consecutive codewords and a wave updates one check for 256.  The handle owns, allocated at
  *   create for ldb = max_batch rounded up to 256 codewords, the APP values [N][ldb] int8 and ONE 32-bit state word
  *   per check and codeword [n_c][ldb] (corrected m2 << 26 | corrected m1 << 20 | first argmin position << 16 | the
@@ -461,11 +463,37 @@ void ibl_layered_destroy(ibl_layered* h);
  *   but the last when early_stop is set, output) with the same guarantees: no allocation, no host synchronisation,
  *   no read-back; finished and padding codewords store nothing that reaches the caller; a finished codeword's values
  *   are frozen at its stop iteration.
- * ibl_layered_is_fixed  *fixed = 1 for a handle of ibl_layered_create_fixed, 0 otherwise.
+ * ibl_layered_create_fixed_fused  the same arithmetic, bit for bit, in the fused on-chip form of the fp32 decoder: one
+ *   wave owns one codeword in LDS through all iterations, one launch per decode, and a wave whose codeword's syndrome
+ *   is zero takes its next codeword at once.  Validation as ibl_layered_create_fixed, the parameters before the
+ *   graph: out-of-range alpha16 / beta_q / q_max / scale, imax or max_batch < 1 and a NULL out are IBL_EINVAL, then
+ *   "graph is NULL", then the layers.
+ *   Fit rule: a codeword occupies  cw_bytes = ldn + 4 n_c  bytes of LDS (wide: ldn + 8 n_c), ldn = N rounded up to a
+ *   multiple of 4, and a workgroup keeps  cw_per_group = min(4, floor(160 KiB / cw_bytes))  codewords, one wave
+ *   each (WLAN N = 1944: 5,832 bytes, 28 would fit; N = 16200, n_c = 9000: 52,200 bytes, 3 codewords, where the fp32
+ *   fused kernel's 172,800 do not fit).  cw_per_group = 0 is IBL_EUNSUPPORTED with cw_bytes and the 160 KiB in the
+ *   message (DVB-S2 N = 64800: use ibl_layered_create_fixed).  Several workgroups share a CU, so the cap of 4 costs
+ *   no occupancy; IBL_LAYFIX_FUSED_CW = 1..16 in the environment at create replaces it (a measurement aid).
+ *   LDS layout of a wave's slice: P[ldn] int8 APP values, then S[n_c], the state word of ibl_layered_create_fixed;
+ *   a wide handle has S[n_c] then S1[n_c], its two state words.  P is read and written with byte accesses.
+ *   Memory owned: the fp32 fused decoder's device plan (4 words per task, 64 variable indices per task and edge
+ *   position) and a [max_batch][ldn] int8 staging buffer; nothing per check and codeword in device memory.
+ *   ibl_layered_decode on such a handle takes llr_dtype and out_dtype in {IBL_F32, IBL_I8} in any combination
+ *   (anything else is IBL_EINVAL; B > max_batch is IBL_EINVAL); d_out may be d_llr when the dtypes match.  It
+ *   enqueues THREE launches at any imax — stage-in (64 x 64 tile transpose into the staging buffer, quantising
+ *   IBL_F32 or copying IBL_I8 with -128 -> -127), the fused kernel, stage-out (transpose back, int8 or
+ *   f32(P) / f32(scale)) — with no allocation, no host synchronisation and no read-back: capturable.
+ *   ibl_layered_path_in_use gives 1, ibl_layered_is_fixed 1, ibl_layered_is_wide as for any handle,
+ *   ibl_layered_geometry the real (cw_per_group, ngroups, grid); ibl_layered_set_compaction and
+ *   ibl_layered_compaction_stats refuse with IBL_EUNSUPPORTED.
+ * ibl_layered_is_fixed  *fixed = 1 for a handle of ibl_layered_create_fixed or _fixed_fused, 0 otherwise.
  */
 int ibl_layered_create_fixed(const ibl_graph* g, int32_t n_layers, const int32_t* layer_ptr,
                              const int32_t* layer_checks, int32_t imax, int32_t alpha16, int32_t beta_q, int32_t q_max,
                              float scale, int32_t max_batch, int32_t path, ibl_layered** out);
+int ibl_layered_create_fixed_fused(const ibl_graph* g, int32_t n_layers, const int32_t* layer_ptr,
+                                   const int32_t* layer_checks, int32_t imax, int32_t alpha16, int32_t beta_q,
+                                   int32_t q_max, float scale, int32_t max_batch, ibl_layered** out);
 int ibl_layered_is_fixed(const ibl_layered* h, int32_t* fixed);
 
 /*

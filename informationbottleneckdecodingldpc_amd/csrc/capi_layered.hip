@@ -1,6 +1,7 @@
 // C ABI (include/ibldpc.h): the layered normalised / offset min-sum decoder (layered_plan.h, layered_kernels.hip):
 // the fused on-chip kernel for codes whose codeword state fits the LDS, the per-layer path over HBM otherwise, and
-// the fixed-point arithmetic on the per-layer path (ibl_layered_create_fixed).
+// the fixed-point arithmetic on the per-layer path (ibl_layered_create_fixed) and fused on chip
+// (ibl_layered_create_fixed_fused).
 #include <cmath>
 #include <cstring>
 
@@ -41,6 +42,10 @@ struct ibl_layered {
   // PO [n_c][ldb] on the fp32 per-layer path, S1 [n_c][ldb] in fixed point (the fused kernel's PO is in LDS)
   int32_t wide = 0;
   DevBuf<uint32_t> PO, S1;
+  // fixed point, fused on chip (ibl_layered_create_fixed_fused; fixed = 1, fused = 1): task, idx, n_tasks,
+  // cw_per_group, cw_bytes and bpc as on the fp32 fused handle, and the [max_batch][ldn] int8 codeword rows of
+  // layered_plan.h fixfused_buf_bytes(n_v, max_batch)
+  DevBuf<int8_t> buf8;
 };
 
 namespace {
@@ -145,6 +150,24 @@ int layered_run_fixed(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int3
     if (early_stop && it < h->imax) HIPCHK(launch_layfix_stop(a, it, s));
   }
   HIPCHK(launch_layfix_stage_out(a, d_out, out_dtype, s));
+  return IBL_OK;
+}
+
+// stage-in, the fused kernel, stage-out: three launches at any imax
+int layered_run_fixed_fused(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out,
+                            int32_t out_dtype, int32_t early_stop, int32_t* d_iters, hipStream_t s) {
+  const ibl_graph* g = h->g;
+  HIPCHK(launch_layfix_fused_stage_in(d_llr, llr_dtype, h->buf8, g->n_v, B, h->scale, s));
+  LayFixFusedArgs a{};
+  a.buf = h->buf8; a.task = h->task; a.idx = h->idx; a.iters = d_iters;
+  a.alpha16 = h->alpha16; a.beta_q = h->beta_q; a.q_max = h->q_max;
+  a.n_v = g->n_v; a.ldn = fixfused_ldn(g->n_v); a.n_c = g->n_c; a.n_tasks = h->n_tasks; a.B = B; a.imax = h->imax;
+  a.early = early_stop ? 1 : 0;
+  a.cw_per_group = h->cw_per_group; a.cw_bytes = (int32_t)h->cw_bytes;
+  int32_t grid = 0;
+  layered_geometry(h, B, &a.ngroups, &grid);
+  HIPCHK(launch_layfix_fused(a, h->wide != 0, grid, (size_t)h->cw_per_group * h->cw_bytes, s));
+  HIPCHK(launch_layfix_fused_stage_out(h->buf8, d_out, out_dtype, g->n_v, B, h->scale, s));
   return IBL_OK;
 }
 }  // namespace
@@ -261,6 +284,61 @@ int ibl_layered_create_fixed(const ibl_graph* g, int32_t n_layers, const int32_t
   return IBL_OK;
 }
 
+int ibl_layered_create_fixed_fused(const ibl_graph* g, int32_t n_layers, const int32_t* layer_ptr,
+                                   const int32_t* layer_checks, int32_t imax, int32_t alpha16, int32_t beta_q,
+                                   int32_t q_max, float scale, int32_t max_batch, ibl_layered** out) {
+  if (!out) return fail(IBL_EINVAL, "out is NULL");
+  *out = nullptr;
+  if (imax < 1 || max_batch < 1) return fail(IBL_EINVAL, "imax and max_batch must be >= 1");
+  if (!fix_params_ok(alpha16, beta_q, q_max))
+    return fail(IBL_EINVAL, "alpha16 must lie in [0, 16], beta_q in [0, 63], q_max in [1, 63]");
+  if (!(scale > 0.f) || std::isinf(scale)) return fail(IBL_EINVAL, "scale must be finite and > 0");
+  if (!g) return fail(IBL_EINVAL, "graph is NULL");
+  const std::vector<int32_t> ip = graph_indptr(g);
+  int rc = ibl_layers_validate(g->n_v, g->n_c, ip.data(), g->h_cols.data(), n_layers, layer_ptr, layer_checks);
+  if (rc) return rc;
+  const bool wide = layered_is_wide(g->n_c, ip.data());
+  // IBL_LAYFIX_FUSED_CW=1..16 replaces the cap on the codewords of a workgroup (DESIGN.md "Layered min-sum: fixed
+  // point, fused" for the numbers); read at create
+  int32_t cap = kLayFixFusedMaxCw;
+  if (const char* v = getenv("IBL_LAYFIX_FUSED_CW")) {
+    cap = atoi(v);
+    if (cap < 1 || cap > kLayFixFusedBoundCw) return fail(IBL_EINVAL, "IBL_LAYFIX_FUSED_CW must lie in [1, 16]");
+  }
+  const size_t cw_bytes = fixfused_cw_bytes(g->n_v, g->n_c, wide);
+  const int32_t cw = fixfused_cw_per_group(g->n_v, g->n_c, wide, cap);
+  if (cw < 1)
+    return fail(IBL_EUNSUPPORTED, std::string("code does not fit the fixed-point fused kernel: one codeword needs "
+                                              "cw_bytes = ") + (wide ? "N + 8 n_c = " : "N + 4 n_c = ") +
+                                      std::to_string(cw_bytes) + " bytes of LDS, a workgroup has " +
+                                      std::to_string(kLayLds) + " (160 KiB): use ibl_layered_create_fixed");
+  if (fixfused_stage_tiles(g->n_v, max_batch) > 0x7fffffffll)
+    return fail(IBL_EINVAL, "max_batch is too large for the staging kernels' grid");
+  LayeredPlan pl;
+  plan_layered(g->n_v, g->n_c, ip.data(), g->h_cols.data(), n_layers, layer_ptr, layer_checks, &pl);
+  HIPCHK(hipSetDevice(g->device));
+  std::unique_ptr<ibl_layered> h(new ibl_layered());
+  h->g = g; h->imax = imax; h->max_batch = max_batch;
+  h->fused = 1; h->fixed = 1; h->wide = wide;
+  h->alpha16 = alpha16; h->beta_q = beta_q; h->q_max = q_max; h->scale = scale;
+  h->n_tasks = pl.n_tasks; h->cw_per_group = cw; h->cw_bytes = cw_bytes;
+  if ((rc = h->task.upload(pl.task)) || (rc = h->idx.upload(pl.idx)) ||
+      (rc = h->buf8.alloc(fixfused_buf_bytes(g->n_v, max_batch))))
+    return rc;
+  int bpc = 0;
+  size_t priv = 0;
+  const hipError_t e = layfix_fused_occupancy(wide, cw, (size_t)cw * cw_bytes, &bpc, &priv);
+  if (e != hipSuccess)
+    return fail(IBL_EHIP, std::string("fixed-point fused kernel occupancy: ") + hipGetErrorString(e));
+  if (bpc < 1) return fail(IBL_EHIP, "no occupancy for the fixed-point fused kernel");
+  if ((rc = refuse_private(priv, "a fixed-point fused layered kernel has a ",
+                           "-byte private segment (register spill): rebuild required")))
+    return rc;
+  h->bpc = bpc;
+  *out = h.release();
+  return IBL_OK;
+}
+
 int ibl_layered_is_fixed(const ibl_layered* h, int32_t* fixed) {
   if (!h || !fixed) return fail(IBL_EINVAL, "NULL argument");
   *fixed = h->fixed;
@@ -346,6 +424,9 @@ int ibl_layered_decode(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int
       return fail(IBL_EINVAL, "LLR dtypes of a fixed-point decoder must be IBL_F32 or IBL_I8");
     if (!d_llr || !d_out) return fail(IBL_EINVAL, "NULL buffer");
     HIPCHK(hipSetDevice(h->g->device));
+    if (h->fused)
+      return layered_run_fixed_fused(h, d_llr, llr_dtype, B, d_out, out_dtype, early_stop, d_iters,
+                                     (hipStream_t)stream);
     return layered_run_fixed(h, d_llr, llr_dtype, B, d_out, out_dtype, early_stop, d_iters, (hipStream_t)stream);
   }
   if (llr_dtype == kF64 || out_dtype == kF64) return fail(IBL_EUNSUPPORTED, "the layered decoder is fp32 only");

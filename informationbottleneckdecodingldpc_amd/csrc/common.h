@@ -440,4 +440,23 @@ hipError_t layfix_private_bytes(size_t* bytes);
 // over the kernels only a wide handle launches, fp32 and fixed point
 hipError_t lay_wide_private_bytes(size_t* bytes);
 
+// Fixed point, fused on chip (layered_plan.h "fixed point, fused"): one wave per codeword as LayeredArgs, the
+// wave's LDS slice P[ldn] int8 | S[n_c] (wide: | S1[n_c]).
+struct LayFixFusedArgs {
+  int8_t* buf;              // [B][ldn] codeword rows: quantised channel values in, APP values out (in place)
+  const int32_t* task;      // the fp32 fused kernel's plan (LayeredPlan)
+  const int32_t* idx;
+  int32_t* iters;           // [B] or nullptr
+  int32_t alpha16, beta_q, q_max;
+  int32_t n_v, ldn, n_c, n_tasks, B, imax, early, ngroups, cw_per_group, cw_bytes;
+};
+hipError_t layfix_fused_occupancy(bool wide, int cw_per_group, size_t lds, int* blocks_per_cu, size_t* private_bytes);
+hipError_t launch_layfix_fused(const LayFixFusedArgs& a, bool wide, int grid, size_t lds, hipStream_t s);
+// buf[b][v] = the quantised (kF32, by `scale`) or copied (kI8, -128 -> -127) llr[v][b]; the row padding 0
+hipError_t launch_layfix_fused_stage_in(const void* llr, int32_t dtype, int8_t* buf, int n_v, int B, float scale,
+                                        hipStream_t s);
+// out[v][b] = buf[b][v] (kI8) or f32(buf[b][v]) / scale (kF32)
+hipError_t launch_layfix_fused_stage_out(const int8_t* buf, void* out, int32_t dtype, int n_v, int B, float scale,
+                                         hipStream_t s);
+
 }  // namespace ibl

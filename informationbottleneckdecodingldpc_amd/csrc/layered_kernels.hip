@@ -1241,6 +1241,256 @@ hipError_t lay_wide_private_bytes(size_t* bytes) {
                            bytes);
 }
 
+// ---------------------------------------------------------------------------------------------------------------
+// Fixed point, fused on chip (include/ibldpc.h "Layered min-sum, fixed point", the fused kernel; layered_plan.h
+// "fixed point, fused").
+//
+// lay_fused_body in integers: one wave owns one codeword, lane = check of a task, the fp32 kernel's plan, loop over
+// groups and per-codeword stop. The wave's slice of LDS is P[ldn] int8 and one state word per check S[n_c]
+// (fix_state_word; wide: S and S1, fix_state_words_wide), a quarter to a third of the fp32 slice. The arithmetic is
+// layfix_minsum with the lane's D bytes in the low bytes of p[] and j = 0.
+// P is read and written one BYTE per lane and edge (ds_read_i8 / ds_write_b8): a layer's checks share no variable,
+// so no two lanes of a task touch the same byte, but they do touch different bytes of one dword in one instruction,
+// which only a byte store keeps apart (a dword read-modify-write would lose the neighbours' updates).
+namespace {
+
+template <int D, bool kWide>
+__device__ __forceinline__ void layfix_cn(int8_t* __restrict__ P, uint32_t* __restrict__ S, uint32_t* __restrict__ S1,
+                                          const int32_t* __restrict__ idx, int slot, int alpha16, int beta, int qm) {
+  static_assert(D <= (kWide ? kLayWideMaxD : kLayMaxD), "degree body out of range");
+  int v[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) v[k] = idx[64 * k];
+  uint32_t p[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) p[k] = (uint32_t)(int32_t)P[v[k]];
+  int m1, m2;
+  uint32_t pos, sg;
+  if constexpr (kWide) {
+    const uint32_t w0 = S[slot];
+    m1 = (int)fix_wide_m1(w0);
+    m2 = (int)fix_wide_m2(w0);
+    pos = fix_wide_pos(w0);
+    sg = S1[slot];
+  } else {
+    const uint32_t w = S[slot];
+    m1 = (int)((w >> 20) & 63u);
+    m2 = (int)(w >> 26);
+    pos = (w >> 16) & 15u;
+    sg = w;
+  }
+  layfix_minsum<D>(p, 0, m1, m2, pos, sg, alpha16, beta, qm);
+#pragma unroll
+  for (int k = 0; k < D; ++k) P[v[k]] = (int8_t)p[k];
+  if constexpr (kWide) {
+    const FixWideWords w = fix_state_words_wide((uint32_t)m1, (uint32_t)m2, pos, sg);
+    S[slot] = w.w0;
+    S1[slot] = w.w1;
+  } else {
+    S[slot] = fix_state_word((uint32_t)m1, (uint32_t)m2, pos, sg);
+  }
+}
+
+template <bool kWide>
+__device__ __forceinline__ void layfix_cn_any(int d, int8_t* P, uint32_t* S, uint32_t* S1, const int32_t* idx,
+                                              int slot, int alpha16, int beta, int qm) {
+#define LAY_CASE(D) case D: layfix_cn<D, kWide>(P, S, S1, idx, slot, alpha16, beta, qm); break;
+  if constexpr (kWide) {
+    switch (d) {
+      LAY_CASES_32
+      default: break;
+    }
+  } else {
+    switch (d) {
+      LAY_CASES_16
+      default: break;
+    }
+  }
+#undef LAY_CASE
+}
+
+template <bool kWide>
+__device__ __forceinline__ void layfix_fused_body(const LayFixFusedArgs a) {
+  extern __shared__ __align__(16) unsigned char lay_lds[];
+  const int lane = (int)(threadIdx.x & 63u);
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int ncw = a.cw_per_group;
+  if (wave >= ncw) return;
+  unsigned char* base = lay_lds + (size_t)wave * (size_t)a.cw_bytes;   // cw_bytes and ldn are multiples of 4
+  int8_t* P = reinterpret_cast<int8_t*>(base);
+  uint32_t* S = reinterpret_cast<uint32_t*>(base + a.ldn);
+  uint32_t* S1 = kWide ? S + a.n_c : nullptr;
+  const int alpha16 = a.alpha16, beta = a.beta_q, qm = a.q_max;
+  for (int g = (int)blockIdx.x; g < a.ngroups; g += (int)gridDim.x) {
+    const int b = g * ncw + wave;
+    if (b >= a.B) break;   // wave-uniform; later groups of this workgroup lie further still
+    int8_t* row = a.buf + (size_t)b * (size_t)a.ldn;
+    for (int v = 4 * lane; v < a.ldn; v += 256)
+      *reinterpret_cast<uint32_t*>(P + v) = *reinterpret_cast<const uint32_t*>(row + v);
+    for (int c = lane; c < a.n_c; c += 64) {
+      S[c] = 0u;
+      if constexpr (kWide) S1[c] = 0u;
+    }
+    __builtin_amdgcn_wave_barrier();
+    int it = 1;
+    for (;; ++it) {
+      for (int t = 0; t < a.n_tasks; ++t) {
+        const int first = sload(a.task, 4 * t), cnt = sload(a.task, 4 * t + 1), d = sload(a.task, 4 * t + 2),
+                  s0 = sload(a.task, 4 * t + 3);
+        if (lane < cnt) layfix_cn_any<kWide>(d, P, S, S1, a.idx + first + lane, s0 + lane, alpha16, beta, qm);
+        __builtin_amdgcn_wave_barrier();   // the next task's reads stay behind this task's writes (other lanes')
+      }
+      if (it >= a.imax) break;
+      if (a.early) {
+        // syndrome of the hard decisions after the complete iteration, as lay_fused_body: leaves at the first task
+        // with an unsatisfied check
+        bool bad = false;
+        for (int t = 0; t < a.n_tasks && !bad; ++t) {
+          const int first = sload(a.task, 4 * t), cnt = sload(a.task, 4 * t + 1), d = sload(a.task, 4 * t + 2);
+          uint32_t par = 0;
+          if (lane < cnt) {
+            const int32_t* ix = a.idx + first + lane;
+            for (int k = 0; k < d; ++k) par ^= (P[ix[64 * k]] < 0) ? 1u : 0u;
+          }
+          bad = __builtin_amdgcn_readfirstlane((int)(__ballot(par != 0) != 0ull)) != 0;
+        }
+        if (!bad) break;
+      }
+    }
+    for (int v = 4 * lane; v < a.ldn; v += 256)
+      *reinterpret_cast<uint32_t*>(row + v) = *reinterpret_cast<const uint32_t*>(P + v);
+    if (a.iters && lane == 0) a.iters[b] = it;
+    __builtin_amdgcn_wave_barrier();   // the next codeword's rows stay behind these reads
+  }
+}
+
+// tile geometry of the two staging kernels: block -> (first variable, first codeword) of its 64 x 64 tile
+__device__ __forceinline__ void layfix_fused_tile(int B, size_t* r0, size_t* c0) {
+  const unsigned tiles_x = (unsigned)((B + 63) / 64);
+  *r0 = (size_t)(blockIdx.x / tiles_x) * 64;
+  *c0 = (size_t)(blockIdx.x % tiles_x) * 64;
+}
+
+}  // namespace
+
+__global__ __launch_bounds__(64 * kLayFixFusedBoundCw) void layfix_fused(const LayFixFusedArgs a) {
+  layfix_fused_body<false>(a);
+}
+__global__ __launch_bounds__(64 * kLayFixFusedBoundCw) void layfix_fused_wide(const LayFixFusedArgs a) {
+  layfix_fused_body<true>(a);
+}
+
+// buf[b][v] = quantised / copied llr[v][b] for v < n_v, b < B, 0 for n_v <= v < ldn: a 64 x 64 tile (variables x
+// codewords) through LDS, 256 threads. It is read a row of the caller's array per wave and written a dword of four
+// consecutive variables per thread, 16 threads a codeword's 64 bytes.
+__global__ __launch_bounds__(256) void layfix_fused_stage_in(const void* __restrict__ llr, int dtype,
+                                                             int8_t* __restrict__ buf, int n_v, int ldn, int B,
+                                                             float scale) {
+  __shared__ int8_t tile[64][68];   // [variable][codeword]
+  const int tx = (int)(threadIdx.x & 63u), ty = (int)(threadIdx.x >> 6);
+  size_t r0, c0;
+  layfix_fused_tile(B, &r0, &c0);
+  for (int j = ty; j < 64; j += 4) {
+    const size_t r = r0 + j, c = c0 + tx;
+    int x = 0;
+    if (r < (size_t)n_v && c < (size_t)B) {
+      const size_t src = r * (size_t)B + c;
+      if (dtype == kF32) {
+        // one rounded product, rint to even, clamped as a float, then converted (layfix_stage_in's statement)
+        const float f = __builtin_rintf(static_cast<const float*>(llr)[src] * scale);
+        x = (int)fminf(fmaxf(f, -(float)kLayFixApp), (float)kLayFixApp);
+      } else {
+        x = max((int)static_cast<const int8_t*>(llr)[src], -kLayFixApp);
+      }
+    }
+    tile[j][tx] = (int8_t)x;
+  }
+  __syncthreads();
+#pragma unroll
+  for (int pass = 0; pass < 4; ++pass) {
+    const int id = pass * 256 + (int)threadIdx.x, q = id & 15, j = id >> 4;
+    const size_t c = c0 + j, r = r0 + 4 * q;
+    if (c < (size_t)B && r < (size_t)ldn) {   // ldn is a multiple of 4: the dword lies inside the row
+      uint32_t w = 0;
+#pragma unroll
+      for (int i = 0; i < 4; ++i) w |= (uint32_t)(uint8_t)tile[4 * q + i][j] << (8 * i);
+      *reinterpret_cast<uint32_t*>(buf + c * (size_t)ldn + r) = w;
+    }
+  }
+}
+
+// out[v][b] = buf[b][v] (IBL_I8) or f32(buf[b][v]) / scale (IBL_F32): the same tiles, the other way
+__global__ __launch_bounds__(256) void layfix_fused_stage_out(const int8_t* __restrict__ buf, void* __restrict__ out,
+                                                              int dtype, int n_v, int ldn, int B, float scale) {
+  __shared__ int8_t tile[64][68];   // [variable][codeword]
+  const int tx = (int)(threadIdx.x & 63u), ty = (int)(threadIdx.x >> 6);
+  size_t r0, c0;
+  layfix_fused_tile(B, &r0, &c0);
+#pragma unroll
+  for (int pass = 0; pass < 4; ++pass) {
+    const int id = pass * 256 + (int)threadIdx.x, q = id & 15, j = id >> 4;
+    const size_t c = c0 + j, r = r0 + 4 * q;
+    uint32_t w = 0;
+    if (c < (size_t)B && r < (size_t)ldn) w = *reinterpret_cast<const uint32_t*>(buf + c * (size_t)ldn + r);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) tile[4 * q + i][j] = (int8_t)(w >> (8 * i));
+  }
+  __syncthreads();
+  for (int j = ty; j < 64; j += 4) {
+    const size_t r = r0 + j, c = c0 + tx;
+    if (r < (size_t)n_v && c < (size_t)B) {
+      const int x = (int)tile[j][tx];
+      const size_t dst = r * (size_t)B + c;
+      if (dtype == kF32) static_cast<float*>(out)[dst] = (float)x / scale;
+      else static_cast<int8_t*>(out)[dst] = (int8_t)x;
+    }
+  }
+}
+
+// blocks per CU of the fused kernel and the largest private segment over it and the two staging kernels
+hipError_t layfix_fused_occupancy(bool wide, int cw_per_group, size_t lds, int* blocks_per_cu, size_t* private_bytes) {
+  const void* f = wide ? (const void*)layfix_fused_wide : (const void*)layfix_fused;
+  hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
+  if (e != hipSuccess) return e;
+  if ((e = lay_private_bytes({f, (const void*)layfix_fused_stage_in, (const void*)layfix_fused_stage_out},
+                             private_bytes)) != hipSuccess)
+    return e;
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(blocks_per_cu, f, 64 * cw_per_group, lds);
+}
+
+hipError_t launch_layfix_fused(const LayFixFusedArgs& a, bool wide, int grid, size_t lds, hipStream_t s) {
+  if (!a.buf || !a.task || !a.idx || a.cw_per_group < 1 || a.cw_per_group > kLayFixFusedBoundCw || a.n_tasks < 1 ||
+      a.B < 1 || a.ngroups < 1 || grid < 1 || a.n_v < 1 || a.n_c < 1 || a.ldn != fixfused_ldn(a.n_v) ||
+      (size_t)a.cw_bytes != fixfused_cw_bytes(a.n_v, a.n_c, wide) ||
+      lds < (size_t)a.cw_per_group * (size_t)a.cw_bytes || lds > (size_t)kLdsBytes ||
+      (int64_t)a.ngroups * a.cw_per_group < a.B || !fix_params_ok(a.alpha16, a.beta_q, a.q_max))
+    return hipErrorInvalidValue;
+  LayFixFusedArgs args = a;
+  void* p[] = {&args};
+  const void* f = wide ? (const void*)layfix_fused_wide : (const void*)layfix_fused;
+  return hipLaunchKernel(f, dim3(grid), dim3(64 * a.cw_per_group), p, lds, s);
+}
+
+hipError_t launch_layfix_fused_stage_in(const void* llr, int32_t dtype, int8_t* buf, int n_v, int B, float scale,
+                                        hipStream_t s) {
+  if (!llr || !buf || n_v < 1 || B < 1 || !layfix_dtype_ok(dtype) || !(scale > 0.f)) return hipErrorInvalidValue;
+  const int64_t tiles = fixfused_stage_tiles(n_v, B);
+  if (tiles > 0x7fffffffll) return hipErrorInvalidValue;
+  int ldn = fixfused_ldn(n_v);
+  void* p[] = {(void*)&llr, (void*)&dtype, (void*)&buf, (void*)&n_v, (void*)&ldn, (void*)&B, (void*)&scale};
+  return hipLaunchKernel((const void*)layfix_fused_stage_in, dim3((unsigned)tiles), dim3(256), p, 0, s);
+}
+
+hipError_t launch_layfix_fused_stage_out(const int8_t* buf, void* out, int32_t dtype, int n_v, int B, float scale,
+                                         hipStream_t s) {
+  if (!buf || !out || n_v < 1 || B < 1 || !layfix_dtype_ok(dtype) || !(scale > 0.f)) return hipErrorInvalidValue;
+  const int64_t tiles = fixfused_stage_tiles(n_v, B);
+  if (tiles > 0x7fffffffll) return hipErrorInvalidValue;
+  int ldn = fixfused_ldn(n_v);
+  void* p[] = {(void*)&buf, (void*)&out, (void*)&dtype, (void*)&n_v, (void*)&ldn, (void*)&B, (void*)&scale};
+  return hipLaunchKernel((const void*)layfix_fused_stage_out, dim3((unsigned)tiles), dim3(256), p, 0, s);
+}
+
 #undef LAY_CASES_32
 #undef LAY_CASES_16
 

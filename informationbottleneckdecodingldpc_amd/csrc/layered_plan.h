@@ -4,8 +4,9 @@
 // UndefinedBehaviorSanitizer, into the CPU-only checkers tests/asan/layered_plan_check.cpp
 // (tests/test_cpu_layered.py), tests/asan/layered_pass_plan_check.cpp (tests/test_cpu_layered_passes.py),
 // tests/asan/layered_fixed_plan_check.cpp (tests/test_cpu_layered_fixed.py),
-// tests/asan/layered_compact_plan_check.cpp (tests/test_cpu_layered_compact.py) and
-// tests/asan/layered_wide_plan_check.cpp (tests/test_cpu_layered_wide.py).
+// tests/asan/layered_compact_plan_check.cpp (tests/test_cpu_layered_compact.py),
+// tests/asan/layered_wide_plan_check.cpp (tests/test_cpu_layered_wide.py) and
+// tests/asan/layered_fixed_fused_plan_check.cpp (tests/test_cpu_layered_fixed_fused.py).
 //
 // A layer is a set of checks no two of which share a variable; the layers are disjoint, cover every check and
 // are decoded in order (include/ibldpc.h "Layered min-sum"). The device plan cuts every layer into tasks of up
@@ -329,5 +330,36 @@ constexpr uint32_t fix_wide_m2(uint32_t w0) { return (w0 >> 11) & 63u; }
 constexpr uint32_t fix_wide_pos(uint32_t w0) { return w0 & 31u; }
 // the low D bits set, D in [1, 32] (1u << 32 is undefined)
 constexpr uint32_t fix_wide_mask(int D) { return 0xFFFFFFFFu >> (32 - D); }
+
+// ---- fixed point, fused on chip (include/ibldpc.h "Layered min-sum, fixed point", the fused kernel; checked by
+// tests/asan/layered_fixed_fused_plan_check.cpp) -----------------------------------------------------------------
+// One wave owns one codeword, as in the fp32 fused kernel, and the device plan is that kernel's (plan_layered:
+// task, idx). The wave's slice of LDS is P[ldn] int8, ldn = N rounded up to 4 so that the state words behind it are
+// aligned, then S[n_c] (fix_state_word) or, wide, S[n_c] and S1[n_c] (fix_state_words_wide). Codewords travel
+// through a [max_batch][ldn] int8 scratch buffer, rows of whole dwords; the staging kernels move 64 x 64 tiles
+// (64 variables x 64 codewords) between it and the caller's [N][B] arrays.
+// Codewords (= waves) of a workgroup: the cap a handle is created with, and the most the kernels are built for
+// (their launch bounds: 1,024 threads, which caps the registers at 128 a lane). Small workgroups measured fastest
+// (DESIGN.md "Layered min-sum: fixed point, fused"): 8, 4, 2 and 1 tie on a large batch, all ahead of 16, and 4 or
+// fewer spread a small batch over more CUs.
+constexpr int kLayFixFusedMaxCw = 4;
+constexpr int kLayFixFusedBoundCw = 16;
+
+inline int32_t fixfused_ldn(int32_t n_v) { return (int32_t)(((int64_t)n_v + 3) / 4 * 4); }
+inline size_t fixfused_cw_bytes(int32_t n_v, int32_t n_c, bool wide = false) {
+  return (size_t)fixfused_ldn(n_v) + (size_t)(wide ? 8 : 4) * (size_t)n_c;
+}
+// Codewords a workgroup keeps on chip: 0 = the code does not fit. cap: in [1, kLayFixFusedBoundCw]
+inline int32_t fixfused_cw_per_group(int32_t n_v, int32_t n_c, bool wide = false, int32_t cap = kLayFixFusedMaxCw) {
+  return (int32_t)std::min<size_t>((size_t)cap, (size_t)kLayLds / fixfused_cw_bytes(n_v, n_c, wide));
+}
+// bytes of the scratch buffer of a handle of max_batch
+inline size_t fixfused_buf_bytes(int32_t n_v, int32_t max_batch) {
+  return (size_t)max_batch * (size_t)fixfused_ldn(n_v);
+}
+// workgroups of a staging launch for a batch of B: tiles over the ldn scratch columns (variables) x the codewords
+inline int64_t fixfused_stage_tiles(int32_t n_v, int32_t B) {
+  return (((int64_t)fixfused_ldn(n_v) + 63) / 64) * (((int64_t)B + 63) / 64);
+}
 
 }  // namespace ibl

@@ -454,16 +454,21 @@ class LayeredFixedDecoder:
     per-layer kernels over HBM (``path`` ``"auto"`` or ``"passes"``; ``"fused"`` raises :class:`_lib.IBLError`,
     ``IBL_EUNSUPPORTED``: that kernel is not built) and owns about N + 4 n_c + N / 8 bytes per codeword of
     ``max_batch``. ``decode`` takes and gives float32 or int8 tensors in any combination.
+    ``path="onchip"`` runs the fused on-chip kernel of the same arithmetic instead
+    (``ibl_layered_create_fixed_fused``): one wave per codeword in LDS, three launches per decode, the same values
+    and iteration counts. A codeword needs N (rounded up to 4) + 4 n_c bytes of LDS, a workgroup holds up to 4;
+    a code that does not fit (DVB-S2 N = 64800) raises ``IBL_EUNSUPPORTED``. :attr:`path_in_use` is then
+    ``"fused"`` and :meth:`geometry` the real one. ``"auto"`` never chooses it.
     Check degrees 2..32: a code with a check of degree above 16 makes a *wide* decoder (:attr:`wide`) with two state
-    words per check and codeword, N + 8 n_c + N / 8 bytes per codeword."""
+    words per check and codeword, N + 8 n_c + N / 8 bytes per codeword (on chip: N + 8 n_c of LDS)."""
 
-    _PATHS = LayeredDecoder._PATHS
+    _PATHS = {**LayeredDecoder._PATHS, "onchip": None}   # "onchip" is an entry point of its own, not a path value
     _DT = {torch.float32: _lib.IBL_F32, torch.int8: _lib.IBL_I8}
 
     def __init__(self, graph: Graph, layers, imax: int, max_batch: int, alpha16: int = 16, beta_q: int = 0,
                  q_max: int = 31, scale: float = 2.0, path: str = "auto"):
         if path not in self._PATHS:
-            raise ValueError('path must be "fused", "passes" or "auto"')
+            raise ValueError('path must be "fused", "passes", "auto" or "onchip"')
         self.path = path
         self.graph = graph
         self.imax = int(imax)
@@ -475,10 +480,16 @@ class LayeredFixedDecoder:
             chk = np.zeros(1, np.int32)
         self.n_layers = nl
         h = ctypes.c_void_p()
-        _lib.check(_lib.load().ibl_layered_create_fixed(graph.handle, nl, ptr, chk, self.imax, self.alpha16,
-                                                        self.beta_q, self.q_max, self.scale, self.max_batch,
-                                                        self._PATHS[path], ctypes.byref(h)),
-                   "ibl_layered_create_fixed")
+        if path == "onchip":
+            _lib.check(_lib.load().ibl_layered_create_fixed_fused(graph.handle, nl, ptr, chk, self.imax, self.alpha16,
+                                                                  self.beta_q, self.q_max, self.scale, self.max_batch,
+                                                                  ctypes.byref(h)),
+                       "ibl_layered_create_fixed_fused")
+        else:
+            _lib.check(_lib.load().ibl_layered_create_fixed(graph.handle, nl, ptr, chk, self.imax, self.alpha16,
+                                                            self.beta_q, self.q_max, self.scale, self.max_batch,
+                                                            self._PATHS[path], ctypes.byref(h)),
+                       "ibl_layered_create_fixed")
         self._h = h
 
     path_in_use = LayeredDecoder.path_in_use

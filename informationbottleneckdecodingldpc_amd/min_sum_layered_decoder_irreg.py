@@ -12,7 +12,9 @@ and method names so the same drivers (``ber.run_ber``) take it. Keyword-only ext
 * ``fixed`` — ``True`` decodes in fixed point (:class:`.engine.LayeredFixedDecoder`, include/ibldpc.h "Layered
   min-sum, fixed point") with ``scale`` integer units per LLR unit and messages saturated at ``q_max``: ``alpha``
   must be a multiple of 1/16 in [0, 1] and ``beta * scale`` an integer in [0, 63]; ``llr_max`` is not used (the
-  APP values saturate at 127 units); ``path`` ``"passes"`` or ``"auto"`` (``"fused"`` raises ``ValueError``).
+  APP values saturate at 127 units); ``path`` ``"passes"`` or ``"auto"`` (``"fused"`` raises ``ValueError``), or
+  ``"onchip"``: the fused on-chip kernel of the fixed-point arithmetic, for codes whose codeword fits the LDS
+  (N + 4 n_c bytes; same results, ``ValueError`` without ``fixed=True`` or with ``compact``).
   Input and output stay float32;
 * ``compact`` — ``True`` or ``(every, min_free_pct)``: the per-layer kernels move the running codewords together
   between iterations (:class:`.engine.LayeredDecoder`); same results. ``ValueError`` with ``fixed=True`` or
@@ -39,10 +41,12 @@ class Min_Sum_Layered_Decoder_class_irregular(CodeMixin):
     def __init__(self, filename, imax_, cardinality_T_channel_, msg_at_time_, *, layers=None, Z=None,
                  alpha: float = 1.0, beta: float = 0.0, llr_max: float = 150.0, path: str = "fused",
                  fixed: bool = False, scale: float = 2.0, q_max: int = 31, compact=None):
-        if path not in LayeredDecoder._PATHS:
-            raise ValueError('path must be "fused", "passes" or "auto"')
+        if path not in LayeredFixedDecoder._PATHS:
+            raise ValueError('path must be "fused", "passes" or "auto" (fixed=True: or "onchip")')
         self.path = path
         self.fixed = bool(fixed)
+        if path == "onchip" and not self.fixed:
+            raise ValueError('path="onchip" is the fixed-point fused kernel: it needs fixed=True (fp32: path="fused")')
         self.compact = None if compact is False else compact
         if self.compact is not None and (self.fixed or path == "fused"):
             raise ValueError('compact runs on the fp32 per-layer kernels: not with fixed=True or path="fused"')
