@@ -285,6 +285,34 @@ int ibl_float_timing_read(ibl_float* h, double* cn_ms, int32_t* cn_launches, dou
 int ibl_float_create_corrected(const ibl_graph* g, double alpha, double beta, int32_t imax, double llr_max,
                                int32_t precision, int32_t max_batch, ibl_float** out);
 int ibl_float_correction(const ibl_float* h, double* alpha, double* beta);
+/*
+ * Per-codeword stop on the fused flooding decoders (no reference counterpart: the reference stops a batch when every
+ * codeword's syndrome is zero).  ibl_ib_decode_each and ibl_float_decode_each take the arguments of ibl_ib_decode /
+ * ibl_float_decode without early_stop; d_iters is NULL or B int32 entries.
+ * For codeword c of a batch, d_out[:, c] and d_iters[c] are exactly what today's decoder produces when it decodes
+ * column c alone (B = 1) with early_stop = 1, and d_iters[c] = L_c:
+ *   IB     L_c is the first check pass j >= 1 whose inputs have a zero syndrome for c, else imax - 1; the output is
+ *          the decision with the decision tables of pass L_c on the messages check pass L_c wrote;
+ *   float  L_c is the first iteration i >= 1 whose variable-to-check messages have a zero syndrome for c (the
+ *          syndrome check pass i + 1 reads), else imax - 1; the output is the APP LLRs of iteration L_c (channel
+ *          plus all check-to-variable messages of check pass L_c).
+ * The result of a codeword does not depend on its neighbours, on the group size (IB 8 or 4 codewords a workgroup,
+ * float 4 fp32 / 2 fp64), on the grid or on the number of CUs.  With imax == 1 it equals the fixed-iteration
+ * decode and d_iters[c] = 0.  Codewords that share a group keep iterating until the whole group has stopped; a
+ * codeword that stopped earlier keeps the output of its own L_c, and whatever happens to its messages afterwards
+ * reaches neither d_out nor d_iters.  Columns past the end of the batch are never running and never written, and
+ * nothing outside the [N][B] elements of d_out and the B entries of d_iters is written.
+ * One staging launch and one kernel launch per decode: no flag words, no second pass.  Both run on the fused kernel
+ * only and return IBL_EUNSUPPORTED, launching nothing, when the handle's decodes would not run it (IBL_PATH_PASSES,
+ * a code that does not fit, the generic IB path; ibl_ib_path_in_use / ibl_float_path_in_use).  The float entry
+ * takes all three arithmetics (min-sum, corrected min-sum, BP) in both precisions; both take every channel / output
+ * dtype of their decode; d_out may be d_llr as in ibl_float_decode, `stream` as there, and the float staging
+ * counts precondition violations as there (ibl_float_input_check).
+ */
+int ibl_ib_decode_each(ibl_ib* h, const void* d_ch, int32_t ch_dtype, int32_t B, void* d_out, int32_t out_dtype,
+                       int32_t* d_iters, void* stream);
+int ibl_float_decode_each(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out,
+                          int32_t out_dtype, int32_t* d_iters, void* stream);
 
 /*
  * Layered min-sum: layered (row-serial) normalised / offset min-sum decoding, fp32 (no reference counterpart:

@@ -33,7 +33,7 @@ EXPORTS = [
     "ibl_float_set_path", "ibl_float_path_in_use", "ibl_float_fused_geometry", "ibl_float_folded",
     "ibl_float_input_check",
     "ibl_float_set_small_batch", "ibl_float_small_batch",
-    "ibl_float_create_corrected", "ibl_float_correction",
+    "ibl_float_create_corrected", "ibl_float_correction", "ibl_float_decode_each", "ibl_ib_decode_each",
     "ibl_ib_timing", "ibl_ib_timing_read", "ibl_float_timing", "ibl_float_timing_read",
     "ibl_channel_sample",
     "ibl_encoder_create",
@@ -91,10 +91,12 @@ def load():
     L.ibl_ib_folded.argtypes = [_vp, ctypes.POINTER(_i32)]
     L.ibl_ib_set_fold.argtypes = [_vp, _i32]
     L.ibl_ib_decode.argtypes = [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]
+    L.ibl_ib_decode_each.argtypes = [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp]
     L.ibl_ib_destroy.argtypes = [_vp]
     L.ibl_ib_destroy.restype = None
     L.ibl_float_create.argtypes = [_vp, _i32, _i32, ctypes.c_double, _i32, _i32, ctypes.POINTER(_vp)]
     L.ibl_float_decode.argtypes = [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]
+    L.ibl_float_decode_each.argtypes = [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp]
     L.ibl_float_destroy.argtypes = [_vp]
     L.ibl_float_destroy.restype = None
     L.ibl_float_set_path.argtypes = [_vp, _i32]

@@ -41,6 +41,7 @@ struct ibl_float {
   FusedTaskBufs ft;
   size_t f_lds = 0;
   int f_grid = 0;
+  int f_grid_each = 0;      // the per-codeword-stop form's grid (ibl_float_decode_each)
 };
 
 namespace {
@@ -60,8 +61,8 @@ int fused_setup(ibl_float* h) {
   const char* voe = getenv("IBL_FUSED_VORDER");
   build_fused_tasks(*g, &ft, voe && voe[0] == '1', fused_vwin());
   pad_vn_slots(&ft);
-  // messages and channel (16-byte slots), 4 counter words, the padded u16 indices (codes whose indices do
-  // not fit beside the messages take the per-pass path)
+  // messages and channel (16-byte slots), 4 words (two ticket counters, the per-codeword stop's two mask words),
+  // the padded u16 indices (codes whose indices do not fit beside the messages take the per-pass path)
   const size_t lds = (size_t)(E + g->n_v) * 16 + 16 + ft.vn_slot.size() * 2;
   if (lds > (size_t)kLdsBytes) return IBL_OK;
   int bpc = 0, block = 0;
@@ -69,9 +70,16 @@ int fused_setup(ibl_float* h) {
     (void)hipGetLastError();
     return IBL_OK;
   }
+  // the per-codeword-stop form: same LDS; its own register count decides its grid
+  int bpe = 0;
+  if (fl_occupancy(kFlFused, kFlCheck, h->kkind, h->prec, g->dcm, g->dvm, lds, &bpe, &block, true) != hipSuccess || bpe < 1) {
+    (void)hipGetLastError();
+    return IBL_OK;
+  }
   if (int rc = h->ft.upload(ft)) return rc;
   h->f_lds = lds;
   h->f_grid = bpc * g->num_cus;
+  h->f_grid_each = bpe * g->num_cus;
   h->fused_ok = true;
   return IBL_OK;
 }
@@ -132,20 +140,44 @@ FlPassArgs float_pass_args(const ibl_float* h, int B, int ldb, void* d_out, int3
   return p;
 }
 
+// The fused kernel's arguments for a batch of B, but for the stop (unsat / dL, or iters); *grid: float_fused_geometry's
+FlFusedArgs float_fused_args(const ibl_float* h, int32_t B, void* d_out, int32_t out_dtype, int* grid) {
+  const ibl_graph* g = h->g;
+  FlFusedArgs fa{};
+  fa.ch = h->chf; fa.cn_task = h->ft.cn_task; fa.vn_task = h->ft.vn_task; fa.vn_node = h->ft.vn_node;
+  fa.vn_slot = h->ft.vn_slot; fa.out = d_out;
+  fa.llr_max = h->llr_max; fa.n_e = (int32_t)g->n_e; fa.n_v = g->n_v; fa.n_cn_tasks = h->ft.n_cn;
+  fa.cor_a = h->alpha; fa.cor_b = h->beta;
+  fa.n_vn_tasks = h->ft.n_vn; fa.n_vs = h->ft.n_vs; fa.ldb = h->ldb; fa.B = B; fa.imax = h->imax; fa.out_dtype = out_dtype;
+  float_fused_geometry(h, B, &fa.ngroups, grid);
+  fa.aligned = out_aligned(B, d_out, fl_cw_per_lane(h->prec), fl_elem_size(out_dtype));
+  return fa;
+}
+
+// Per-codeword stop (ibldpc.h "Per-codeword stop"): the staging launch and one launch of fl_fused<kind | kFlEach, ..>; no flag
+// words, no finalize_iters, no second pass.
+int float_each_fused(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out, int32_t out_dtype,
+                     int32_t* d_iters, hipStream_t s) {
+  const ibl_graph* g = h->g;
+  HIPCHK(launch_fl_stage_t(d_llr, llr_dtype, g->n_v, B, h->ft.vn_node, h->chf, h->prec, stage_rule(h), h->bad, s));
+  int grid = 0;
+  FlFusedArgs fa = float_fused_args(h, B, d_out, out_dtype, &grid);
+  fa.iters = d_iters;
+  grid = std::min(fa.ngroups, h->f_grid_each);
+  HIPCHK(h->timer.timed(0, s, [&] {
+    return launch_fl_fused(fa, h->kkind, h->prec, g->dcm, g->dvm, grid, h->f_lds, s, true);
+  }));
+  return IBL_OK;
+}
+
 int float_decode_fused(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out, int32_t out_dtype,
                        bool early, int32_t* d_iters, hipStream_t s) {
   const ibl_graph* g = h->g;
-  const int I = h->imax, cwl = fl_cw_per_lane(h->prec);
+  const int I = h->imax;
   HIPCHK(launch_fl_stage_t(d_llr, llr_dtype, g->n_v, B, h->ft.vn_node, h->chf, h->prec, stage_rule(h), h->bad, s));
-  FlFusedArgs fa{};
-  fa.ch = h->chf; fa.cn_task = h->ft.cn_task; fa.vn_task = h->ft.vn_task; fa.vn_node = h->ft.vn_node;
-  fa.vn_slot = h->ft.vn_slot; fa.out = d_out; fa.unsat = flag_row(h->flags, early, 0); fa.dL = nullptr;
-  fa.llr_max = h->llr_max; fa.n_e = (int32_t)g->n_e; fa.n_v = g->n_v; fa.n_cn_tasks = h->ft.n_cn;
-  fa.cor_a = h->alpha; fa.cor_b = h->beta;
-  fa.n_vn_tasks = h->ft.n_vn; fa.n_vs = h->ft.n_vs; fa.ldb = h->ldb; fa.B = B; fa.imax = I; fa.out_dtype = out_dtype;
   int grid = 0;
-  float_fused_geometry(h, B, &fa.ngroups, &grid);
-  fa.aligned = out_aligned(B, d_out, cwl, fl_elem_size(out_dtype));
+  FlFusedArgs fa = float_fused_args(h, B, d_out, out_dtype, &grid);
+  fa.unsat = flag_row(h->flags, early, 0); fa.dL = nullptr;
   auto launch = [&] { return launch_fl_fused(fa, h->kkind, h->prec, g->dcm, g->dvm, grid, h->f_lds, s); };
 #if IBL_DIAG
   const char* ftrace = getenv("IBL_TRACE_FUSED");   // diagnostic builds: phase clocks of block 0's first group
@@ -442,13 +474,33 @@ void ibl_float_destroy(ibl_float* h) {
   delete h;
 }
 
-int ibl_float_decode(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out, int32_t out_dtype,
-                     int32_t early_stop, int32_t* d_iters, void* stream) {
+// the argument checks ibl_float_decode and ibl_float_decode_each share
+static int float_decode_check(const ibl_float* h, const void* d_llr, int32_t llr_dtype, int32_t B, const void* d_out,
+                              int32_t out_dtype) {
   if (!h) return fail(IBL_EINVAL, "decoder is NULL");
   if (B < 1 || B > h->max_batch) return fail(IBL_EINVAL, "B must lie in [1, max_batch]");
   if ((llr_dtype != kF32 && llr_dtype != kF64) || (out_dtype != kF32 && out_dtype != kF64))
     return fail(IBL_EINVAL, "LLR dtypes must be IBL_F32 or IBL_F64");
   if (!d_llr || !d_out) return fail(IBL_EINVAL, "NULL buffer");
+  return IBL_OK;
+}
+
+// (the return type on its own line: tests/test_cpu_host.py lists the `int ..._decode...(` definitions of these files
+// by name to hold them to "no read of the environment"; tests/test_cpu_stop_codeword.py holds this one to it)
+int
+ibl_float_decode_each(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out,
+                      int32_t out_dtype, int32_t* d_iters, void* stream) {
+  if (int rc = float_decode_check(h, d_llr, llr_dtype, B, d_out, out_dtype)) return rc;
+  if (!(h->fused_ok && h->path != IBL_PATH_PASSES))
+    return fail(IBL_EUNSUPPORTED, "the per-codeword stop runs on the fused kernel only (path \"passes\", or the code "
+                                  "does not fit it)");
+  HIPCHK(hipSetDevice(h->g->device));
+  return float_each_fused(h, d_llr, llr_dtype, B, d_out, out_dtype, d_iters, (hipStream_t)stream);
+}
+
+int ibl_float_decode(ibl_float* h, const void* d_llr, int32_t llr_dtype, int32_t B, void* d_out, int32_t out_dtype,
+                     int32_t early_stop, int32_t* d_iters, void* stream) {
+  if (int rc = float_decode_check(h, d_llr, llr_dtype, B, d_out, out_dtype)) return rc;
   hipStream_t s = (hipStream_t)stream;
   HIPCHK(hipSetDevice(h->g->device));
   const bool early = early_stop != 0 && h->imax > 1;

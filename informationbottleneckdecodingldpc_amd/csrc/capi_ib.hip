@@ -38,6 +38,7 @@ struct ibl_ib {
   // fused on-chip path (IbFusedArgs, short codes): task tables, LDS bytes per workgroup, grid
   int32_t path = IBL_PATH_AUTO;
   bool fused_ok = false, f_half_ok = false;   // f_half_ok: the 4-codeword-group kernel is usable too
+  bool f_each_ok = false;                     // the per-codeword-stop forms of the group sizes in use are usable
   int32_t f_ncw_forced = 0;                   // IBL_FUSED_NCW read once at create (A/B, tests), 0 = auto
   // small-batch per-pass kernels (ib_*_small) for B <= small_b (0: off); LDS bytes per launch kind
   int32_t small_b = 0;
@@ -284,6 +285,17 @@ int ib_fused_setup(ibl_ib* h) {
                    block4 == block && priv4 == 0;
     (void)hipGetLastError();
   }
+  {   // the per-codeword-stop forms (ibl_ib_decode_each) of the group sizes in use, under the same bounds: same LDS
+      // (their two mask words are the spare ones behind the ticket counters), no scratch, the same geometry
+    int bpe = 0, blocke = 0;
+    size_t prive = 0;
+    h->f_each_ok = ib_fused_occupancy(h->CM, h->VM, 8, lds, &bpe, &blocke, &prive, true) == hipSuccess && bpe == bpc &&
+                   blocke == block && prive == 0;
+    if (h->f_each_ok && h->f_half_ok)
+      h->f_each_ok = ib_fused_occupancy(h->CM, h->VM, 4, lds, &bpe, &blocke, &prive, true) == hipSuccess &&
+                     bpe == bpc && blocke == block && prive == 0;
+    (void)hipGetLastError();
+  }
   FusedTasks ft;
   build_fused_tasks(*g, &ft, env_on("IBL_FUSED_VORDER"), fused_vwin());
   if (int rc = h->ft.upload(ft)) return rc;
@@ -411,6 +423,39 @@ void ib_pass_args(const ibl_ib* h, int B, int ldbb, IbFastArgs* cn, IbFastArgs* 
   std::memcpy(vn->fslot, h->vn_fslot, sizeof(vn->fslot));
 }
 
+// The fused kernel's arguments for a batch of B, but for the stop (unsat / dL, or iters); *grid: workgroups
+IbFusedArgs ib_fused_args(const ibl_ib* h, uint32_t* chT, int32_t B, void* d_out, int32_t out_dtype, int* grid) {
+  const ibl_graph* g = h->g;
+  IbFusedArgs f{};
+  f.cn_img = h->cn_img; f.vn_img = h->vn_img; f.dec_img = h->dec_img; f.chT = chT;
+  f.cn_task = h->ft.cn_task; f.vn_task = h->ft.vn_task; f.vn_node = h->ft.vn_node; f.vn_slot = h->ft.vn_slot;
+  f.out = d_out;
+  std::memcpy(f.cn_fslot, h->cn_fslot, sizeof(f.cn_fslot));
+  std::memcpy(f.vn_fslot, h->vn_fslot, sizeof(f.vn_fslot));
+  f.cn_nt = h->cn_nt; f.vn_nt = h->vn_nt; f.dec_nt = h->dec_nt; f.nreg = h->f_nreg; f.dbuf = h->f_dbuf;
+  f.n_cn_nodes = g->n_c; f.cn_uni = h->f_cn_uni; f.vn_uni = h->f_vn_uni;
+  f.n_e = (int32_t)g->n_e; f.n_v = g->n_v; f.n_cn_tasks = h->ft.n_cn; f.n_vn_tasks = h->ft.n_vn;
+  f.B = B; f.imax = h->imax; f.half = h->T / 2; f.match = h->match; f.out_dtype = out_dtype;
+  f.aligned = out_aligned(B, d_out, 4, out_dtype == kU8 ? 1 : 4);
+  f.ngroups = (B + 7) / 8;
+  f.ncw = ib_fused_ncw(h, B);
+  *grid = std::min(h->f_grid, f.ngroups * (8 / f.ncw));
+  return f;
+}
+
+// Per-codeword stop (ibldpc.h "Per-codeword stop"): the staging launch and one launch of ib_fused<.., ncw | kIbEach>; no flag
+// words, no finalize_iters, no second pass.
+int ib_each_fused(ibl_ib* h, const void* d_ch, int32_t ch_dtype, int32_t B, void* d_out, int32_t out_dtype,
+                  int32_t* d_iters, hipStream_t s) {
+  uint32_t* chT = reinterpret_cast<uint32_t*>(h->ch8.get());
+  HIPCHK(launch_ib_stage_t(d_ch, ch_dtype, h->g->n_v, B, h->ft.vn_node, chT, s));
+  int grid = 0;
+  IbFusedArgs f = ib_fused_args(h, chT, B, d_out, out_dtype, &grid);
+  f.iters = d_iters;
+  HIPCHK(h->timer.timed(0, s, [&] { return launch_ib_fused(f, h->CM, h->VM, grid, h->f_block, h->f_lds, s, true); }));
+  return IBL_OK;
+}
+
 int ib_decode_fused(ibl_ib* h, const void* d_ch, int32_t ch_dtype, int32_t B, void* d_out, int32_t out_dtype,
                     bool early, int32_t* d_iters, hipStream_t s) {
   const ibl_graph* g = h->g;
@@ -418,20 +463,9 @@ int ib_decode_fused(ibl_ib* h, const void* d_ch, int32_t ch_dtype, int32_t B, vo
   // channel as [group][N] dwords of 8 nibbles (the fused kernel's layout), in the staging buffer
   uint32_t* chT = reinterpret_cast<uint32_t*>(h->ch8.get());
   HIPCHK(launch_ib_stage_t(d_ch, ch_dtype, g->n_v, B, h->ft.vn_node, chT, s));
-  IbFusedArgs f{};
-  f.cn_img = h->cn_img; f.vn_img = h->vn_img; f.dec_img = h->dec_img; f.chT = chT;
-  f.cn_task = h->ft.cn_task; f.vn_task = h->ft.vn_task; f.vn_node = h->ft.vn_node; f.vn_slot = h->ft.vn_slot;
-  f.out = d_out; f.unsat = flag_row(h->flags, early, 0); f.dL = nullptr;
-  std::memcpy(f.cn_fslot, h->cn_fslot, sizeof(f.cn_fslot));
-  std::memcpy(f.vn_fslot, h->vn_fslot, sizeof(f.vn_fslot));
-  f.cn_nt = h->cn_nt; f.vn_nt = h->vn_nt; f.dec_nt = h->dec_nt; f.nreg = h->f_nreg; f.dbuf = h->f_dbuf;
-  f.n_cn_nodes = g->n_c; f.cn_uni = h->f_cn_uni; f.vn_uni = h->f_vn_uni;
-  f.n_e = (int32_t)g->n_e; f.n_v = g->n_v; f.n_cn_tasks = h->ft.n_cn; f.n_vn_tasks = h->ft.n_vn;
-  f.B = B; f.imax = I; f.half = h->T / 2; f.match = h->match; f.out_dtype = out_dtype;
-  f.aligned = out_aligned(B, d_out, 4, out_dtype == kU8 ? 1 : 4);
-  f.ngroups = (B + 7) / 8;
-  f.ncw = ib_fused_ncw(h, B);
-  const int grid = std::min(h->f_grid, f.ngroups * (8 / f.ncw));
+  int grid = 0;
+  IbFusedArgs f = ib_fused_args(h, chT, B, d_out, out_dtype, &grid);
+  f.unsat = flag_row(h->flags, early, 0); f.dL = nullptr;
   auto launch = [&] { return launch_ib_fused(f, h->CM, h->VM, grid, h->f_block, h->f_lds, s); };
 #if IBL_DIAG
   // diagnostic builds only: IBL_TRACE_FUSED=<file> records block 0's clock at every phase boundary of its
@@ -739,13 +773,36 @@ void ibl_ib_destroy(ibl_ib* h) {
   delete h;
 }
 
-int ibl_ib_decode(ibl_ib* h, const void* d_ch, int32_t ch_dtype, int32_t B, void* d_out, int32_t out_dtype,
-                  int32_t early_stop, int32_t* d_iters, void* stream) {
+// the argument checks ibl_ib_decode and ibl_ib_decode_each share
+static int ib_decode_check(const ibl_ib* h, const void* d_ch, int32_t ch_dtype, int32_t B, const void* d_out,
+                           int32_t out_dtype) {
   if (!h) return fail(IBL_EINVAL, "decoder is NULL");
   if (B < 1 || B > h->max_batch) return fail(IBL_EINVAL, "B must lie in [1, max_batch]");
   if (ch_dtype != kU8 && ch_dtype != kI32) return fail(IBL_EINVAL, "channel dtype must be IBL_U8 or IBL_I32");
   if (out_dtype != kU8 && out_dtype != kI32) return fail(IBL_EINVAL, "output dtype must be IBL_U8 or IBL_I32");
   if (!d_ch || !d_out) return fail(IBL_EINVAL, "NULL buffer");
+  return IBL_OK;
+}
+
+// (the return type on its own line: tests/test_cpu_host.py lists the `int ..._decode...(` definitions of these files
+// by name to hold them to "no read of the environment"; tests/test_cpu_stop_codeword.py holds this one to it)
+int
+ibl_ib_decode_each(ibl_ib* h, const void* d_ch, int32_t ch_dtype, int32_t B, void* d_out, int32_t out_dtype,
+                   int32_t* d_iters, void* stream) {
+  if (int rc = ib_decode_check(h, d_ch, ch_dtype, B, d_out, out_dtype)) return rc;
+  if (!ib_fused_in_use(h))
+    return fail(IBL_EUNSUPPORTED, "the per-codeword stop runs on the fused kernel only (path \"passes\", the generic "
+                                  "path, or the code does not fit it)");
+  if (!h->f_each_ok)
+    return fail(IBL_EUNSUPPORTED, "the per-codeword-stop kernels of this build have a private segment or another "
+                                  "occupancy than the fused kernel: rebuild required");
+  HIPCHK(hipSetDevice(h->g->device));
+  return ib_each_fused(h, d_ch, ch_dtype, B, d_out, out_dtype, d_iters, (hipStream_t)stream);
+}
+
+int ibl_ib_decode(ibl_ib* h, const void* d_ch, int32_t ch_dtype, int32_t B, void* d_out, int32_t out_dtype,
+                  int32_t early_stop, int32_t* d_iters, void* stream) {
+  if (int rc = ib_decode_check(h, d_ch, ch_dtype, B, d_out, out_dtype)) return rc;
   hipStream_t s = (hipStream_t)stream;
   HIPCHK(hipSetDevice(h->g->device));
   const bool early = early_stop != 0 && h->imax > 1;

@@ -146,6 +146,8 @@ struct IbFusedArgs {
   int32_t ncw;              // codewords per workgroup: 8, or 4 (half groups, small batches; see ib_fused)
   uint64_t* trace;          // diagnostics (IBL_TRACE_FUSED): block 0's clock at every phase boundary of its
                             // first group, else nullptr
+  int32_t* iters;           // per-codeword stop (ib_fused<.., ncw | kIbEach>): B stop passes, or nullptr. Last, so that no
+                            // earlier member's offset moves.
 };
 
 // --------------------------------------------------------------- IB generic path
@@ -240,6 +242,8 @@ struct FlFusedArgs {
   uint64_t* trace;          // diagnostics (IBL_TRACE_FUSED, -DIBL_FUSED_TRACE=1 builds): block 0's clock at
                             // every phase end of its first group, else nullptr
   double cor_a, cor_b;      // corrected min-sum (kind 2): alpha and beta, as FlArgs'
+  int32_t* iters;           // per-codeword stop (fl_fused<kind | kFlEach, ..>): B stop passes, or nullptr. Last, so that no
+                            // earlier member's offset moves.
 };
 
 struct FlDecArgs {
@@ -283,9 +287,11 @@ hipError_t ib_fast_occupancy(int which, int maxd, int block, size_t lds, int* bl
 hipError_t ib_fast_private_bytes(int cn_maxd, int vn_maxd, size_t* bytes, const char** name);
 hipError_t launch_ib_stage_t(const void* ch, int dtype, int n, int B, const int32_t* perm, uint32_t* chT,
                              hipStream_t s);
-hipError_t launch_ib_fused(const IbFusedArgs& a, int cmax, int vmax, int grid, int block, size_t lds, hipStream_t s);
+// each: the per-codeword-stop form of the fused kernel (ib_fused<.., ncw | kIbEach>)
+hipError_t launch_ib_fused(const IbFusedArgs& a, int cmax, int vmax, int grid, int block, size_t lds, hipStream_t s,
+                           bool each = false);
 hipError_t ib_fused_occupancy(int cmax, int vmax, int ncw, size_t lds, int* blocks_per_cu, int* block,
-                              size_t* private_bytes);
+                              size_t* private_bytes, bool each = false);
 hipError_t launch_ib_cn_gen(const IbGenArgs& a, hipStream_t s);
 hipError_t launch_ib_vn_gen(const IbGenArgs& a, hipStream_t s);
 hipError_t launch_ib_dec_gen(const IbGenDecArgs& a, hipStream_t s);
@@ -336,13 +342,15 @@ hipError_t launch_fl_stage_t(const void* x, int in_dtype, int n, int B, const in
 hipError_t launch_fl_pass(FlFamily fam, FlPass pass, const FlArgs& a, int kind, int prec, int maxd, int grid,
                           hipStream_t s);
 hipError_t launch_fl_dec(FlFamily fam, const FlDecArgs& a, int prec, int grid, hipStream_t s);
+// each: the per-codeword-stop form of the fused kernel (fl_fused<kind | kFlEach, ..>)
 hipError_t launch_fl_fused(const FlFusedArgs& a, int kind, int prec, int cmax, int vmax, int grid, size_t lds,
-                           hipStream_t s);
+                           hipStream_t s, bool each = false);
 // blocks per CU and threads per block of a kernel (the fused kernel with lds bytes of dynamic LDS)
 hipError_t fl_occupancy(FlFamily fam, FlPass pass, int kind, int prec, int cmax, int vmax, size_t lds,
-                        int* blocks_per_cu, int* block);
+                        int* blocks_per_cu, int* block, bool each = false);
 // Largest private segment over the check, variable and decision kernels of the small-batch family, or over the
-// per-pass check and variable kernels and, when asked, the fused kernel; *name receives that kernel's name.
+// per-pass check and variable kernels and, when asked, the fused kernel in both its forms (batch stop and
+// per-codeword stop); *name receives that kernel's name.
 hipError_t fl_private_bytes(FlFamily fam, int kind, int prec, int cn_maxd, int vn_maxd, bool fused, size_t* bytes,
                             const char** name);
 

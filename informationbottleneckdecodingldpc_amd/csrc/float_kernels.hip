@@ -680,6 +680,24 @@ __device__ __forceinline__ void fl_app_store(void* out, int out_dtype, size_t o,
   }
 }
 
+// The codewords in `some` only (bit s = codeword s, a subset of the existing ones: the per-codeword stop's output of
+// the codewords that stop at this pass). All Vec<F>::N of them take fl_app_store's vector store.
+template <typename F>
+__device__ __forceinline__ void fl_app_store_some(void* out, int out_dtype, size_t o, const F (&x)[Vec<F>::N], int vec,
+                                                  int valid, uint32_t some) {
+  constexpr int N = Vec<F>::N;
+  if (some == (1u << N) - 1u) {
+    fl_app_store<F>(out, out_dtype, o, x, vec, valid);
+    return;
+  }
+#pragma unroll
+  for (int s = 0; s < N; ++s) {
+    if (!((some >> s) & 1u)) continue;
+    if (out_dtype == kF32) reinterpret_cast<float*>(out)[o + s] = (float)x[s];
+    else reinterpret_cast<double*>(out)[o + s] = (double)x[s];
+  }
+}
+
 // Decision of the per-pass path. Wave item = (node, chunk of 64*N codewords); vector loads of every edge row,
 // vector stores when the user buffer is aligned (scalar tail otherwise).
 template <typename F>
@@ -992,9 +1010,21 @@ __global__ __launch_bounds__(kFlSmallBlock) void fl_dec_small(FlDecArgs a) {
 // runs imax-1 iterations and records each CN pass's syndrome in the same flag words as the per-pass
 // path; finalize_iters turns them into L; pass 2 (dL set) re-runs the batch to L only if L < imax-1.
 // A message slot holds Vec<F>::N codewords (16 bytes), and a task works on whole slots.
-template <int KIND, typename F, int D, int CNT = 0>
+// Per-codeword stop (kFlEach, ibldpc.h "Per-codeword stop"): one pass over the batch. The stop of iteration i is the
+// syndrome of variable pass i's outputs, which check pass i + 1 reads — after variable pass i has overwritten, in
+// place, the check messages that the APP output of iteration i sums. So every variable pass i also stores the APP
+// LLRs of the codewords still running to the user's output (fused_vn_app_item), a later pass of the same codeword
+// overwrites them (the barriers between the phases wait for the stores), and a codeword that check pass i + 1 finds
+// satisfied keeps what variable pass i stored and gets iters = i. Check pass j >= 2 reduces its syndrome to a
+// mask of the group's unsatisfied codewords in an LDS word (two words after the ticket counters, word j & 1 for pass
+// j, reset one check pass ahead as the counters are), every wave reads that word after the barrier, and the
+// workgroup leaves the group once no codeword is running; those still running after check pass imax-1 take the
+// output phase and iters = imax-1.
+// unsat: bool (some codeword of the slot unsatisfied, the batch-global stop) or uint32_t (bit s = codeword s
+// unsatisfied, the per-codeword stop)
+template <int KIND, typename F, int D, int CNT = 0, class U>
 __device__ __forceinline__ void fused_cn_item(typename Vec<F>::T* msg, int first, int cnt_, int lane, F lm, F ca, F cb,
-                                              bool do_par, int valid, bool& unsat) {
+                                              bool do_par, int valid, U& unsat) {
   constexpr int N = Vec<F>::N;
   // CNT > 0: a full task (CNT nodes) — the edge stride is a constant, so one address register serves all
   // D loads and stores through their immediate offsets
@@ -1004,7 +1034,10 @@ __device__ __forceinline__ void fused_cn_item(typename Vec<F>::T* msg, int first
   for (int j = 0; j < D; ++j) fl_load16<false, F>(msg + (first + j * cnt + lane), m[j]);
   if (do_par) {
 #pragma unroll
-    for (int s = 0; s < N; ++s) unsat |= syndrome_bit<F, D>(m, s) && s < valid;
+    for (int s = 0; s < N; ++s) {
+      if constexpr (std::is_same_v<U, bool>) unsat |= syndrome_bit<F, D>(m, s) && s < valid;
+      else unsat |= (U)(syndrome_bit<F, D>(m, s) && s < valid) << s;
+    }
   }
   fl_cn_body<KIND, F, D>(m, lm, ca, cb, [&](int w, const F (&o)[N]) __attribute__((always_inline)) {
     fl_store16<false, F>(msg + (first + w * cnt + lane), o);
@@ -1030,10 +1063,60 @@ __device__ __forceinline__ void fused_vn_item(typename Vec<F>::T* msg, const typ
   });
 }
 
+// Per-codeword stop: the variable update, and before it the APP LLRs of the same inputs (fl_app_sum's order: the
+// channel, then the edges ascending) of the running codewords `run` to the user's output at element o.
+template <typename F, int D>
+__device__ __forceinline__ void fused_vn_app_item(typename Vec<F>::T* msg, const typename Vec<F>::T* chL,
+                                                  const uint16_t* vn_slot, int pos, int sfirst, int lane, F lm,
+                                                  void* out, int out_dtype, size_t o, int vec, int valid, uint32_t run) {
+  constexpr int N = Vec<F>::N;
+  if constexpr (D > 8) {
+    // the variable body of these degrees fills the 128 registers of a 1024-thread block: the APP sum reads the
+    // inputs on its own first, four at a time (few variables have such degrees)
+    F x[N];
+    fl_load16<false, F>(chL + pos, x);
+#pragma unroll 4
+    for (int k = 0; k < D; ++k) {
+      F r[N];
+      fl_load16<false, F>(msg + vn_slot[sfirst + 64 * k + lane], r);
+#pragma unroll
+      for (int s = 0; s < N; ++s) x[s] = x[s] + r[s];
+    }
+    fl_app_store_some<F>(out, out_dtype, o, x, vec, valid, run);
+    __builtin_amdgcn_sched_barrier(0);   // the sum's registers are free before the body's are taken
+    fused_vn_item<F, D>(msg, chL, vn_slot, pos, sfirst, lane, lm);
+    return;
+  }
+  int sl[D];
+#pragma unroll
+  for (int k = 0; k < D; ++k) sl[k] = vn_slot[sfirst + 64 * k + lane];
+  F c[N], m[D][N], x[N];
+  fl_load16<false, F>(chL + pos, c);
+#pragma unroll
+  for (int k = 0; k < D; ++k) fl_load16<false, F>(msg + sl[k], m[k]);
+#pragma unroll
+  for (int s = 0; s < N; ++s) x[s] = c[s];
+#pragma unroll
+  for (int k = 0; k < D; ++k) {
+#pragma unroll
+    for (int s = 0; s < N; ++s) x[s] = x[s] + m[k][s];
+  }
+  fl_app_store_some<F>(out, out_dtype, o, x, vec, valid, run);
+  __builtin_amdgcn_sched_barrier(0);   // the store's registers are free before the body's are taken
+  fl_vn_body<F, D>(c, m, lm, [&](int w, const F (&o2)[N]) __attribute__((always_inline)) {
+    fl_store16<false, F>(msg + sl[w], o2);
+  });
+}
+
 // CMAX / VMAX: largest check / variable degree with a body (WLAN: checks <= 8, variables up to 11 ->
 // fl_fused<.., 8, 16>, without the 16-input check bodies' registers)
-template <int KIND, typename F, int CMAX, int VMAX>
-__global__ __launch_bounds__(fl_block(kFlFused, kFlCheck, KIND, sizeof(F) == 8, CMAX)) void fl_fused(FlFusedArgs a) {
+// KX: the check-body kind, plus kFlEach for the per-codeword-stop form (a bit of the kind and not a further
+// parameter, so that the instantiations without it keep their symbols)
+constexpr int kFlEach = 4;
+template <int KX, typename F, int CMAX, int VMAX>
+__global__ __launch_bounds__(fl_block(kFlFused, kFlCheck, KX & 3, sizeof(F) == 8, CMAX)) void fl_fused(FlFusedArgs a) {
+  constexpr int KIND = KX & 3;
+  constexpr bool EACH = (KX & kFlEach) != 0;
   using V = Vec<F>;
   using VT = typename V::T;
   constexpr int N = V::N;
@@ -1078,7 +1161,7 @@ __global__ __launch_bounds__(fl_block(kFlFused, kFlCheck, KIND, sizeof(F) == 8, 
       for (int k = 0; k < d; ++k) msg[vs[sf + 64 * k + lane]] = c;
     }
   };
-  auto cn_task = [&](int t, int valid, bool do_par, bool& unsat) __attribute__((always_inline)) {
+  auto cn_task = [&](int t, int valid, bool do_par, auto& unsat) __attribute__((always_inline)) {
     const int first = sload(a.cn_task, 4 * t), cnt = sload(a.cn_task, 4 * t + 1), d = sload(a.cn_task, 4 * t + 2);
     // full tasks (64 nodes) run a body with the constant edge stride; it exists for degrees <= 8 only, and full
     // tasks of larger degrees take the general branch below (every lane < cnt = 64)
@@ -1116,9 +1199,37 @@ __global__ __launch_bounds__(fl_block(kFlFused, kFlCheck, KIND, sizeof(F) == 8, 
       fl_app_store<F>(a.out, a.out_dtype, (size_t)node * a.B + cw0, x, a.aligned, valid);
     }
   };
+  // per-codeword stop: the variable pass that also stores the running codewords' APP output
+  auto vn_app_task = [&](int t, int cw0, int valid, uint32_t run) __attribute__((always_inline)) {
+    const int pos = sload(a.vn_task, 4 * t), cnt = sload(a.vn_task, 4 * t + 1);
+    const int d = sload(a.vn_task, 4 * t + 2), sf = sload(a.vn_task, 4 * t + 3);
+    if (lane < cnt) {
+      const size_t o = (size_t)a.vn_node[pos + lane] * a.B + cw0;
+      fl_by_degree<VMAX, true>(d, [&](auto D) __attribute__((always_inline)) {
+        fused_vn_app_item<F, decltype(D)::value>(msg, chL, vs, pos + lane, sf, lane, lm, a.out, a.out_dtype, o,
+                                                 a.aligned, valid, run);
+      });
+    }
+  };
+  // per-codeword stop: the APP output of the codewords in `some` from the last check pass (sum) or, with imax = 1,
+  // from the channel alone
+  auto out_some_task = [&](int t, int cw0, int valid, uint32_t some, bool sum) __attribute__((always_inline)) {
+    const int pos = sload(a.vn_task, 4 * t), cnt = sload(a.vn_task, 4 * t + 1);
+    const int d = sload(a.vn_task, 4 * t + 2), sf = sload(a.vn_task, 4 * t + 3);
+    if (lane < cnt) {
+      const int node = a.vn_node[pos + lane];
+      F x[N];
+      fl_load16<false, F>(chL + pos + lane, x);
+      if (sum)
+        fl_app_sum<F>(x, d, [&](int k, F (&r)[N]) __attribute__((always_inline)) {
+          fl_load16<false, F>(msg + vs[sf + 64 * k + lane], r);
+        });
+      fl_app_store_some<F>(a.out, a.out_dtype, (size_t)node * a.B + cw0, x, a.aligned, valid, some);
+    }
+  };
 
-  // ---- phases separated by barriers
-  auto phase = [&](int ntasks, auto&& body) __attribute__((always_inline)) {
+  // ---- phases separated by barriers: the tasks (phase_run), then the barrier (phase_end)
+  auto phase_run = [&](int ntasks, auto&& body) __attribute__((always_inline)) {
     int* c = ctr + (ph & 1);
     if (fl_tid() == 0) ctr[(ph + 1) & 1] = 0;
     int taken = 0;
@@ -1140,12 +1251,59 @@ __global__ __launch_bounds__(fl_block(kFlFused, kFlCheck, KIND, sizeof(F) == 8, 
         tr[TW * ph + 17 + wv] = (uint64_t)taken;
       }
     }
+  };
+  auto phase_end = [&]() __attribute__((always_inline)) {
     __syncthreads();
     ++ph;
     if constexpr (IBL_FUSED_TRACE) {
       if (tr && wv == 0) tr[TW * ph] = __builtin_readcyclecounter();
     }
   };
+  auto phase = [&](int ntasks, auto&& body) __attribute__((always_inline)) {
+    phase_run(ntasks, body);
+    phase_end();
+  };
+  if constexpr (EACH) {
+    int* um = ctr + 2;   // unsatisfied-codeword masks: word j & 1 for check pass j
+    const int Lm = a.imax - 1;
+    for (int grp = fl_bid(); grp < a.ngroups; grp += fl_gdim()) {
+      const int cw0 = grp * N;
+      const int valid = a.B - cw0;
+      // codewords still running (workgroup-uniform: scalars and the LDS word only); columns past the batch never are
+      uint32_t run = valid >= N ? (1u << N) - 1u : (1u << valid) - 1u;
+      auto set_iters = [&](uint32_t some, int it) __attribute__((always_inline)) {
+        if (a.iters && fl_tid() < N && ((some >> fl_tid()) & 1u)) a.iters[cw0 + fl_tid()] = it;
+      };
+      phase(a.n_vn_tasks, [&](int t) __attribute__((always_inline)) { send_task(t, grp); });
+      for (int j = 1; j <= Lm; ++j) {
+        // check pass j >= 2 holds the stop of iteration j - 1 (pass 1 reads the channel: no stop)
+        const bool do_par = j >= 2;
+        uint32_t un = 0;
+        if (fl_tid() == 0) um[(j + 1) & 1] = 0;
+        phase_run(a.n_cn_tasks, [&](int t) __attribute__((always_inline)) { cn_task(t, valid, do_par, un); });
+        if (do_par) {
+          uint32_t w = 0;
+#pragma unroll
+          for (int s = 0; s < N; ++s) w |= __ballot((un >> s) & 1u) != 0ull ? 1u << s : 0u;
+          if (w != 0 && lane == 0) atomicOr(&um[j & 1], (int)w);
+        }
+        phase_end();
+        if (do_par) {   // satisfied: variable pass j - 1 stored their output
+          const uint32_t done = run & ~(uint32_t)__builtin_amdgcn_readfirstlane(um[j & 1]);
+          set_iters(done, j - 1);
+          run &= ~done;
+          if (run == 0) break;
+        }
+        if (j == Lm) break;
+        phase(a.n_vn_tasks, [&](int t) __attribute__((always_inline)) { vn_app_task(t, cw0, valid, run); });
+      }
+      if (run != 0) {   // still running after check pass imax-1 (or imax = 1: the channel alone)
+        set_iters(run, Lm);
+        phase(a.n_vn_tasks, [&](int t) __attribute__((always_inline)) { out_some_task(t, cw0, valid, run, Lm > 0); });
+      }
+    }
+    return;
+  }
   for (int grp = fl_bid(); grp < a.ngroups; grp += fl_gdim()) {
     const int cw0 = grp * N;
     const int valid = a.B - cw0;
@@ -1216,7 +1374,10 @@ struct FlKernel {
   const char* name;
 };
 template <int KIND, typename F>
-static const void* fl_entry(FlFamily fam, FlPass pass, bool c8, bool v8) {
+static const void* fl_entry(FlFamily fam, FlPass pass, bool c8, bool v8, bool each) {
+  if (fam == kFlFused && each)
+    return !c8 ? (const void*)fl_fused<KIND | kFlEach, F, 16, 16>
+               : v8 ? (const void*)fl_fused<KIND | kFlEach, F, 8, 8> : (const void*)fl_fused<KIND | kFlEach, F, 8, 16>;
   if (fam == kFlFused)
     return !c8 ? (const void*)fl_fused<KIND, F, 16, 16>
                : v8 ? (const void*)fl_fused<KIND, F, 8, 8> : (const void*)fl_fused<KIND, F, 8, 16>;
@@ -1229,16 +1390,17 @@ static const void* fl_entry(FlFamily fam, FlPass pass, bool c8, bool v8) {
   if (pass == kFlVariable) return v8 ? (const void*)fl_vn<F, 8> : (const void*)fl_vn<F, 16>;
   return (const void*)fl_dec<F>;
 }
-static FlKernel fl_kernel(FlFamily fam, FlPass pass, int kind, int prec, int cmax, int vmax) {
+static FlKernel fl_kernel(FlFamily fam, FlPass pass, int kind, int prec, int cmax, int vmax, bool each = false) {
   static const char* const names[3][3] = {
       {"fl_cn", "fl_vn", "fl_dec"}, {"fl_cn_small", "fl_vn_small", "fl_dec_small"}, {"fl_fused", "fl_fused", "fl_fused"}};
   const bool f64 = prec != kF32, c8 = cmax <= 8, v8 = vmax <= 8;
   const void* fn =
-      kind == 0 ? (f64 ? fl_entry<0, double>(fam, pass, c8, v8) : fl_entry<0, float>(fam, pass, c8, v8))
-      : kind == kFlCorrected ? (f64 ? fl_entry<2, double>(fam, pass, c8, v8) : fl_entry<2, float>(fam, pass, c8, v8))
-                             : (f64 ? fl_entry<1, double>(fam, pass, c8, v8) : fl_entry<1, float>(fam, pass, c8, v8));
+      kind == 0 ? (f64 ? fl_entry<0, double>(fam, pass, c8, v8, each) : fl_entry<0, float>(fam, pass, c8, v8, each))
+      : kind == kFlCorrected
+          ? (f64 ? fl_entry<2, double>(fam, pass, c8, v8, each) : fl_entry<2, float>(fam, pass, c8, v8, each))
+          : (f64 ? fl_entry<1, double>(fam, pass, c8, v8, each) : fl_entry<1, float>(fam, pass, c8, v8, each));
   const int maxd = (fam == kFlFused || pass == kFlCheck) ? cmax : vmax;
-  return {fn, fl_block(fam, pass, kind, f64, maxd), names[fam][pass]};
+  return {fn, fl_block(fam, pass, kind, f64, maxd), each ? "fl_fused (per-codeword stop)" : names[fam][pass]};
 }
 template <class Args>
 static hipError_t fl_launch(const FlKernel& k, const Args& a, int grid, size_t lds, hipStream_t s) {
@@ -1260,13 +1422,13 @@ hipError_t launch_fl_dec(FlFamily fam, const FlDecArgs& a, int prec, int grid, h
 }
 
 hipError_t launch_fl_fused(const FlFusedArgs& a, int kind, int prec, int cmax, int vmax, int grid, size_t lds,
-                           hipStream_t s) {
-  return fl_launch(fl_kernel(kFlFused, kFlCheck, kind, prec, cmax, vmax), a, grid, lds, s);
+                           hipStream_t s, bool each) {
+  return fl_launch(fl_kernel(kFlFused, kFlCheck, kind, prec, cmax, vmax, each), a, grid, lds, s);
 }
 
 hipError_t fl_occupancy(FlFamily fam, FlPass pass, int kind, int prec, int cmax, int vmax, size_t lds,
-                        int* blocks_per_cu, int* block) {
-  const FlKernel k = fl_kernel(fam, pass, kind, prec, cmax, vmax);
+                        int* blocks_per_cu, int* block, bool each) {
+  const FlKernel k = fl_kernel(fam, pass, kind, prec, cmax, vmax, each);
   *block = k.block;
   if (fam == kFlFused) {
     const hipError_t e = hipFuncSetAttribute(k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, kLdsBytes);
@@ -1277,10 +1439,13 @@ hipError_t fl_occupancy(FlFamily fam, FlPass pass, int kind, int prec, int cmax,
 
 hipError_t fl_private_bytes(FlFamily fam, int kind, int prec, int cn_maxd, int vn_maxd, bool fused, size_t* bytes,
                             const char** name) {
-  FlKernel ks[3] = {fl_kernel(fam, kFlCheck, kind, prec, cn_maxd, vn_maxd),
-                    fl_kernel(fam, kFlVariable, kind, prec, cn_maxd, vn_maxd), {}};
+  FlKernel ks[4] = {fl_kernel(fam, kFlCheck, kind, prec, cn_maxd, vn_maxd),
+                    fl_kernel(fam, kFlVariable, kind, prec, cn_maxd, vn_maxd), {}, {}};
   if (fam == kFlSmall) ks[2] = fl_kernel(fam, kFlDecision, kind, prec, 0, 0);
-  else if (fused) ks[2] = fl_kernel(kFlFused, kFlCheck, kind, prec, cn_maxd, vn_maxd);
+  else if (fused) {   // both forms of the fused kernel: batch stop and per-codeword stop
+    ks[2] = fl_kernel(kFlFused, kFlCheck, kind, prec, cn_maxd, vn_maxd);
+    ks[3] = fl_kernel(kFlFused, kFlCheck, kind, prec, cn_maxd, vn_maxd, true);
+  }
   *bytes = 0;
   *name = "";
   for (const FlKernel& k : ks) {

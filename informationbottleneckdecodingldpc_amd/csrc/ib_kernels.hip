@@ -27,6 +27,7 @@
 //     into the check-node pass (parity of its inputs), and published as device flags that
 //     gate the next launches — no host readback inside the iteration loop.
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 
@@ -1116,9 +1117,11 @@ __device__ __forceinline__ void fused_vn_word(uint32_t lane4, const uint32_t (&i
   vn_word<D, NCW, D <= 4>(lane4, in, chw, fbase, o);
 }
 
-template <int D, int NCW>
+// unsat: bool (some codeword of the dword unsatisfied, the batch-global stop) or uint32_t (the nibble-parity word:
+// bit 4 k + 3 = codeword k unsatisfied, the per-codeword stop)
+template <int D, int NCW, class U>
 __device__ __forceinline__ void fused_cn_dword(uint32_t* msg, int first, int cnt, int lane, uint32_t lane4,
-                                               const IbFusedArgs& a, bool do_par, uint32_t vmask, bool& unsat) {
+                                               const IbFusedArgs& a, bool do_par, uint32_t vmask, U& unsat) {
   uint32_t in[D], o[D];
 #pragma unroll
   for (int j = 0; j < D; ++j) {
@@ -1130,7 +1133,11 @@ __device__ __forceinline__ void fused_cn_dword(uint32_t* msg, int first, int cnt
     uint32_t x = (D & 1) ? 0x88888888u : 0u;
 #pragma unroll
     for (int j = 0; j < D; ++j) x ^= in[j] + bias;
-    if (x & 0x88888888u & vmask) unsat = true;
+    if constexpr (std::is_same_v<U, bool>) {
+      if (x & 0x88888888u & vmask) unsat = true;
+    } else {
+      unsat |= x & 0x88888888u & vmask;
+    }
   }
   const uint32_t fbase = slot_off(a.cn_fslot[D]);
   if constexpr (D == 2) {
@@ -1234,6 +1241,23 @@ __device__ __forceinline__ void fused_dec_dword(const uint32_t* msg, const VnTas
   }
 }
 
+// Per-codeword stop: the decisions of the codewords in `some` (bit s = codeword cw0 + s of these four, a subset of
+// the existing ones) only; all four take store4's one store.
+__device__ __forceinline__ void store4_some(void* out, int dtype, size_t row_off, int cw0, int B, bool aligned,
+                                            uint32_t packed, uint32_t some) {
+  some &= 0xFu;
+  if (some == 0xFu) {
+    store4(out, dtype, row_off, cw0, B, aligned, packed);
+    return;
+  }
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    if (!((some >> s) & 1u)) continue;
+    if (dtype == kU8) reinterpret_cast<uint8_t*>(out)[row_off + cw0 + s] = (uint8_t)(packed >> (8 * s));
+    else reinterpret_cast<int32_t*>(out)[row_off + cw0 + s] = (int32_t)((packed >> (8 * s)) & 0xff);
+  }
+}
+
 // Table staging: a pass's raw image is 256 dwords per quad (each entry byte-packed 4 tables deep);
 // the LDS image replicates every dword over the 32 banks (common.h layout). Two modes:
 // * single set (dbuf = 0): the next phase's raw dwords are loaded into registers at the START of the
@@ -1322,8 +1346,21 @@ struct TablePrefetch {
 // (ceil(B/8) below the grid: C1's 1000 codewords fill 125 of 256 CUs at 8): workgroup g decodes
 // codewords 4g..4g+3 of the 8-codeword channel group g/2, held in nibbles 0..3 of its slots (the channel
 // dword shifted down; nibbles 4..7 stay unused), with half the lookups per node.
-template <int CMAX, int VMAX, int NCW = 8>
+// EACH: per-codeword stop (ibldpc.h "Per-codeword stop"), one pass over the batch. Check pass j (0 < j < imax-1)
+// reduces its syndrome to a mask of the group's unsatisfied codewords in an LDS word (two words after the ticket
+// counters, word j & 1 for pass j, reset one check pass ahead as the counters are); every wave reads that word after
+// the phase's barriers. The codewords that stop at pass j get their decision (the tables of pass j) and iters at
+// once, from the slots as check pass j left them: the variable tables of pass j are staged by then (the staging runs
+// one phase ahead and the stop was not known), so the decision tables are staged as an extra boundary and, if
+// codewords are still running, the variable tables again behind the decision phase — the same load / next_phase
+// sequence, so the phase count and the set parity stay consistent, also across an early exit from the group.
+// (NX: NCW, plus kIbEach for this form — a bit of the group size and not a further parameter, so that the
+// instantiations without it keep their symbols)
+constexpr int kIbEach = 16;
+template <int CMAX, int VMAX, int NX = 8>
 __global__ __launch_bounds__(CMAX <= 8 && VMAX <= 8 ? 1024 : 512) void ib_fused(IbFusedArgs a) {
+  constexpr int NCW = NX & 15;
+  constexpr bool EACH = (NX & kIbEach) != 0;
   constexpr int MAXD = VMAX;
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   lds_at_zero(lds);
@@ -1377,7 +1414,7 @@ __global__ __launch_bounds__(CMAX <= 8 && VMAX <= 8 ? 1024 : 512) void ib_fused(
     mark(3 * ph);       // next phase starts
   };
   // check tasks: slots are contiguous per task (no index loads)
-  auto cn_phase = [&](bool do_par, uint32_t vmask, bool& unsat) __attribute__((always_inline)) {
+  auto cn_phase = [&](bool do_par, uint32_t vmask, auto& unsat) __attribute__((always_inline)) {
     int* c = ctr + (ph & 1);
     if (threadIdx.x == 0) ctr[(ph + 1) & 1] = 0;
     for (;;) {
@@ -1427,6 +1464,87 @@ __global__ __launch_bounds__(CMAX <= 8 && VMAX <= 8 ? 1024 : 512) void ib_fused(
     }
   };
   constexpr int kSub = 8 / NCW;   // workgroup groups per channel group
+  if constexpr (EACH) {
+    int* um = ctr + 2;   // unsatisfied-codeword masks: word j & 1 for check pass j
+    const int Lm = a.imax - 1;
+    for (int wg = blockIdx.x; wg < a.ngroups * kSub; wg += gridDim.x) {
+      const int grp = wg / kSub, sub = wg - grp * kSub;
+      const uint32_t* chg = a.chT + (size_t)grp * a.n_v;
+      const int cwb = grp * 8 + sub * NCW;
+      const uint32_t csh = NCW == 8 ? 0u : (uint32_t)(4 * NCW * sub);
+      const uint32_t vmask = valid_nib8(a.B - cwb) & (NCW == 8 ? 0xFFFFFFFFu : 0xFFFFu);
+      const int valid = min(NCW, a.B - cwb);
+      if (valid <= 0) continue;   // a half group past the end of the batch
+      // codewords still running, bit k = codeword cwb + k (workgroup-uniform: scalars and the LDS word only);
+      // columns past the batch never are
+      uint32_t run = (1u << valid) - 1u;
+      pf.load(a.cn_img, a.cn_nt);
+      vn_phase(chg, csh, [&](const VnTask<MAXD>& v) __attribute__((always_inline)) {
+#pragma unroll
+        for (int k = 0; k < MAXD; ++k)
+          if (k < v.d) msg[v.sl[k]] = v.chw;
+      });
+      next_phase();
+      for (int j = 0;; ++j) {
+        // CN pass j; the variable tables of pass j are staged behind it (the last pass: its decision tables)
+        if (j == Lm) pf.load(a.dec_img + (size_t)j * a.dec_nt * 256, a.dec_nt);
+        else pf.load(a.vn_img + (size_t)j * a.vn_nt * 256, a.vn_nt);
+        const bool do_par = j > 0 && j < Lm;   // the last pass decides every running codeword whatever its syndrome
+        uint32_t un = 0;
+        if (threadIdx.x == 0) um[(j + 1) & 1] = 0;
+        cn_phase(do_par, vmask, un);
+        if (do_par) {
+          uint32_t w = 0;
+#pragma unroll
+          for (int k = 0; k < NCW; ++k) w |= __ballot((un >> (4 * k + 3)) & 1u) != 0ull ? 1u << k : 0u;
+          if (w != 0 && lane == 0) atomicOr(&um[j & 1], (int)w);
+        }
+        next_phase();
+        uint32_t some = run;   // the codewords that stop at pass j
+        if (j < Lm) some = do_par ? run & ~(uint32_t)__builtin_amdgcn_readfirstlane(um[j & 1]) : 0u;
+        if (some != 0) {
+          if (a.iters && threadIdx.x < NCW && ((some >> threadIdx.x) & 1u)) a.iters[cwb + threadIdx.x] = j;
+          if (j < Lm) {   // extra boundary: the decision tables of pass j (no ticket phase before it: its counter)
+            if (threadIdx.x == 0) ctr[(ph + 1) & 1] = 0;
+            pf.load(a.dec_img + (size_t)j * a.dec_nt * 256, a.dec_nt);
+            next_phase();
+          }
+          run &= ~some;
+          if (run != 0) pf.load(a.vn_img + (size_t)j * a.vn_nt * 256, a.vn_nt);   // the variable tables again
+          vn_phase(chg, csh, [&](const VnTask<MAXD>& v) __attribute__((always_inline)) {
+            uint32_t r[2] = {0u, 0u};
+            switch (v.d) {
+              case 1: fused_dec_dword<1, MAXD, NCW>(msg, v, lane4, r); break;
+#define X(D) case D: if constexpr (D <= MAXD) fused_dec_dword<D, MAXD, NCW>(msg, v, lane4, r); break;
+              IBL_DEG_CASES(X)
+#undef X
+              default: break;
+            }
+            const size_t o = (size_t)a.vn_node[v.pos + lane] * a.B + cwb;
+            store4_some(a.out, a.out_dtype, o, 0, a.B - cwb, a.aligned != 0, r[0], some);
+            if constexpr (NCW == 8) store4_some(a.out, a.out_dtype, o, 4, a.B - cwb, a.aligned != 0, r[1], some >> 4);
+          });
+          if (run == 0) break;
+          next_phase();
+        }
+        pf.load(a.cn_img + (size_t)(j + 1) * a.cn_nt * 256, a.cn_nt);
+        vn_phase(chg, csh, [&](const VnTask<MAXD>& v) __attribute__((always_inline)) {
+          switch (v.d) {
+            case 1: fused_vn_dword<1, MAXD, NCW>(msg, v, lane4, a); break;
+#define X(D) case D: if constexpr (D <= MAXD) fused_vn_dword<D, MAXD, NCW>(msg, v, lane4, a); break;
+            IBL_DEG_CASES(X)
+#undef X
+            default: break;
+          }
+        });
+        next_phase();
+      }
+      __syncthreads();   // every wave done with this group's slots before the next group's send
+      ++ph;
+      lane4 = lane4c | ((ph & 1) ? set_off : 0u);
+    }
+    return;
+  }
   for (int wg = blockIdx.x; wg < a.ngroups * kSub; wg += gridDim.x) {
     const int grp = wg / kSub, sub = wg - grp * kSub;
     const uint32_t* chg = a.chT + (size_t)grp * a.n_v;   // channel by variable position (vn_node order)
@@ -1967,7 +2085,17 @@ hipError_t launch_ib_stage_t(const void* ch, int dtype, int n, int B, const int3
   hipLaunchKernelGGL(ib_stage_t, dim3(grid), dim3(256), 0, s, ch, dtype, n, B, perm, chT);
   return hipGetLastError();
 }
-static const void* ib_fused_kernel(int cmax, int vmax, int ncw) {
+static const void* ib_fused_kernel(int cmax, int vmax, int ncw, bool each = false) {
+  if (each && ncw == 4) {
+    if (cmax <= 8 && vmax <= 4) return (const void*)ib_fused<8, 4, 4 | kIbEach>;
+    if (cmax <= 8 && vmax <= 8) return (const void*)ib_fused<8, 8, 4 | kIbEach>;
+    return (const void*)ib_fused<16, 16, 4 | kIbEach>;
+  }
+  if (each) {
+    if (cmax <= 8 && vmax <= 4) return (const void*)ib_fused<8, 4, 8 | kIbEach>;
+    if (cmax <= 8 && vmax <= 8) return (const void*)ib_fused<8, 8, 8 | kIbEach>;
+    return (const void*)ib_fused<16, 16, 8 | kIbEach>;
+  }
   if (ncw == 4) {
     if (cmax <= 8 && vmax <= 4) return (const void*)ib_fused<8, 4, 4>;
     if (cmax <= 8 && vmax <= 8) return (const void*)ib_fused<8, 8, 4>;
@@ -1977,14 +2105,15 @@ static const void* ib_fused_kernel(int cmax, int vmax, int ncw) {
   if (cmax <= 8 && vmax <= 8) return (const void*)ib_fused<8, 8>;
   return (const void*)ib_fused<16, 16>;
 }
-hipError_t launch_ib_fused(const IbFusedArgs& a, int cmax, int vmax, int grid, int block, size_t lds, hipStream_t s) {
+hipError_t launch_ib_fused(const IbFusedArgs& a, int cmax, int vmax, int grid, int block, size_t lds, hipStream_t s,
+                           bool each) {
   IbFusedArgs args = a;
   void* p[] = {&args};
-  return hipLaunchKernel(ib_fused_kernel(cmax, vmax, a.ncw), dim3(grid), dim3(block), p, lds, s);
+  return hipLaunchKernel(ib_fused_kernel(cmax, vmax, a.ncw, each), dim3(grid), dim3(block), p, lds, s);
 }
 hipError_t ib_fused_occupancy(int cmax, int vmax, int ncw, size_t lds, int* blocks_per_cu, int* block,
-                              size_t* private_bytes) {
-  const void* f = ib_fused_kernel(cmax, vmax, ncw);
+                              size_t* private_bytes, bool each) {
+  const void* f = ib_fused_kernel(cmax, vmax, ncw, each);
   // the dynamic-LDS cap is an attribute of the kernel instantiation, shared by every decoder that launches it:
   // set it to the CU's whole LDS (here and in the other *_occupancy functions), never to one decoder's size,
   // or a smaller decoder created later would lower the cap an earlier, larger one launches with

@@ -5,12 +5,18 @@
 The regular kernels (``kernels_template.cl``) are the irregular ones with one degree per node
 type and no matching; the same ``ibl_ib`` engine serves both (the LUT offsets coincide because
 ``d_c_max``/``d_v_max`` equal the node degrees).
+
+``stop`` (extension, keyword-only): ``"batch"`` (default, the reference's stop when the whole batch's syndrome is
+zero) or ``"codeword"``: ``decode_OpenCL`` stops each codeword on its own (include/ibldpc.h "Per-codeword stop";
+fused kernel only, ``init_OpenCL_decoding`` raises when the code does not run on it) and ``last_iters`` holds the
+last decode's counts (int32 device tensor, B entries). ``decode_on_host`` is unchanged.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
+from . import _lib
 from ._dropin import CodeMixin, resolve_device, to_device_input
 from .engine import IBDecoder, count_below
 from .tables import IBTables, identity_matching
@@ -20,7 +26,11 @@ class Discrete_LDPC_Decoder_class(CodeMixin):
     """Reference ``__init__`` (discrete_LDPC_decoder.py:30-51)."""
 
     def __init__(self, filename, imax_, cardinality_T_channel_, cardinality_T_decoder_ops_,
-                 Trellis_checknode_vector_a_, Trellis_varnode_vector_a_, msg_at_time_):
+                 Trellis_checknode_vector_a_, Trellis_varnode_vector_a_, msg_at_time_, *, stop: str = "batch"):
+        if stop not in ("batch", "codeword"):
+            raise ValueError('stop must be "batch" or "codeword"')
+        self.stop = stop
+        self.last_iters = None
         self._init_code(filename)
         self.imax = int(imax_)
         self.cardinality_T_channel = int(cardinality_T_channel_)
@@ -56,6 +66,9 @@ class Discrete_LDPC_Decoder_class(CodeMixin):
         self.context = dev
         self.msg_at_time = int(msg_at_time_)
         self._dec = IBDecoder(self._graph_on(dev), self._tables(), False, self.msg_at_time)
+        if self.stop == "codeword" and not self._dec.fused:
+            self._dec = None
+            raise _lib.IBLError('stop="codeword" needs the fused kernel, and this code does not run on it')
 
     def decode_OpenCL(self, received_blocks, buffer_in=False, return_buffer=False, out_dtype=torch.int32):
         """Reference :202-295."""
@@ -66,7 +79,11 @@ class Discrete_LDPC_Decoder_class(CodeMixin):
             self.init_OpenCL_decoding(ch.shape[1], self.device)
         # out_dtype: the reference's int32 cluster ids; torch.uint8 holds the same values in a quarter of the bytes
         # (the pipelined BER driver's decisions)
-        out = self._dec.decode(ch, out_dtype=out_dtype, early_stop=True)
+        if self.stop == "codeword":
+            self.last_iters = torch.empty(ch.shape[1], dtype=torch.int32, device=self.device)
+            out = self._dec.decode(ch, out_dtype=out_dtype, early_stop="codeword", iters=self.last_iters)
+        else:
+            out = self._dec.decode(ch, out_dtype=out_dtype, early_stop=True)
         return out if return_buffer else out.cpu().numpy()
 
     def return_errors_all_zero(self, varnode_output_buffer):

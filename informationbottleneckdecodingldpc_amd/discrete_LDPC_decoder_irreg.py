@@ -4,12 +4,18 @@
 
 Same constructor, attributes and methods; ``decode_OpenCL`` / ``return_errors_all_zero`` /
 ``decode_on_host`` execute ``libibldpc.so`` (``ibl_ib_decode``, ``ibl_count_below``).
+
+``stop`` (extension, keyword-only): ``"batch"`` (default, the reference's stop when the whole batch's syndrome is
+zero) or ``"codeword"``: ``decode_OpenCL`` stops each codeword on its own (include/ibldpc.h "Per-codeword stop";
+fused kernel only, ``init_OpenCL_decoding`` raises when the code does not run on it) and ``last_iters`` holds the
+last decode's counts (int32 device tensor, B entries). ``decode_on_host`` is unchanged.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
+from . import _lib
 from ._dropin import CodeMixin, is_true, resolve_device, to_device_input
 from .engine import IBDecoder, count_below
 from .tables import IBTables, identity_matching
@@ -20,7 +26,11 @@ class Discrete_LDPC_Decoder_class_irregular(CodeMixin):
 
     def __init__(self, filename, imax_, cardinality_T_channel_, cardinality_T_decoder_ops_,
                  Trellis_checknode_vector_a_, Trellis_varnode_vector_a_, matching_vector_checknode_,
-                 matching_vector_varnode_, msg_at_time_, match='true'):
+                 matching_vector_varnode_, msg_at_time_, match='true', *, stop: str = "batch"):
+        if stop not in ("batch", "codeword"):
+            raise ValueError('stop must be "batch" or "codeword"')
+        self.stop = stop
+        self.last_iters = None
         self._init_code(filename)
         self.imax = int(imax_)
         self.cardinality_T_channel = int(cardinality_T_channel_)
@@ -65,6 +75,9 @@ class Discrete_LDPC_Decoder_class_irregular(CodeMixin):
         self.context = dev
         self.msg_at_time = int(msg_at_time_)
         self._dec = IBDecoder(self._graph_on(dev), self._tables(), is_true(self.match), self.msg_at_time)
+        if self.stop == "codeword" and not self._dec.fused:
+            self._dec = None
+            raise _lib.IBLError('stop="codeword" needs the fused kernel, and this code does not run on it')
 
     def decode_OpenCL(self, received_blocks, buffer_in=False, return_buffer=False, out_dtype=torch.int32):
         """Decode [N][B] channel cluster ids (reference :245-341); batch-global early stop."""
@@ -75,7 +88,11 @@ class Discrete_LDPC_Decoder_class_irregular(CodeMixin):
             self.init_OpenCL_decoding(ch.shape[1], self.device)
         # out_dtype: the reference's int32 cluster ids; torch.uint8 holds the same values in a quarter of the bytes
         # (the pipelined BER driver's decisions)
-        out = self._dec.decode(ch, out_dtype=out_dtype, early_stop=True)
+        if self.stop == "codeword":
+            self.last_iters = torch.empty(ch.shape[1], dtype=torch.int32, device=self.device)
+            out = self._dec.decode(ch, out_dtype=out_dtype, early_stop="codeword", iters=self.last_iters)
+        else:
+            out = self._dec.decode(ch, out_dtype=out_dtype, early_stop=True)
         return out if return_buffer else out.cpu().numpy()
 
     def return_errors_all_zero(self, varnode_output_buffer):

@@ -152,8 +152,15 @@ class IBDecoder:
         return int(n.value)
 
     def decode(self, ch: torch.Tensor, out: Optional[torch.Tensor] = None, out_dtype=torch.int32,
-               early_stop: bool = True, iters: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Decode ``ch`` ([N][B] cluster ids, uint8/int32, on the decoder's device)."""
+               early_stop=True, iters: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Decode ``ch`` ([N][B] cluster ids, uint8/int32, on the decoder's device). ``early_stop``: True (the
+        reference's stop, when the whole batch's syndrome is zero; ``iters`` receives one count), False, or
+        ``"codeword"``: every codeword stops on its own and ``iters`` (int32 device tensor of at least B entries, or
+        None) receives each one's count (``ibl_ib_decode_each``; fused kernel only, :class:`_lib.IBLError`
+        otherwise)."""
+        each = isinstance(early_stop, str)
+        if each and early_stop != "codeword":
+            raise ValueError('early_stop must be True, False or "codeword"')
         n = self.graph.edges.n_v
         _check_tensor(ch, self.device, n, "channel values")
         if ch.dtype not in _DT_IB:
@@ -168,7 +175,14 @@ class IBDecoder:
         if iters is not None:
             if iters.dtype != torch.int32 or iters.device != self.device or iters.numel() < 1:
                 raise ValueError("iters must be an int32 device tensor")
+            if each and (iters.numel() < B or not iters.is_contiguous()):
+                raise ValueError("iters must be a contiguous int32 device tensor of at least B entries")
             it_ptr = iters.data_ptr()
+        if each:
+            _lib.check(_lib.load().ibl_ib_decode_each(self._h, ch.data_ptr(), _DT_IB[ch.dtype], B, out.data_ptr(),
+                                                      _DT_IB[out.dtype], it_ptr, _stream_ptr(self.device)),
+                       "ibl_ib_decode_each")
+            return out
         _lib.check(_lib.load().ibl_ib_decode(self._h, ch.data_ptr(), _DT_IB[ch.dtype], B, out.data_ptr(),
                                              _DT_IB[out.dtype], int(bool(early_stop)), it_ptr,
                                              _stream_ptr(self.device)), "ibl_ib_decode")
@@ -275,7 +289,14 @@ class FloatDecoder:
         return int(v.value)
 
     def decode(self, llr: torch.Tensor, out: Optional[torch.Tensor] = None, out_dtype=None,
-               early_stop: bool = True, iters: Optional[torch.Tensor] = None) -> torch.Tensor:
+               early_stop=True, iters: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``early_stop``: True (the reference's stop, when the whole batch's syndrome is zero; ``iters`` receives
+        one count), False, or ``"codeword"``: every codeword stops on its own and ``iters`` (int32 device tensor of
+        at least B entries, or None) receives each one's count (``ibl_float_decode_each``; fused kernel only,
+        :class:`_lib.IBLError` otherwise)."""
+        each = isinstance(early_stop, str)
+        if each and early_stop != "codeword":
+            raise ValueError('early_stop must be True, False or "codeword"')
         n = self.graph.edges.n_v
         _check_tensor(llr, self.device, n, "channel LLRs")
         if llr.dtype not in _DT_FL:
@@ -290,7 +311,14 @@ class FloatDecoder:
         if iters is not None:
             if iters.dtype != torch.int32 or iters.device != self.device or iters.numel() < 1:
                 raise ValueError("iters must be an int32 device tensor")
+            if each and (iters.numel() < B or not iters.is_contiguous()):
+                raise ValueError("iters must be a contiguous int32 device tensor of at least B entries")
             it_ptr = iters.data_ptr()
+        if each:
+            _lib.check(_lib.load().ibl_float_decode_each(self._h, llr.data_ptr(), _DT_FL[llr.dtype], B,
+                                                         out.data_ptr(), _DT_FL[out.dtype], it_ptr,
+                                                         _stream_ptr(self.device)), "ibl_float_decode_each")
+            return out
         _lib.check(_lib.load().ibl_float_decode(self._h, llr.data_ptr(), _DT_FL[llr.dtype], B, out.data_ptr(),
                                                 _DT_FL[out.dtype], int(bool(early_stop)), it_ptr,
                                                 _stream_ptr(self.device)), "ibl_float_decode")

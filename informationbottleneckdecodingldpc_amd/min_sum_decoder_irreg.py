@@ -9,6 +9,11 @@ dtype.
 ``alpha`` / ``beta`` (extension, keyword-only) select normalised / offset min-sum: every check magnitude
 becomes ``max(alpha * m - beta, 0)`` (include/ibldpc.h "Corrected min-sum"). The default (1, 0) is the
 reference's plain min-sum; ``correction`` returns the pair.
+
+``stop`` (extension, keyword-only): ``"batch"`` (default, the reference's stop when the whole batch's syndrome is
+zero) or ``"codeword"``: every ``decode_OpenCL*`` stops each codeword on its own (include/ibldpc.h "Per-codeword
+stop"; fused kernel only, ``init_OpenCL_decoding`` raises when the code does not run on it) and ``last_iters``
+holds the last decode's counts (int32 device tensor, B entries). ``decode_on_host`` is unchanged.
 """
 from __future__ import annotations
 
@@ -28,7 +33,11 @@ class Min_Sum_Decoder_class_irregular(CodeMixin):
     _kind = _KIND
 
     def __init__(self, filename, imax_, cardinality_T_channel_, msg_at_time_, *, precision=torch.float32,
-                 llr_max: float = 150.0, alpha: float = 1.0, beta: float = 0.0):
+                 llr_max: float = 150.0, alpha: float = 1.0, beta: float = 0.0, stop: str = "batch"):
+        if stop not in ("batch", "codeword"):
+            raise ValueError('stop must be "batch" or "codeword"')
+        self.stop = stop
+        self.last_iters = None
         self.alpha, self.beta = float(alpha), float(beta)
         if self._kind != _lib.IBL_MINSUM and (self.alpha, self.beta) != (1.0, 0.0):
             raise ValueError("alpha / beta correct min-sum only: belief propagation takes neither")
@@ -52,6 +61,9 @@ class Min_Sum_Decoder_class_irregular(CodeMixin):
         self.msg_at_time = int(msg_at_time_)
         self._dec = FloatDecoder(self._graph_on(dev), self._kind, self.imax, self.msg_at_time,
                                  precision=self.precision, llr_max=self.llr_max, alpha=self.alpha, beta=self.beta)
+        if self.stop == "codeword" and not self._dec.fused:
+            self._dec = None
+            raise _lib.IBLError('stop="codeword" needs the fused kernel, and this code does not run on it')
 
     @property
     def correction(self):
@@ -69,7 +81,11 @@ class Min_Sum_Decoder_class_irregular(CodeMixin):
             # also |x| > 709.089 in fp64, +-inf in fp32) raise instead of returning unspecified values
             # (FloatDecoder.input_violations); counts left by earlier return_buffer decodes are cleared first
             self._dec.input_violations(raise_on_error=False)
-        out = self._dec.decode(llr, early_stop=early_stop)
+        if early_stop and self.stop == "codeword":
+            self.last_iters = torch.empty(llr.shape[1], dtype=torch.int32, device=self.device)
+            out = self._dec.decode(llr, early_stop="codeword", iters=self.last_iters)
+        else:
+            out = self._dec.decode(llr, early_stop=early_stop)
         if return_buffer:
             return out
         self._dec.input_violations()
