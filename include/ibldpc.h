@@ -171,6 +171,18 @@ int ibl_ib_timing_read(ibl_ib* h, double* cn_ms, int32_t* cn_launches, double* v
  * .init_OpenCL_decoding (min_sum_decoder_irreg.py:167-218, bp_decoder_irreg.py:167-218).
  * kind = IBL_MINSUM | IBL_BP; precision = IBL_F32 (BASELINE build) | IBL_F64 (the reference's
  * double precision); llr_max = clamp of BP / VN messages (the reference's LLR_MAX = 150).
+ * Degrees (ibl_float_create and ibl_float_create_corrected alike): check degrees up to 32, variable degrees up to
+ * 16; a code outside either range is IBL_EUNSUPPORTED, and ibl_last_error names the kind of node, the limit and the
+ * code's largest degree of that kind.  A handle whose code has a check of degree above 16 is WIDE
+ * (ibl_float_is_wide; DVB-S2 normal frames at rates 4/5 to 9/10, 5G NR base graph 1): its check passes and its fused
+ * kernel are instantiations of their own, in which checks of degree 17..32 run one body that takes the degree at
+ * run time, and checks of degree 2..16 the bodies of a narrow handle.  A narrow handle runs exactly the kernels it
+ * ran before wide handles existed.  The semantics are the same at every degree: min-sum magnitudes are the minimum
+ * over the other inputs, signs the XOR of their signs, bit-identical to the reference's fold; corrected min-sum
+ * applies its two rounded operations to the (minimum, second minimum) pair; fp64 BP folds the other inputs in the
+ * reference's order for every output; fp32 BP keeps its forward-backward association order, extended to the
+ * degree.  The three kernel families (per pass, small batch, fused) give the same bits, the per-pass path folds
+ * degree-2 variables, and the per-codeword stop runs on a wide handle that takes the fused kernel, as on a narrow one.
  */
 int ibl_float_create(const ibl_graph* g, int32_t kind, int32_t imax, double llr_max, int32_t precision,
                      int32_t max_batch, ibl_float** out);
@@ -231,6 +243,11 @@ int ibl_float_fused_geometry(const ibl_float* h, int32_t B, int32_t* ngroups, in
  * variables, or IBL_FL_FOLD=0 in the environment when the decoder was created).
  */
 int ibl_float_folded(const ibl_float* h, int32_t* n_folded);
+/*
+ * *wide = 1 for a handle whose code has a check of degree above 16 (see ibl_float_create), else 0.  Read-only; as
+ * ibl_layered_is_wide for the layered decoders.
+ */
+int ibl_float_is_wide(const ibl_float* h, int32_t* wide);
 /*
  * Small-batch kernels of the per-pass float path (no reference counterpart; outputs identical): batches
  * B <= max_b run kernels whose wave item is up to 64 nodes of one degree (lane = node) x 4 fp32 / 2 fp64

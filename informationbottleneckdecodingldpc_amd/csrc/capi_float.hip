@@ -21,6 +21,7 @@ struct ibl_float {
   // kkind is the check-body kind every launch, occupancy and private-segment query takes (0, 1 or 2)
   int32_t kkind = 0;
   double alpha = 1.0, beta = 0.0;
+  bool wide = false;        // a check of degree 17..32: the check and fused kernels are the wide instantiations
   DevBuf<uint8_t> cin, vbuf0, vbuf1, chf;   // inboxes and staged channel, fp32 or fp64 elements
   DevBuf<int32_t> flags, dL;
   int grid_cn = 0, grid_vn = 0;
@@ -304,9 +305,15 @@ int float_decode_passes(ibl_float* h, const void* d_llr, int32_t llr_dtype, int3
 // the check-body kind of the kernels: `kind`, or 2 for corrected min-sum with (alpha, beta) != (1, 0).
 int float_create(const ibl_graph* g, int32_t kind, int32_t kkind, double alpha, double beta, int32_t imax,
                  double llr_max, int32_t precision, int32_t max_batch, ibl_float** out) {
-  if (g->dcm > kMaxD || g->dvm > kMaxD) return fail(IBL_EUNSUPPORTED, "float decoders support node degrees <= 16");
+  if (g->dcm > kFlWideD)
+    return fail(IBL_EUNSUPPORTED, "float decoders support check degrees <= 32 (the code has a check of degree " +
+                                      std::to_string(g->dcm) + ")");
+  if (g->dvm > kMaxD)
+    return fail(IBL_EUNSUPPORTED, "float decoders support variable degrees <= 16 (the code has a variable of degree " +
+                                      std::to_string(g->dvm) + ")");
   HIPCHK(hipSetDevice(g->device));
   std::unique_ptr<ibl_float> h(new ibl_float());
+  h->wide = g->dcm > kMaxD;
   h->g = g; h->kind = kind; h->imax = imax; h->prec = precision; h->max_batch = max_batch; h->llr_max = llr_max;
   h->kkind = kkind; h->alpha = alpha; h->beta = beta;
   // rows padded to the wave item of the per-pass kernels (fp32 256 / fp64 128 codewords), not beyond: the
@@ -387,6 +394,12 @@ int ibl_float_small_batch(const ibl_float* h, int32_t* max_b) {
 int ibl_float_folded(const ibl_float* h, int32_t* n_folded) {
   if (!h || !n_folded) return fail(IBL_EINVAL, "NULL argument");
   *n_folded = h->n_folded;
+  return IBL_OK;
+}
+
+int ibl_float_is_wide(const ibl_float* h, int32_t* wide) {
+  if (!h || !wide) return fail(IBL_EINVAL, "NULL argument");
+  *wide = h->wide ? 1 : 0;
   return IBL_OK;
 }
 

@@ -185,6 +185,10 @@ struct IbGenDecArgs {
 // on-chip — with a check, a variable and a decision (APP output) pass each; the fused kernel is all of them.
 enum FlFamily : int { kFlPerPass = 0, kFlSmall = 1, kFlFused = 2 };
 enum FlPass : int { kFlCheck = 0, kFlVariable = 1, kFlDecision = 2, kFlSend = 3 };
+// Largest check degree of the float decoders. Checks above kMaxD (plan.h; still the variable side's limit and the IB
+// fast path's) make a handle wide: its check and fused kernels are the MAXD = kFlWideD instantiations, which run
+// degrees 17..kFlWideD through one body (float_kernels.hip fl_cn_wide_body).
+constexpr int kFlWideD = 32;
 // by decoder precision (or buffer dtype): codewords in a lane's 16 bytes, bytes per element
 constexpr int fl_cw_per_lane(int prec) { return prec == kF32 ? 4 : 2; }
 constexpr size_t fl_elem_size(int dtype) { return dtype == kF32 ? 4 : 8; }

@@ -231,6 +231,12 @@ __device__ __forceinline__ bool syndrome_bit(const F (&m)[D][Vec<F>::N], int s) 
 
 // Check-body kinds: the public IBL_MINSUM (0) and IBL_BP (1), and the library's own corrected min-sum.
 constexpr int kFlCorrected = 2;
+// The check and fused kernels take the kind as KX = kind plus flag bits (kFlEach, at fl_fused: the per-codeword-stop
+// form). kFlWide marks the wide instantiations and goes with MAXD = kFlWideD: a bit of the kind and not a parameter
+// or a kernel of another name, so that the narrow instantiations keep their symbols and a wide kernel's symbol differs
+// from every narrow one's in its first argument (the censuses of the narrow kernels by kind, as
+// tests/test_cpu_minsum_corrected.py's of kind 2, then count what they always counted).
+constexpr int kFlWide = 8;
 
 // Corrected min-sum magnitude (ibldpc.h "Corrected min-sum"): r = max(a * M - b, 0) as one rounded
 // multiplication and one rounded subtraction. HIP contracts a * M - b into a fused multiply-add by default,
@@ -425,6 +431,157 @@ __device__ __forceinline__ void fl_cn_body(const F (&m)[D][Vec<F>::N], F lm, F c
   }
 }
 
+// Wide check-node body: one body for every degree d in 17..kFlWideD (wave-uniform, taken at run time), for the wide
+// instantiations (MAXD = kFlWideD) of the three families. It holds no input array: load(j, r) fetches input j of
+// the lane's codewords (any number of times), put(w, o) receives output w in ascending w, and input w is always
+// loaded before output w is put, so the fused kernel may run it in place. par[s] gets the XOR of the high words of
+// codeword s's inputs (bit 31: the syndrome parity, as syndrome_bit).
+//   min-sum / corrected: the running (min, second min, position of the first minimum) and a word of the inputs'
+//     sign bits per codeword (the wide layered kernels' form): output w takes the second minimum at the first
+//     minimum's position and the minimum elsewhere. On a tie the second minimum equals the minimum, so the values
+//     are those of fl_cn_body's |m_w| == mn1 ? o2 : o1 bit for bit; zero inputs and the tiny-LLR assumption as there.
+//   fp32 BP: fl_cn_body's forward-backward form in the same association order (S_j = m_j [+] S_{j+1},
+//     out_w = P_w [+] S_{w+1}, P_{w+1} = m_w [+] P_w). The suffixes stay in registers (31 x N), the steps are fully
+//     unrolled and predicated on the degree, and the forward sweep loads each input again instead of keeping it.
+//   fp64 BP: the reference's per-output sequential folds with the shared prefix (kernels_min_and_BP.cl:63-69), as
+//     rolled loops that load their inputs again: (d - 2)(d + 3) / 2 box-pluses, each an exp and a log call.
+template <typename F> __device__ __forceinline__ uint32_t fl_hi32(F x) {
+  if constexpr (sizeof(F) == 4) return __float_as_uint(x);
+  else return (uint32_t)((uint64_t)__double_as_longlong(x) >> 32);
+}
+template <typename F> __device__ __forceinline__ F fl_with_sign(F mag, uint32_t sign31) {   // mag >= +0
+  if constexpr (sizeof(F) == 4) return __uint_as_float((sign31 & 0x80000000u) | __float_as_uint(mag));
+  else return __longlong_as_double((long long)(((uint64_t)(sign31 & 0x80000000u) << 32) | (uint64_t)__double_as_longlong(mag)));
+}
+template <int KIND, typename F, class Load, class Put>
+__device__ __forceinline__ void fl_cn_wide_body(int d, F lm, F ca, F cb, uint32_t (&par)[Vec<F>::N], Load&& load,
+                                                Put&& put) {
+  constexpr int N = Vec<F>::N;
+  F o[N], r[N];
+  if constexpr (KIND != 1) {
+    using Bt = Bits<F>;
+    F mn1[N], mn2[N];
+    uint32_t sw[N];   // bit j = sign of input j
+    int pos[N];
+    load(0, r);
+#pragma unroll
+    for (int s = 0; s < N; ++s) {
+      mn1[s] = fabs(r[s]);
+      mn2[s] = __builtin_huge_val();
+      pos[s] = 0;
+      par[s] = fl_hi32(r[s]);
+      sw[s] = par[s] >> 31;
+    }
+#pragma unroll 8
+    for (int j = 1; j < d; ++j) {
+      load(j, r);
+#pragma unroll
+      for (int s = 0; s < N; ++s) {
+        const uint32_t h = fl_hi32(r[s]);
+        par[s] ^= h;
+        sw[s] |= (h >> 31) << j;
+        pos[s] = fabs(r[s]) < mn1[s] ? j : pos[s];
+        mn2[s] = Bt::med3_a(mn1[s], mn2[s], r[s]);
+        mn1[s] = Bt::lo_a(mn1[s], r[s]);
+      }
+    }
+    F o1[N], o2[N];
+#pragma unroll
+    for (int s = 0; s < N; ++s) {
+      o1[s] = KIND == kFlCorrected ? fl_corrected(mn1[s], ca, cb) : mn1[s];
+      o2[s] = KIND == kFlCorrected ? fl_corrected(mn2[s], ca, cb) : mn2[s];
+    }
+#pragma unroll 2
+    for (int w = 0; w < d; ++w) {
+#pragma unroll
+      for (int s = 0; s < N; ++s)
+        o[s] = fl_with_sign<F>(pos[s] == w ? o2[s] : o1[s], par[s] ^ ((sw[s] >> w) << 31));
+      put(w, o);
+    }
+  } else if constexpr (sizeof(F) == 4) {
+    F S[kFlWideD][N], P[N];   // S[j] = m_j [+] ... [+] m_{d-1}, 1 <= j <= d - 1
+#pragma unroll
+    for (int s = 0; s < N; ++s) par[s] = 0;
+#pragma unroll
+    for (int j = kFlWideD - 1; j >= 1; --j) {
+      if (j <= 16 || j < d) {   // d >= 17
+        load(j, r);
+        constexpr int kLast = kFlWideD - 1;
+        const int jn = j < kLast ? j + 1 : kLast;   // j = 31 is always the last input
+#pragma unroll
+        for (int s = 0; s < N; ++s) par[s] ^= fl_hi32(r[s]);
+        if (j >= 16 && j == d - 1) {
+#pragma unroll
+          for (int s = 0; s < N; ++s) S[j][s] = r[s];
+        } else {
+#pragma unroll
+          for (int s = 0; s < N; ++s) S[j][s] = boxplus(r[s], S[jn][s], lm);
+        }
+      }
+    }
+    load(0, r);
+#pragma unroll
+    for (int s = 0; s < N; ++s) {
+      par[s] ^= fl_hi32(r[s]);
+      o[s] = clampllr(S[1][s], lm);
+      P[s] = r[s];
+    }
+    put(0, o);
+#pragma unroll
+    for (int w = 1; w <= kFlWideD - 2; ++w) {
+      if (w <= 15 || w <= d - 2) {
+        load(w, r);
+#pragma unroll
+        for (int s = 0; s < N; ++s) o[s] = clampllr(boxplus(P[s], S[w + 1][s], lm), lm);
+        put(w, o);
+#pragma unroll
+        for (int s = 0; s < N; ++s) P[s] = boxplus(r[s], P[s], lm);
+      }
+    }
+#pragma unroll
+    for (int s = 0; s < N; ++s) o[s] = clampllr(P[s], lm);
+    put(d - 1, o);
+  } else {
+    F t[N], P[N];
+    load(1, t);
+#pragma unroll
+    for (int s = 0; s < N; ++s) par[s] = fl_hi32(t[s]);
+    for (int j = 2; j < d; ++j) {
+      load(j, r);
+#pragma unroll
+      for (int s = 0; s < N; ++s) {
+        par[s] ^= fl_hi32(r[s]);
+        t[s] = boxplus(r[s], t[s], lm);
+      }
+    }
+    load(0, P);
+#pragma unroll
+    for (int s = 0; s < N; ++s) {
+      par[s] ^= fl_hi32(P[s]);
+      o[s] = clampllr(t[s], lm);
+    }
+    put(0, o);
+    for (int w = 1; w <= d - 2; ++w) {
+#pragma unroll
+      for (int s = 0; s < N; ++s) t[s] = P[s];
+      for (int j = w + 1; j < d; ++j) {
+        load(j, r);
+#pragma unroll
+        for (int s = 0; s < N; ++s) t[s] = boxplus(r[s], t[s], lm);
+      }
+      load(w, r);
+#pragma unroll
+      for (int s = 0; s < N; ++s) o[s] = clampllr(t[s], lm);
+      put(w, o);
+#pragma unroll
+      for (int s = 0; s < N; ++s) P[s] = boxplus(r[s], P[s], lm);
+    }
+#pragma unroll
+    for (int s = 0; s < N; ++s) o[s] = clampllr(P[s], lm);
+    put(d - 1, o);
+  }
+}
+
 
 // Degree-2 variable fold (FlArgs::fold): a degree-2 variable's update is one add and a clamp per output,
 // out(c1) = clamp(ch + m(c2 -> v)) (kernels_min_and_BP.cl:110-118; fl_vn_body<D=2> in the same order), so
@@ -478,6 +635,56 @@ __device__ __forceinline__ void fl_cn_item(const FlArgs& a, int node, int st, in
   fl_cn_body<KIND, F, D>(m, lm, ca, cb,
                          [&](int w, const F (&o)[N]) __attribute__((always_inline)) { ob.put(w, o, sink); });
   ob.flush(sink);
+}
+
+// Syndrome of a wide check from fl_cn_wide_body's parity words; U as fused_cn_item's
+template <typename F, class U>
+__device__ __forceinline__ void fl_wide_syndrome(const uint32_t (&par)[Vec<F>::N], int valid, U& unsat) {
+#pragma unroll
+  for (int s = 0; s < Vec<F>::N; ++s) {
+    const bool p = (par[s] >> 31) != 0 && s < valid;
+    if constexpr (std::is_same_v<U, bool>) unsat |= p;
+    else unsat |= (U)p << s;
+  }
+}
+
+// fl_cn_item for a check of degree d in 17..kFlWideD (fl_cn_wide_body): the same fold sink, every output stored as
+// soon as it is final, its row loaded as a scalar then
+template <int KIND, typename F>
+__device__ __forceinline__ void fl_cn_wide_item(const FlArgs& a, int node, int st, int d, int cw0, bool do_par,
+                                                int valid, bool& unsat) {
+  constexpr int N = Vec<F>::N;
+  const F lm = (F)a.llr_max;
+  int fp0 = -1, fp1 = -1, fd0 = 0, fd1 = 0;
+  F c0[N], c1[N];
+  if (a.fold_mode) {
+    const int* fr = a.fold + (size_t)kFoldRec * node;
+    fp0 = sload(fr, 0);
+    fp1 = sload(fr, 1);
+    fd0 = sload(fr, 2);
+    fd1 = sload(fr, 3);
+    if (fp0 >= 0) fl_load16<kFlNt, F>(a.ch, c0, a.ldb, sload(fr, 4), cw0);
+    if (fp1 >= 0) fl_load16<kFlNt, F>(a.ch, c1, a.ldb, sload(fr, 5), cw0);
+  }
+  auto fold_put = [&](int w, const F (&c)[N], int row, const F (&o)[N]) __attribute__((always_inline)) {
+    F f[N];
+#pragma unroll
+    for (int s = 0; s < N; ++s) f[s] = clampllr(c[s] + o[s], lm);
+    fl_store16<kFlNt, F>(a.fout, f, a.ldb, row, cw0);
+    if (a.fold_mode == 2) fl_store16<kFlNt, F>(a.out, o, a.ldb, sload(a.tgt, st + w), cw0);
+  };
+  F ca, cb;
+  fl_correction<KIND, F>(a, ca, cb);
+  uint32_t par[N];
+  fl_cn_wide_body<KIND, F>(
+      d, lm, ca, cb, par,
+      [&](int j, F (&r)[N]) __attribute__((always_inline)) { fl_load16<kFlNt, F>(a.in, r, a.ldb, st + j, cw0); },
+      [&](int w, const F (&o)[N]) __attribute__((always_inline)) {
+        if (w == fp0) fold_put(w, c0, fd0, o);
+        else if (w == fp1) fold_put(w, c1, fd1, o);
+        else fl_store16<kFlNt, F>(a.out, o, a.ldb, sload(a.tgt, st + w), cw0);
+      });
+  if (do_par) fl_wide_syndrome<F>(par, valid, unsat);
 }
 
 // Variable-node body on channel c and inputs m; put(w, o) receives extrinsic output w.
@@ -555,6 +762,9 @@ __device__ __forceinline__ void fl_vn_item(const FlArgs& a, int node, int st, in
 // phases) unless the check bodies need more than 128 VGPRs (check degree > 8, or fp64 box-plus). Corrected
 // min-sum (kind 2) takes plain min-sum's block sizes here and in the fused kernel: its bodies need no private
 // segment at either. The small-batch kernels run kFlSmallBlock threads, the per-pass decision 256.
+// The wide instantiations (MAXD = kFlWideD) take the MAXD = 16 sizes, which `maxd > 8` already says: they hold the
+// degree-16 bodies, and the wide body (fl_cn_wide_body) keeps no input array — its largest form, the fp32
+// box-plus with 31 x 4 suffixes in registers, fits the 256 VGPRs of a 512-thread block.
 constexpr int fl_block(FlFamily fam, FlPass pass, int kind, bool f64, int maxd) {
   if (fam == kFlSmall) return kFlSmallBlock;
   if (fam == kFlFused) return (maxd > 8 || (kind == 1 && f64)) ? 512 : 1024;
@@ -575,6 +785,11 @@ __device__ __forceinline__ void fl_by_degree(int d, Fn&& f) {
   }
 }
 
+// The check kernels' wide instantiations (MAXD = kFlWideD) run a degree above 16 through the one wide body before this
+// switch, under `if constexpr (MAXD > 16)`, so that the other instantiations hold the statements they always held;
+// degrees up to 16 keep their bodies in every instantiation (fl_narrow(MAXD): the switch's largest degree).
+constexpr int fl_narrow(int maxd) { return maxd > 16 ? 16 : maxd; }
+
 // Items (node, chunk) are dealt to blocks round-robin ({b*wpb + w + nw*i}) and handed to the
 // block's waves by LDS tickets (take_ticket): ticket k -> item b*wpb + k % wpb + nw * (k / wpb).
 __device__ __forceinline__ int fl_next_item(int* ctr, int lane, int wpb, int nw) {
@@ -582,8 +797,10 @@ __device__ __forceinline__ int fl_next_item(int* ctr, int lane, int wpb, int nw)
   return (int)fl_bid() * wpb + (k % wpb) + nw * (k / wpb);
 }
 
-template <int KIND, typename F, int MAXD>
-__global__ __launch_bounds__(fl_block(kFlPerPass, kFlCheck, KIND, sizeof(F) == 8, MAXD)) void fl_cn(FlArgs a) {
+template <int KX, typename F, int MAXD>
+__global__ __launch_bounds__(fl_block(kFlPerPass, kFlCheck, KX & 3, sizeof(F) == 8, MAXD)) void fl_cn(FlArgs a) {
+  constexpr int KIND = KX & 3;
+  static_assert(((KX & kFlWide) != 0) == (MAXD > 16), "kFlWide goes with MAXD = kFlWideD");
   const int lane = fl_tid() & 63;
   if (!fl_gate(a.gate, lane)) return;
   constexpr int CWL = Vec<F>::N;
@@ -602,7 +819,13 @@ __global__ __launch_bounds__(fl_block(kFlPerPass, kFlCheck, KIND, sizeof(F) == 8
     const int d = sload(a.deg, node), st = sload(a.start, node);
     const int cw0 = chunk * CH + lane * CWL;
     const int valid = a.B - cw0;
-    fl_by_degree<MAXD, false>(d, [&](auto D) __attribute__((always_inline)) {
+    if constexpr (MAXD > 16) {
+      if (d > 16) {
+        fl_cn_wide_item<KIND, F>(a, node, st, d, cw0, do_par, valid, unsat);
+        continue;
+      }
+    }
+    fl_by_degree<fl_narrow(MAXD), false>(d, [&](auto D) __attribute__((always_inline)) {
       fl_cn_item<KIND, F, decltype(D)::value>(a, node, st, cw0, do_par, valid, unsat);
     });
   }
@@ -930,6 +1153,22 @@ __device__ __forceinline__ void fl_cn_small_item(const FlArgs& a, int st, int cw
   });
 }
 
+// a check of degree d in 17..kFlWideD (fl_cn_wide_body)
+template <int KIND, typename F>
+__device__ __forceinline__ void fl_cn_small_wide_item(const FlArgs& a, int st, int d, int cw0, bool do_par, bool& unsat) {
+  constexpr int N = Vec<F>::N;
+  F ca, cb;
+  fl_correction<KIND, F>(a, ca, cb);
+  uint32_t par[N];
+  fl_cn_wide_body<KIND, F>(
+      d, (F)a.llr_max, ca, cb, par,
+      [&](int j, F (&r)[N]) __attribute__((always_inline)) { fl_load16<false, F>(a.in, r, a.ldb, st + j, cw0); },
+      [&](int w, const F (&o)[N]) __attribute__((always_inline)) {
+        fl_store16<kFlNt, F>(a.out, o, a.ldb, a.tgt[st + w], cw0);
+      });
+  if (do_par) fl_wide_syndrome<F>(par, a.B - cw0, unsat);
+}
+
 template <typename F, int D>
 __device__ __forceinline__ void fl_vn_small_item(const FlArgs& a, int node, int st, int cw0) {
   const F lm = (F)a.llr_max;
@@ -946,15 +1185,23 @@ __device__ __forceinline__ void fl_vn_small_item(const FlArgs& a, int node, int 
   });
 }
 
-template <int KIND, typename F, int MAXD>
+template <int KX, typename F, int MAXD>
 __global__ __launch_bounds__(kFlSmallBlock) void fl_cn_small(FlArgs a) {
+  constexpr int KIND = KX & 3;
+  static_assert(((KX & kFlWide) != 0) == (MAXD > 16), "kFlWide goes with MAXD = kFlWideD");
   const int lane = fl_tid() & 63;
   if (!fl_gate(a.gate, lane)) return;
   const bool do_par = a.unsat != nullptr;
   bool unsat = false;
   fl_small_items<false>(a, lane, [&](int, int st, int c, int d) __attribute__((always_inline)) {
     const int cw0 = c * Vec<F>::N;
-    fl_by_degree<MAXD, false>(d, [&](auto D) __attribute__((always_inline)) {
+    if constexpr (MAXD > 16) {
+      if (d > 16) {
+        fl_cn_small_wide_item<KIND, F>(a, st, d, cw0, do_par, unsat);
+        return;
+      }
+    }
+    fl_by_degree<fl_narrow(MAXD), false>(d, [&](auto D) __attribute__((always_inline)) {
       fl_cn_small_item<KIND, F, decltype(D)::value>(a, st, cw0, do_par, unsat);
     });
   });
@@ -1044,6 +1291,21 @@ __device__ __forceinline__ void fused_cn_item(typename Vec<F>::T* msg, int first
   });
 }
 
+// a check of degree d in 17..kFlWideD (fl_cn_wide_body), in place: the body loads input w before it puts output w,
+// and the inputs it loads again lie above the outputs already stored
+template <int KIND, typename F, class U>
+__device__ __forceinline__ void fused_cn_wide_item(typename Vec<F>::T* msg, int first, int cnt, int d, int lane, F lm,
+                                                   F ca, F cb, bool do_par, int valid, U& unsat) {
+  constexpr int N = Vec<F>::N;
+  typename Vec<F>::T* p = msg + (first + lane);
+  uint32_t par[N];
+  fl_cn_wide_body<KIND, F>(
+      d, lm, ca, cb, par,
+      [&](int j, F (&r)[N]) __attribute__((always_inline)) { fl_load16<false, F>(p + j * cnt, r); },
+      [&](int w, const F (&o)[N]) __attribute__((always_inline)) { fl_store16<false, F>(p + w * cnt, o); });
+  if (do_par) fl_wide_syndrome<F>(par, valid, unsat);
+}
+
 // Variable-edge slot indices: staged into LDS as 16-bit values beside the messages (the fused path
 // requires the room for them, capi_float.hip fused_setup), row k of a task at sfirst + 64k: the D loads share
 // one address and take their row offsets as immediates.
@@ -1117,6 +1379,7 @@ template <int KX, typename F, int CMAX, int VMAX>
 __global__ __launch_bounds__(fl_block(kFlFused, kFlCheck, KX & 3, sizeof(F) == 8, CMAX)) void fl_fused(FlFusedArgs a) {
   constexpr int KIND = KX & 3;
   constexpr bool EACH = (KX & kFlEach) != 0;
+  static_assert(((KX & kFlWide) != 0) == (CMAX > 16), "kFlWide goes with CMAX = kFlWideD");
   using V = Vec<F>;
   using VT = typename V::T;
   constexpr int N = V::N;
@@ -1170,7 +1433,13 @@ __global__ __launch_bounds__(fl_block(kFlFused, kFlCheck, KX & 3, sizeof(F) == 8
         fused_cn_item<KIND, F, decltype(D)::value, 64>(msg, first, cnt, lane, lm, ca, cb, do_par, valid, unsat);
       });
     } else if (lane < cnt) {
-      fl_by_degree<CMAX, false>(d, [&](auto D) __attribute__((always_inline)) {
+      if constexpr (CMAX > 16) {
+        if (d > 16) {
+          fused_cn_wide_item<KIND, F>(msg, first, cnt, d, lane, lm, ca, cb, do_par, valid, unsat);
+          return;
+        }
+      }
+      fl_by_degree<fl_narrow(CMAX), false>(d, [&](auto D) __attribute__((always_inline)) {
         fused_cn_item<KIND, F, decltype(D)::value>(msg, first, cnt, lane, lm, ca, cb, do_par, valid, unsat);
       });
     }
@@ -1367,14 +1636,22 @@ hipError_t launch_fl_send(const FlArgs& a, int prec, hipStream_t s) {
 
 // The one table of the node and decision kernels: entry point, threads per block (fl_block) and name of the
 // kernel of (family, pass, check-body kind, precision, largest check / variable degree). Degrees <= 8 take the
-// MAXD = 8 instantiations; the fused kernel is one kernel for every pass.
+// MAXD = 8 instantiations, a largest check degree above 16 the check and fused kernels' MAXD = kFlWideD ones (wide
+// handles); the fused kernel is one kernel for every pass.
 struct FlKernel {
   const void* fn;
   int block;
   const char* name;
 };
 template <int KIND, typename F>
-static const void* fl_entry(FlFamily fam, FlPass pass, bool c8, bool v8, bool each) {
+static const void* fl_entry(FlFamily fam, FlPass pass, bool c8, bool v8, bool each, bool wide) {
+  if (wide) {   // a check of degree 17..kFlWideD: the check kernels' wide column (the others have no check body)
+    constexpr int KW = KIND | kFlWide;
+    if (fam == kFlFused)
+      return each ? (const void*)fl_fused<KW | kFlEach, F, kFlWideD, 16> : (const void*)fl_fused<KW, F, kFlWideD, 16>;
+    if (pass == kFlCheck)
+      return fam == kFlSmall ? (const void*)fl_cn_small<KW, F, kFlWideD> : (const void*)fl_cn<KW, F, kFlWideD>;
+  }
   if (fam == kFlFused && each)
     return !c8 ? (const void*)fl_fused<KIND | kFlEach, F, 16, 16>
                : v8 ? (const void*)fl_fused<KIND | kFlEach, F, 8, 8> : (const void*)fl_fused<KIND | kFlEach, F, 8, 16>;
@@ -1393,12 +1670,12 @@ static const void* fl_entry(FlFamily fam, FlPass pass, bool c8, bool v8, bool ea
 static FlKernel fl_kernel(FlFamily fam, FlPass pass, int kind, int prec, int cmax, int vmax, bool each = false) {
   static const char* const names[3][3] = {
       {"fl_cn", "fl_vn", "fl_dec"}, {"fl_cn_small", "fl_vn_small", "fl_dec_small"}, {"fl_fused", "fl_fused", "fl_fused"}};
-  const bool f64 = prec != kF32, c8 = cmax <= 8, v8 = vmax <= 8;
+  const bool f64 = prec != kF32, c8 = cmax <= 8, v8 = vmax <= 8, wd = cmax > 16;
   const void* fn =
-      kind == 0 ? (f64 ? fl_entry<0, double>(fam, pass, c8, v8, each) : fl_entry<0, float>(fam, pass, c8, v8, each))
+      kind == 0 ? (f64 ? fl_entry<0, double>(fam, pass, c8, v8, each, wd) : fl_entry<0, float>(fam, pass, c8, v8, each, wd))
       : kind == kFlCorrected
-          ? (f64 ? fl_entry<2, double>(fam, pass, c8, v8, each) : fl_entry<2, float>(fam, pass, c8, v8, each))
-          : (f64 ? fl_entry<1, double>(fam, pass, c8, v8, each) : fl_entry<1, float>(fam, pass, c8, v8, each));
+          ? (f64 ? fl_entry<2, double>(fam, pass, c8, v8, each, wd) : fl_entry<2, float>(fam, pass, c8, v8, each, wd))
+          : (f64 ? fl_entry<1, double>(fam, pass, c8, v8, each, wd) : fl_entry<1, float>(fam, pass, c8, v8, each, wd));
   const int maxd = (fam == kFlFused || pass == kFlCheck) ? cmax : vmax;
   return {fn, fl_block(fam, pass, kind, f64, maxd), each ? "fl_fused (per-codeword stop)" : names[fam][pass]};
 }

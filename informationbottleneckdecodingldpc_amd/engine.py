@@ -208,7 +208,10 @@ class FloatDecoder:
     ``alpha`` / ``beta`` (min-sum only): normalised / offset min-sum, every check magnitude becomes
     ``max(alpha * m - beta, 0)`` as two rounded operations (include/ibldpc.h "Corrected min-sum"); 0 < alpha <= 1,
     beta >= 0. The default (1, 0) is plain min-sum; ``correction`` returns the pair. ``kind=1`` with any other
-    value raises ``ValueError``."""
+    value raises ``ValueError``.
+
+    Check degrees up to 32, variable degrees up to 16 (:class:`_lib.IBLError`, ``IBL_EUNSUPPORTED``, otherwise); a
+    code with a check of degree above 16 makes a *wide* decoder (:attr:`wide`), every path and stop included."""
 
     _PATHS = {"auto": _lib.IBL_PATH_AUTO, "passes": _lib.IBL_PATH_PASSES, "fused": _lib.IBL_PATH_FUSED}
 
@@ -276,6 +279,15 @@ class FloatDecoder:
         f = ctypes.c_int32()
         _lib.check(_lib.load().ibl_float_folded(self._h, ctypes.byref(f)), "ibl_float_folded")
         return int(f.value)
+
+    @property
+    def wide(self) -> bool:
+        """Whether the code has a check of degree above 16 (up to 32: DVB-S2 rates 4/5 to 9/10, 5G NR base graph 1),
+        so that the check passes and the fused kernel run their wide forms (``ibl_float_is_wide``). Variable
+        degrees stay at most 16."""
+        w = ctypes.c_int32()
+        _lib.check(_lib.load().ibl_float_is_wide(self._h, ctypes.byref(w)), "ibl_float_is_wide")
+        return bool(w.value)
 
     def input_violations(self, raise_on_error: bool = True) -> int:
         """Channel LLRs of this decoder's decodes since the last call (on any stream) that broke the

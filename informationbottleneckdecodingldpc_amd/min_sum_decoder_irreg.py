@@ -70,6 +70,12 @@ class Min_Sum_Decoder_class_irregular(CodeMixin):
         """``(alpha, beta)`` of the min-sum correction; (1.0, 0.0) is plain min-sum."""
         return self.alpha, self.beta
 
+    @property
+    def wide(self) -> bool:
+        """Whether the code has a check of degree above 16 (``FloatDecoder.wide``): a property of the code, so it
+        needs no device."""
+        return int(self.degree_checknode_nr.max()) > 16
+
     def _decode(self, received_blocks, buffer_in, return_buffer, early_stop=True):
         if self._dec is None:
             self.init_OpenCL_decoding(self.msg_at_time)
