@@ -129,6 +129,19 @@ int ibl_ib_small_batch(const ibl_ib* h, int32_t* max_b);
 int ibl_ib_folded(const ibl_ib* h, int32_t* n_folded);
 int ibl_ib_set_fold(ibl_ib* h, int32_t on);
 /*
+ * Composite final step of the per-pass fast path's check chains (no reference counterpart; outputs and stop
+ * iterations are identical with and without it): for one check degree D* >= 5 the last two table steps of outputs
+ * 0 .. D*-3, "-> L(., x_{D*-2}) -> F(., x_{D*-1})", are composed on the host at create into one table
+ * C(t, m)[y] = F(L(t, m), y) of 16 nibbles per entry, and the check pass takes them as one 4-byte LDS read and a
+ * nibble select instead of two one-byte reads.  D* is the degree >= 5 with the most checks (ties: the larger);
+ * the composite needs the degree <= 8 per-pass kernels and 64 KiB of LDS behind the check pass's tables, which must
+ * fit one 64-KiB super-region (up to 8 tables: DVB-S2 with matching has 7).  *degree = D*, or 0: no composite
+ * (none planned, or switched off).  ibl_ib_set_composite switches it off / on (default: on); the small-batch
+ * kernels, the generic and the fused path never use it.
+ */
+int ibl_ib_composite(const ibl_ib* h, int32_t* degree);
+int ibl_ib_set_composite(ibl_ib* h, int32_t on);
+/*
  * Codewords per workgroup the fused kernel runs a batch of B with (no reference counterpart; results are
  * identical either way): 8, or 4 (half groups) when 2 * ceil(B / 8) workgroups fit the grid or the
  * environment IBL_FUSED_NCW=4 forces them and the half-group kernel fits the device; 0 when decodes do

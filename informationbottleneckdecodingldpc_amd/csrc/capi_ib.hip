@@ -35,6 +35,12 @@ struct ibl_ib {
   std::vector<int32_t> fold_rec, fold_cn_info, fold_vn_info;
   DevBuf<uint8_t> cin2;
   DevBuf<int32_t> fold, cn_info_f, vn_info_r;
+  // composite final step of the check chains (plan.h ib_composite_degree / ib_composite_image): the check degree
+  // that has one (0: none planned), its per-pass images (imax x 512 dwords, beside cn_img) and the switch of
+  // ibl_ib_set_composite; a launch with the composite takes kIbCompBytes more LDS than kcn.lds
+  int32_t comp_deg = 0;
+  bool comp_on = true;
+  DevBuf<uint32_t> cn_comp;
   // fused on-chip path (IbFusedArgs, short codes): task tables, LDS bytes per workgroup, grid
   int32_t path = IBL_PATH_AUTO;
   bool fused_ok = false, f_half_ok = false;   // f_half_ok: the 4-codeword-group kernel is usable too
@@ -69,7 +75,7 @@ struct IbSlots {   // one pass's LDS table slots (ib_plan_slots)
   int cn_nt = 0, vn_nt = 0;               // all tables of a pass: raw, matching-composed finals, the fold's
 };
 struct IbImages {
-  std::vector<uint32_t> cn_img, vn_img, dec_img;
+  std::vector<uint32_t> cn_img, vn_img, dec_img, cn_comp;
 };
 
 Table make_table(int T, const std::function<int(int, int)>& f) {
@@ -104,8 +110,9 @@ std::vector<int> present(const std::vector<int32_t>& deg) {
 // LDS bytes of a fast CN / VN launch: table quads, the 2 work counters
 size_t fast_lds(int nt) { return lds_of_quads(regions_of(nt)) + 64; }
 
-int pick_cfg(int which, int maxd, int nt, int num_cus, KCfg* k) {
-  k->lds = fast_lds(nt);
+// extra: LDS bytes of the launch beyond the tables' (the check pass's composite super-region)
+int pick_cfg(int which, int maxd, int nt, int num_cus, KCfg* k, size_t extra = 0) {
+  k->lds = fast_lds(nt) + extra;
   int best_waves = 0;
   // largest block first at equal occupancy: a CU's waves then share one work counter
   for (int block : {1024, 768, 640, 512, 384, 256}) {
@@ -195,6 +202,7 @@ IbSlots ib_plan_slots(ibl_ib* h, int32_t flags) {
       h->fold_rec.swap(rec);
     }
   }
+  if (h->fast) h->comp_deg = ib_composite_degree(g->h_cn_deg, CM, sl.cn_nt);
   return sl;
 }
 
@@ -204,12 +212,7 @@ IbImages ib_build_images(ibl_ib* h, const IbLuts& lu, const IbSlots& sl) {
   IbImages im;
   // ---------------- CN images: pass p = 0 (iteration 0 ops) .. imax-1
   const int64_t T2 = (int64_t)T * T;
-  auto cn_raw = [&](int p, int l, int t, int m) -> int {
-    int64_t idx;
-    if (p == 0) idx = (l == 0) ? (int64_t)t * Tc + m : (int64_t)Tc * Tc + (int64_t)(l - 1) * Tc * T + (int64_t)t * T + m;
-    else idx = (int64_t)Tc * Tc + (int64_t)(CM - 3) * Tc * T + (int64_t)(p - 1) * (CM - 2) * T2 + l * T2 + (int64_t)t * T + m;
-    return lu.cn[idx];
-  };
+  auto cn_raw = [&](int p, int l, int t, int m) -> int { return lu.cn[ib_cn_raw_index(Tc, T, CM, p, l, t, m)]; };
   auto vn_raw = [&](int k, int l, int t, int m) -> int {
     const int64_t off = (int64_t)k * ((int64_t)Tc * T + (int64_t)(VM - 1) * T2);
     const int64_t idx = off + (l == 0 ? (int64_t)t * T + m : (int64_t)Tc * T + (int64_t)(l - 1) * T2 + (int64_t)t * T + m);
@@ -235,6 +238,10 @@ IbImages ib_build_images(ibl_ib* h, const IbLuts& lu, const IbSlots& sl) {
       }));
     }
     append_pass(im.cn_img, tbs, regions_of(sl.cn_nt));
+    if (h->comp_deg) {   // chain table D* - 4 into D*'s final table (slots D* - 4 and cn_fslot[D*] of this image)
+      im.cn_comp.resize((size_t)(p + 1) * 512);
+      ib_composite_pass(lu.cn, lu.mc, h->match != 0, T, CM, p, h->comp_deg, &im.cn_comp[(size_t)p * 512]);
+    }
   }
   h->cn_nt = regions_of(sl.cn_nt);
   // ---------------- VN images: pass k = 0 .. imax-2 (extrinsic), decision images k = 0 .. imax-1
@@ -337,6 +344,14 @@ int ib_configure_fast(ibl_ib* h, const IbImages& im) {
       (rc = pick_cfg(1, VM, 4 * h->vn_nt, g->num_cus, &h->kvn)) ||
       (rc = pick_cfg(2, VM, 4 * h->dec_nt, g->num_cus, &h->kdec)))
     return rc;
+  if (h->comp_deg) {   // kept only if the launch with the composite's LDS has the check pass's geometry
+    KCfg kc;
+    if (pick_cfg(0, CM, 4 * h->cn_nt, g->num_cus, &kc, kIbCompBytes) != IBL_OK || kc.block != h->kcn.block ||
+        kc.grid != h->kcn.grid)
+      h->comp_deg = 0;
+    else if ((rc = h->cn_comp.upload(im.cn_comp)))
+      return rc;
+  }
   size_t priv = 0;
   const char* kname = "";
   HIPCHK(ib_fast_private_bytes(CM, VM, &priv, &kname));
@@ -596,7 +611,12 @@ int ib_decode_fast(ibl_ib* h, const void* d_ch, int32_t ch_dtype, int32_t B, voi
   // pass 0: send + checknode_update_iter0, inputs gathered from the staged channel rows
   cn.in = nullptr; cn.gather = g->csr_cols; cn.img = h->cn_img; cn.gate = nullptr; cn.unsat = nullptr;
   cn_fold(0);
-  auto launch_cn = [&]() { return launch_ib_cn_fast(cn, h->CM, h->kcn.grid, h->kcn.block, h->kcn.lds, s); };
+  // composite final step: check pass j runs it from its own image
+  const int comp = h->comp_on ? h->comp_deg : 0;
+  const uint32_t* cimg = comp ? h->cn_comp.get() : nullptr;
+  auto launch_cn = [&]() {
+    return launch_ib_cn_fast(cn, h->CM, h->kcn.grid, h->kcn.block, h->kcn.lds + (comp ? kIbCompBytes : 0), s, cimg, comp);
+  };
   HIPCHK(h->timer.timed(0, s, launch_cn));
   cn.gather = nullptr;
   uint64_t* trace = nullptr;
@@ -621,6 +641,7 @@ int ib_decode_fast(ibl_ib* h, const void* d_ch, int32_t ch_dtype, int32_t B, voi
     vn.out = cb[j & 1];
     HIPCHK(h->timer.timed(1, s, [&] { return launch_ib_vn_fast(vn, h->VM, h->kvn.grid, h->kvn.block, h->kvn.lds, s); }));
     cn.img = h->cn_img + (size_t)j * h->cn_nt * 256;
+    if (comp) cimg = h->cn_comp + (size_t)j * 512;
     cn.gate = gate;
     cn.unsat = flag_row(h->flags, early, j);
     cn.trace = (trace && j == I / 2) ? trace + 3 * nwv : nullptr;
@@ -760,6 +781,18 @@ int ibl_ib_folded(const ibl_ib* h, int32_t* n_folded) {
 int ibl_ib_set_fold(ibl_ib* h, int32_t on) {
   if (!h) return fail(IBL_EINVAL, "decoder is NULL");
   h->fold_on = on != 0;
+  return IBL_OK;
+}
+
+int ibl_ib_composite(const ibl_ib* h, int32_t* degree) {
+  if (!h || !degree) return fail(IBL_EINVAL, "NULL argument");
+  *degree = h->comp_on ? h->comp_deg : 0;
+  return IBL_OK;
+}
+
+int ibl_ib_set_composite(ibl_ib* h, int32_t on) {
+  if (!h) return fail(IBL_EINVAL, "decoder is NULL");
+  h->comp_on = on != 0;
   return IBL_OK;
 }
 

@@ -42,6 +42,7 @@ constexpr int kTbl = 8192;        // LDS bytes per IB lookup table (replicated o
 // column term is one v_perm_b32 that drops a codeword's nibble (spread to a byte) into byte 1 of the
 // lane term (colq); bytes 0, 2, 3 keep the lane, half and super-region bits.
 constexpr int kSuper = 65536;                 // bytes per super-region (2 quads)
+static_assert(kIbCompBytes == (size_t)kSuper, "the composite table is one super-region of the quad layout");
 constexpr int kRowSh = 12, kColSh = 8;        // row / column shifts of a lookup address
 __host__ __device__ constexpr uint32_t quad_off(int q) { return (uint32_t)(q >> 1) * kSuper + (uint32_t)(q & 1) * 128u; }
 __host__ __device__ constexpr uint32_t slot_off(int s) { return quad_off(s >> 2) + (uint32_t)(s & 3); }
@@ -52,6 +53,10 @@ constexpr int kTP = 16;           // IB fast path: alphabet padded to 16 (entry 
 // kMaxD, kLightD, kFoldRec: plan.h
 constexpr int kShards = 64;       // early-stop flag words per iteration (one wave load)
 constexpr int kLdsBytes = 160 * 1024;
+static_assert(kIbLdsBytes == (size_t)kLdsBytes && ib_table_lds(1) == lds_of_quads(regions_of(1)) &&
+                  ib_table_lds(7) == lds_of_quads(regions_of(7)) && ib_table_lds(9) == lds_of_quads(regions_of(9)) &&
+                  ib_table_lds(16) == lds_of_quads(regions_of(16)),
+              "plan.h restates the table layout's LDS size for ib_composite_degree");
 
 enum Dtype : int32_t { kU8 = 1, kI32 = 2, kF32 = 3, kF64 = 4, kI8 = 5 };
 
@@ -268,7 +273,10 @@ struct FlDecArgs {
 hipError_t launch_ib_stage(const void* ch, int dtype, int n, int B, uint8_t* ch8, int ldb, hipStream_t s);
 // writes the first ceil(B / 8) words of every row (the rest of a row is padding no output reads)
 hipError_t launch_ib_stage4(const void* ch, int dtype, int n, int B, uint8_t* ch4, int ldb_bytes, hipStream_t s);
-hipError_t launch_ib_cn_fast(const IbFastArgs& a, int maxd, int grid, int block, size_t lds, hipStream_t s);
+// comp != 0: the check degree whose composite final step the launch runs, from the image cimg (plan.h
+// ib_composite_image) staged behind the tables; lds then includes that super-region (kIbCompBytes)
+hipError_t launch_ib_cn_fast(const IbFastArgs& a, int maxd, int grid, int block, size_t lds, hipStream_t s,
+                             const uint32_t* cimg = nullptr, int comp = 0);
 hipError_t launch_ib_vn_fast(const IbFastArgs& a, int maxd, int grid, int block, size_t lds, hipStream_t s);
 int ib_fast_chunk(int maxd);  // codewords per wave item of the CN/VN kernel for this max degree
 hipError_t launch_ib_dec_fast(const IbDecArgs& a, int grid, int block, size_t lds, hipStream_t s);

@@ -54,6 +54,20 @@ __device__ __forceinline__ uint32_t luc(uint32_t t, uint32_t q, uint32_t c) {
   asm("v_lshl_or_b32 %0, %1, 12, %2" : "=v"(x) : "v"(t), "v"(q));
   return *(lds8_t*)(size_t)(x + c);
 }
+// Composite final step of a check chain (plan.h ib_composite_image; the bodies cn_group_fold_cp): the dword of half
+// y >> 3 of C(t, m) - one ds_read_b32 at (t << 12) | q, q = colk's column term - and, one step later with the output
+// packing, nibble y & 7 of it (cnib; sh = shk's shift), instead of two ds_read_u8.
+typedef __attribute__((address_space(3))) const uint32_t lds32_t;
+__device__ __forceinline__ uint32_t lucw(uint32_t t, uint32_t q) {
+  uint32_t x;
+  asm("v_lshl_or_b32 %0, %1, 12, %2" : "=v"(x) : "v"(t), "v"(q));
+  return *(lds32_t*)(size_t)x;
+}
+__device__ __forceinline__ uint32_t cnib(uint32_t w, uint32_t sh) {
+  uint32_t r;
+  asm("v_bfe_u32 %0, %1, %2, 4" : "=v"(r) : "v"(w), "v"(sh));   // the offset is sh[4:0]
+  return r;
+}
 __device__ __forceinline__ uint32_t lds_base(const uint8_t* p) { return (uint32_t)(size_t)(lds8_t*)p; }
 __device__ __forceinline__ void lds_at_zero(const uint8_t* lds) {
   if (lds_base(lds) != 0u) __builtin_trap();  // uniform scalar test; never taken without static LDS
@@ -136,6 +150,22 @@ __device__ __forceinline__ uint32_t rowcol(uint32_t x, uint32_t y) {
 __device__ __forceinline__ uint32_t colb(uint32_t e, int k, uint32_t lane4) {
   return __builtin_amdgcn_perm(e, lane4, 0x03020000u | ((4u + (uint32_t)(k >> 1)) << 8));
 }
+// Column term of the composite step for codeword k: byte 1 = nibble k of input word w (m, as colq), bit 7 of byte 0 =
+// bit 3 of nibble k of input word y (the half), the rest the lane term of the composite's super-region (lane4k: its
+// bytes 0 and 1 hold the lane alone). The two spreads are per word and parity, shared by a group's codewords; the
+// v_perm_b32 takes bytes 2 and 3 as zeros, so the lane term is one v_or_b32 more.
+__device__ __forceinline__ uint32_t colk(uint32_t w, uint32_t y, int k, uint32_t lane4k) {
+  const uint32_t src = (k & 1) ? ((w >> 4) & 0x0F0F0F0Fu) : (w & 0x0F0F0F0Fu);
+  const uint32_t hy = (k & 1) ? (y & 0x80808080u) : ((y << 4) & 0x80808080u);
+  const uint32_t b = (uint32_t)(k >> 1);
+  return __builtin_amdgcn_perm(src, hy, 0x0C0C0000u | ((4u + b) << 8) | b) | lane4k;
+}
+// Shift of nibble y & 7 in a composite dword, 4 (y & 7), for codeword k of input word y: bits 4:0 of the result (all
+// a v_bfe_u32 offset reads; the bits above are other codewords').
+__device__ __forceinline__ uint32_t shk(uint32_t y, int k) {
+  const uint32_t s = (k & 1) ? ((y >> 2) & 0x1C1C1C1Cu) : ((y << 2) & 0x1C1C1C1Cu);
+  return s >> (8 * (k >> 1));
+}
 // Output packing: a word's nibbles join one dependent chain acc = (t << 4K) | acc, one v_lshl_or_b32 per nibble
 // and none for nibble 0, which starts the word (7 instructions per 8 nibbles; written out, or the compiler
 // rebuilds its shift / shift / v_or3 tree, 10 per 8).
@@ -166,6 +196,13 @@ __device__ __forceinline__ void step_fence() { __builtin_amdgcn_sched_barrier(0)
 #define IBL_LU1_(s, n, e, base, c) n##_##s = lu(colb(IBL_EP(e, s), K0 + ST * s, base), c)
 #define IBL_LINK_(s, n, on, p, q) n##_##s = (on) ? luc(p##_##s, q##_##s, 0u) : p##_##s
 #define IBL_PK_(s, o, v) o = pk<K0 + ST * s>(o, v##_##s)
+#define IBL_QK_(s, q, w, y, base) q##_##s = colk(w, y, K0 + ST * s, base)
+// LS (late shift): the group keeps one shift word per parity and moves a codeword's byte down when its nibble is
+// packed - 3 VALU more per output word of a group, 3 registers fewer (the gathering pass 0, whose folding kernel
+// stands at the cap)
+#define IBL_SH_(s, h, y) h##_##s = shk(y, LS ? ((K0 + ST * s) & 1) : K0 + ST * s)
+#define IBL_LUK_(s, n, p, q) n##_##s = lucw(p##_##s, q##_##s)
+#define IBL_PKK_(s, o, v, h) o = pk<K0 + ST * s>(o, cnib(v##_##s, LS ? h##_##s >> (8 * ((K0 + ST * s) >> 1)) : h##_##s))
 #define IBL_Q2(...) const uint32_t IBL_X2(IBL_Q_, __VA_ARGS__)
 #define IBL_Q4(...) const uint32_t IBL_X4(IBL_Q_, __VA_ARGS__)
 #define IBL_QC2(...) const uint32_t IBL_X2(IBL_QC_, __VA_ARGS__)
@@ -178,6 +215,14 @@ __device__ __forceinline__ void step_fence() { __builtin_amdgcn_sched_barrier(0)
 #define IBL_LINK4(...) const uint32_t IBL_X4(IBL_LINK_, __VA_ARGS__)
 #define IBL_PK2(...) IBL_X2(IBL_PK_, __VA_ARGS__)
 #define IBL_PK4(...) IBL_X4(IBL_PK_, __VA_ARGS__)
+#define IBL_QK2(...) const uint32_t IBL_X2(IBL_QK_, __VA_ARGS__)
+#define IBL_QK4(...) const uint32_t IBL_X4(IBL_QK_, __VA_ARGS__)
+#define IBL_SH2(...) const uint32_t IBL_X2(IBL_SH_, __VA_ARGS__)
+#define IBL_SH4(...) const uint32_t IBL_X4(IBL_SH_, __VA_ARGS__)
+#define IBL_LUK2(...) const uint32_t IBL_X2(IBL_LUK_, __VA_ARGS__)
+#define IBL_LUK4(...) const uint32_t IBL_X4(IBL_LUK_, __VA_ARGS__)
+#define IBL_PKK2(...) IBL_X2(IBL_PKK_, __VA_ARGS__)
+#define IBL_PKK4(...) IBL_X4(IBL_PKK_, __VA_ARGS__)
 
 // all-ones nibbles for the codewords of a word that lie inside the batch
 __device__ __forceinline__ uint32_t valid_nib8(int remaining) {
@@ -366,6 +411,8 @@ __device__ __forceinline__ uint32_t pack4n(uint32_t acc, const uint32_t (&t)[4],
 #define IBL_UNROLLED_FILE "ib_unrolled.inc"
 #endif
 template <int D, int MAXD = 8> constexpr bool kWordCT = D <= 8 && MAXD <= 8;
+// degrees with a composite form of the unrolled check body (ib_cn_fast<8, ..> only)
+template <int D, int MAXD> constexpr bool kCompD = D >= 5 && D <= 8 && MAXD <= 8;
 #include IBL_UNROLLED_FILE
 // the plain unrolled check body is the folding one with nothing folded
 template <int D, int K0, int ST>
@@ -414,15 +461,17 @@ __device__ __forceinline__ void cn_word(uint32_t lane4, const uint32_t (&in)[D],
 
 // the folding bodies (degree-2 variable fold): class FC, lane4c = lane term with the fold table's slot,
 // ch0 / ch1 = channel words of the variables at inputs D-2 / D-1
-template <int D, int FC, int GI = 0>
+// CP: the bodies that end outputs 0 .. D-3 in the composite step (cn_group_fold_cp, degrees 5..8; FC = 0: plain)
+template <int D, int FC, int GI = 0, bool CP = false, bool LS = false>
 __device__ __forceinline__ void cn_word_fold(uint32_t lane4, const uint32_t (&in)[D], uint32_t fbase,
                                              uint32_t lane4c, uint32_t ch0, uint32_t ch1, uint32_t (&outw)[D]) {
   constexpr int S = cn_sched_s(D);
   static_assert(S == 2 || S == 4, "parity groups of 2 or 4 codewords");
-  cn_group_fold_ct<D, FC, word_k0<S, 8>(GI), kWordST<8>>(lane4, in, fbase, lane4c, ch0, ch1, outw);
+  if constexpr (CP) cn_group_fold_cp<D, FC, word_k0<S, 8>(GI), kWordST<8>, LS>(lane4, in, fbase, lane4c, ch0, ch1, outw);
+  else cn_group_fold_ct<D, FC, word_k0<S, 8>(GI), kWordST<8>>(lane4, in, fbase, lane4c, ch0, ch1, outw);
   if constexpr ((GI + 1) * S < 8) {
     __builtin_amdgcn_sched_barrier(0);
-    cn_word_fold<D, FC, GI + 1>(lane4, in, fbase, lane4c, ch0, ch1, outw);
+    cn_word_fold<D, FC, GI + 1, CP, LS>(lane4, in, fbase, lane4c, ch0, ch1, outw);
   }
 }
 // the fold of a finished output word (the keeping passes, which need the unfolded word too): nibble out,
@@ -446,9 +495,14 @@ __device__ __forceinline__ uint32_t fold_word(uint32_t w, uint32_t ch, uint32_t 
 // and the decision reads every row): the body is the plain one and the fold runs over the finished words
 // (fold_word; both values in registers through the chains would spill). The channel words are loaded here, for the current item (pass 0 gathers
 // them as inputs anyway): they are first used after the output chains, so they need no one-item-ahead buffer.
-template <int D, bool GATHER, class Buf, int FC = 0, bool KEEP = false>
+// CP: the item's degree is the one whose composite table this launch staged (ib_phase tests the kernel's argument, a
+// scalar compare per item): its words run the composite bodies. The choice is made per item, not per word: with the
+// two forms of a word side by side the compiler hoists their common start above the branch and merges their ends,
+// and the kernels spill (32 .. 192 B).
+template <int D, bool GATHER, class Buf, int FC = 0, bool KEEP = false, bool CP = false>
 __device__ __forceinline__ void cn_compute(const IbFastArgs& a, uint32_t lane4, const Buf& b,
                                            int fslot, bool do_par, bool& unsat, uint8_t* fout = nullptr) {
+  static_assert(!CP || kCompD<D, Buf::kMax>, "composite bodies: degrees 5..8 of the degree <= 8 kernels");
   constexpr int W = Buf::W;
   uint32_t outw[D][W], trow[D];
   uint32_t chf[2][W] = {};
@@ -508,9 +562,10 @@ __device__ __forceinline__ void cn_compute(const IbFastArgs& a, uint32_t lane4, 
       }
     } else if constexpr (FC != 0 && !KEEP) {
       const uint32_t c0 = GATHER ? in[D - 2] : chf[0][i], c1 = GATHER ? in[D - 1] : chf[1][i];
-      cn_word_fold<D, FC>(lane4, in, fbase, lane4 + slot_off(a.fold_slot), c0, c1, o);
+      cn_word_fold<D, FC, 0, CP, GATHER>(lane4, in, fbase, lane4 + slot_off(a.fold_slot), c0, c1, o);
     } else {
-      cn_word<D, 8, kWordCT<D, Buf::kMax>>(lane4, in, fbase, o);
+      if constexpr (CP) cn_word_fold<D, 0, 0, true, GATHER>(lane4, in, fbase, 0u, 0u, 0u, o);
+      else cn_word<D, 8, kWordCT<D, Buf::kMax>>(lane4, in, fbase, o);
     }
 #pragma unroll
     for (int w = 0; w < D; ++w) outw[w][i] = o[w];
@@ -548,7 +603,7 @@ __device__ __forceinline__ void cn_compute(const IbFastArgs& a, uint32_t lane4, 
 }
 
 // folding check pass: the item's class is wave-uniform (one check per item)
-template <int D, bool GATHER, bool KEEP, class Buf>
+template <int D, bool GATHER, bool KEEP, bool CP, class Buf>
 __device__ __forceinline__ void cn_compute_fold(const IbFastArgs& a, uint32_t lane4, const Buf& b,
                                                 int fslot, bool do_par, bool& unsat) {
   if constexpr (D >= 3 && D <= 8) {
@@ -557,13 +612,19 @@ __device__ __forceinline__ void cn_compute_fold(const IbFastArgs& a, uint32_t la
     uint8_t* fout = a.fout;
     asm volatile("" : "+s"(fout));
     switch (b.fc) {
-      case 1: cn_compute<D, GATHER, Buf, 1, KEEP>(a, lane4, b, fslot, do_par, unsat, fout); return;
-      case 2: cn_compute<D, GATHER, Buf, 2, KEEP>(a, lane4, b, fslot, do_par, unsat, fout); return;
-      case 3: cn_compute<D, GATHER, Buf, 3, KEEP>(a, lane4, b, fslot, do_par, unsat, fout); return;
+      case 1: cn_compute<D, GATHER, Buf, 1, KEEP, CP>(a, lane4, b, fslot, do_par, unsat, fout); return;
+      case 2: cn_compute<D, GATHER, Buf, 2, KEEP, CP>(a, lane4, b, fslot, do_par, unsat, fout); return;
+      case 3: cn_compute<D, GATHER, Buf, 3, KEEP, CP>(a, lane4, b, fslot, do_par, unsat, fout); return;
       default: break;
     }
   }
-  cn_compute<D, GATHER>(a, lane4, b, fslot, do_par, unsat);
+  cn_compute<D, GATHER, Buf, 0, false, CP>(a, lane4, b, fslot, do_par, unsat);
+}
+// one check item of the per-pass kernel: folding pass or not, composite bodies or not
+template <int D, bool GATHER, int FOLD, bool CP, class Buf>
+__device__ __forceinline__ void cn_item(const IbFastArgs& a, uint32_t lane4, const Buf& b, bool do_par, bool& unsat) {
+  if constexpr (FOLD != 0) cn_compute_fold<D, GATHER, FOLD == 2, CP>(a, lane4, b, a.fslot[D], do_par, unsat);
+  else cn_compute<D, GATHER, Buf, 0, false, CP>(a, lane4, b, a.fslot[D], do_par, unsat);
 }
 
 // ---------------------------------------------------------------- variable node
@@ -679,13 +740,45 @@ __device__ __forceinline__ void dec_item(const IbDecArgs& a, uint32_t lane4, int
 // light-first quarters of the block 0: VN 0.4825 ms / 170.4k cw/s, 1: 0.4709 / 171.5k, 2: 0.4703 / 171.8k,
 // 3: 0.4782 / 171.1k; round 5 (quad layout): 1 quarter best (IBL_MIX16 = 4).
 
-// LDS of the CN / VN kernels: [nt table quads (common.h layout)][2 work counters]
-__device__ __forceinline__ int* lds_counters(const uint8_t* lds, const IbFastArgs& a) {
-  return reinterpret_cast<int*>(const_cast<uint8_t*>(lds) + lds_of_quads(a.nt));
+// LDS of the CN / VN kernels: [nt table quads (common.h layout)][the check pass's composite super-region, if
+// staged][2 work counters]
+__device__ __forceinline__ int* lds_counters(const uint8_t* lds, const IbFastArgs& a, bool comp = false) {
+  return reinterpret_cast<int*>(const_cast<uint8_t*>(lds) + lds_of_quads(a.nt) + (comp ? (size_t)kSuper : 0));
 }
 __device__ __forceinline__ void stage_pass(uint8_t* lds, const IbFastArgs& a) {
   if (threadIdx.x < 2) lds_counters(lds, a)[threadIdx.x] = 0;
   stage_tables(lds, a.img, a.nt);
+}
+// The check pass with a composite: its image (cimg: 2 quads' worth of raw dwords, plan.h ib_composite_image) is
+// staged as the two quads of the super-region behind the tables', by stage_tables' rounds over one list of chunks -
+// the tables' first, then the composite's 8 - so all global loads still leave in one dependent round trip (DVB-S2:
+// 8 + 8 chunks, one per wave of a 1024-thread block). The bodies address the composite at kSuper: the host plans it
+// only where the tables take one super-region (ib_composite_degree's LDS rule).
+__device__ __forceinline__ void stage_pass_comp(uint8_t* lds, const IbFastArgs& a, const uint32_t* cimg) {
+  if (threadIdx.x < 2) lds_counters(lds, a, true)[threadIdx.x] = 0;
+  const int nraw = a.nt * 256, nall = nraw + 512, qc = 2 * ((a.nt + 1) >> 1), lane = threadIdx.x & 63;
+  const int wv = threadIdx.x >> 6, nwv = blockDim.x >> 6, nchunk = nall >> 6;
+  for (int c0 = 0; c0 < nchunk; c0 += kStageR * nwv) {
+    uint32_t v[kStageR];
+#pragma unroll
+    for (int k = 0; k < kStageR; ++k) {
+      const int r = (c0 + wv + k * nwv) * 64 + lane;   // a chunk lies in one image: nraw is a multiple of 64
+      v[k] = r < nraw ? a.img[r] : (r < nall ? cimg[r - nraw] : 0u);
+    }
+#pragma unroll
+    for (int k = 0; k < kStageR; ++k) {
+      const int c = c0 + wv + k * nwv;
+      if (c >= nchunk) break;   // wave-uniform
+#pragma unroll
+      for (int p = 0; p < 8; ++p) {
+        const int src = 8 * p + (lane >> 3), r = c * 64 + src;
+        const uint32_t w = __shfl(v[k], src, 64);
+        const int q = r < nraw ? r >> 8 : qc + ((r - nraw) >> 8);
+        *reinterpret_cast<uint4*>(lds + quad_off(q) + (uint32_t)(r & 255) * 256u + 16u * (uint32_t)(lane & 7)) =
+            make_uint4(w, w, w, w);
+      }
+    }
+  }
 }
 
 // Persistent wave loop shared by the CN and VN passes: items (position, chunk) are dealt
@@ -703,7 +796,7 @@ __device__ __forceinline__ void stage_pass(uint8_t* lds, const IbFastArgs& a) {
 template <class Buf, bool VN, bool GATHER, int DLO, int DEPTH = 2, int FOLD = 0>
 __device__ __forceinline__ void ib_phase(const IbFastArgs& a, uint32_t lane4, int lane, int first,
                                          int end, int nw, int wpb, int* ctr, bool do_par, bool& unsat,
-                                         uint64_t* trace_items, const PhaseItems pi) {
+                                         uint64_t* trace_items, const PhaseItems pi, int comp = 0) {
   // always inlined: an out-of-line body would take the item by reference through scratch
   auto compute = [&](const Buf& cur) __attribute__((always_inline)) {
     settle<VN>(cur);
@@ -718,8 +811,14 @@ __device__ __forceinline__ void ib_phase(const IbFastArgs& a, uint32_t lane4, in
     } else {
       switch (cur.d) {
 #define X(D) case D: if constexpr (D > DLO && D <= Buf::kMax) { \
-          if constexpr (FOLD != 0) cn_compute_fold<D, GATHER, FOLD == 2>(a, lane4, cur, a.fslot[D], do_par, unsat); \
-          else cn_compute<D, GATHER>(a, lane4, cur, a.fslot[D], do_par, unsat); } break;
+          if constexpr (kCompD<D, Buf::kMax>) { \
+            if (comp == D) { \
+              asm volatile("; composite item");   /* keeps the two forms' common start in their own arms (it spills hoisted) */ \
+              cn_item<D, GATHER, FOLD, true>(a, lane4, cur, do_par, unsat); \
+              break; \
+            } \
+          } \
+          cn_item<D, GATHER, FOLD, false>(a, lane4, cur, do_par, unsat); } break;
         IBL_DEG_CASES(X)
 #undef X
         default: break;
@@ -795,7 +894,7 @@ __device__ __forceinline__ void ib_phase(const IbFastArgs& a, uint32_t lane4, in
 }
 
 template <int MAXD, bool VN, bool GATHER, int FOLD = 0>
-__device__ __forceinline__ void ib_pass(const IbFastArgs& a, const uint8_t* lds) {
+__device__ __forceinline__ void ib_pass(const IbFastArgs& a, const uint8_t* lds, int comp = 0) {
   const int lane = threadIdx.x & 63;
   const uint32_t lane4 = (uint32_t)(lane & 31) << 2;  // LDS address = byte offset (base checked 0)
   const int wpb = blockDim.x >> 6;
@@ -815,7 +914,7 @@ __device__ __forceinline__ void ib_pass(const IbFastArgs& a, const uint8_t* lds)
     a.trace[3 * gw] = __builtin_readcyclecounter();
     *trace_items = (uint64_t)__smid() << 32;
   }
-  int* ctr = lds_counters(lds, a);  // 2 phase counters
+  int* ctr = lds_counters(lds, a, comp != 0);  // 2 phase counters
   // Variable passes: heavy items (degree > kLightD) are bound by the LDS array, light ones (DVB-S2's
   // degree-2/3 variables, few lookups per byte moved) by HBM. The first IBL_MIX16 sixteenths of the
   // block's waves take the light share first, so both kinds run side by side on every CU; a wave that
@@ -832,10 +931,10 @@ __device__ __forceinline__ void ib_pass(const IbFastArgs& a, const uint8_t* lds)
   for (int r = 0; r < 2; ++r) {
     if ((r == 0) != light_first)
       ib_phase<ItemBuf<MAXD, W>, VN, GATHER, kLightD, 2, FOLD>(a, lane4, lane, 0, heavy_end, nw, wpb, ctr, do_par, unsat,
-                                                      trace_items, PhaseItems{0, 0, a.nchunks});
+                                                      trace_items, PhaseItems{0, 0, a.nchunks}, comp);
     else
       ib_phase<ItemBuf<kLightD, LW>, VN, GATHER, 0, (VN ? IBL_LIGHT_DEPTH : 2), FOLD>(a, lane4, lane, heavy_end, nitems, nw, wpb, ctr + 1, do_par,
-                                                   unsat, trace_items, PhaseItems{heavy_end, a.n_heavy, nch_l});
+                                                   unsat, trace_items, PhaseItems{heavy_end, a.n_heavy, nch_l}, comp);
   }
   if (a.trace && lane == 0) {
     a.trace[3 * gw + 1] = __builtin_readcyclecounter();
@@ -867,14 +966,23 @@ __device__ __forceinline__ void ib_pass(const IbFastArgs& a, const uint8_t* lds)
 // FOLD (MAXD = 8 only): 1 = degree-2 variable fold (cn_compute), 2 = also keeping the folded edges' variable-
 // inbox rows. The folding kernels take the class-sorted work order and the fold records (IbFastArgs::fold).
 template <int MAXD, bool GATHER, int FOLD = 0>
-__global__ __launch_bounds__(MAXD <= 8 ? IBL_LB8C : IBL_LB16, MAXD <= 8 ? IBL_WPE8C : 1) void ib_cn_fast(IbFastArgs a) {
+__global__ __launch_bounds__(MAXD <= 8 ? IBL_LB8C : IBL_LB16, MAXD <= 8 ? IBL_WPE8C : 1) void ib_cn_fast(IbFastArgs a,
+    const uint32_t* cimg, int comp) {
   static_assert(FOLD == 0 || MAXD <= 8, "the max-degree-16 bodies do not fold");
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   if (!gate_open(a.gate, threadIdx.x & 63)) return;  // every wave reads the same words: uniform exit
   lds_at_zero(lds);
-  stage_pass(lds, a);
-  __syncthreads();
-  ib_pass<MAXD, false, GATHER, FOLD>(a, lds);
+  if constexpr (MAXD <= 8) {   // comp: the degree whose composite image cimg is, 0 = none (a run-time argument: one
+                               // kernel serves both, and an item's test of its degree against it is a scalar compare)
+    if (comp != 0) stage_pass_comp(lds, a, cimg);
+    else stage_pass(lds, a);
+    __syncthreads();
+    ib_pass<MAXD, false, GATHER, FOLD>(a, lds, comp);
+  } else {
+    stage_pass(lds, a);
+    __syncthreads();
+    ib_pass<MAXD, false, GATHER, FOLD>(a, lds);
+  }
 }
 
 template <int MAXD>
@@ -1958,20 +2066,26 @@ static bool ib_fold_args_ok(const IbFastArgs& a, int maxd) {
   return maxd <= 8 && a.fold && a.fout && a.fold_slot >= 0 && a.fold_slot < 8 * (int)(kLdsBytes / kSuper) &&
          !(a.gather && a.fold_mode == 2);
 }
-hipError_t launch_ib_cn_fast(const IbFastArgs& a, int maxd, int grid, int block, size_t lds, hipStream_t s) {
+hipError_t launch_ib_cn_fast(const IbFastArgs& a, int maxd, int grid, int block, size_t lds, hipStream_t s,
+                             const uint32_t* cimg, int comp) {
+  // a composite: one of the degrees with a composite body, its image, the tables in one super-region and the LDS
+  // of the launch holding the composite's behind them (the bodies address it at kSuper)
+  if (comp != 0 && !(maxd <= 8 && comp >= 5 && comp <= 8 && cimg && lds_of_quads(a.nt) == (size_t)kSuper &&
+                     lds >= 2 * (size_t)kSuper + 8))
+    return hipErrorInvalidValue;
   if (a.fold_mode != 0) {
     if (!ib_fold_args_ok(a, maxd)) return hipErrorInvalidValue;
-    if (a.gather) hipLaunchKernelGGL((ib_cn_fast<8, true, 1>), dim3(grid), dim3(block), lds, s, a);
-    else if (a.fold_mode == 2) hipLaunchKernelGGL((ib_cn_fast<8, false, 2>), dim3(grid), dim3(block), lds, s, a);
-    else hipLaunchKernelGGL((ib_cn_fast<8, false, 1>), dim3(grid), dim3(block), lds, s, a);
+    if (a.gather) hipLaunchKernelGGL((ib_cn_fast<8, true, 1>), dim3(grid), dim3(block), lds, s, a, cimg, comp);
+    else if (a.fold_mode == 2) hipLaunchKernelGGL((ib_cn_fast<8, false, 2>), dim3(grid), dim3(block), lds, s, a, cimg, comp);
+    else hipLaunchKernelGGL((ib_cn_fast<8, false, 1>), dim3(grid), dim3(block), lds, s, a, cimg, comp);
     return hipGetLastError();
   }
   if (a.gather) {
-    if (maxd <= 8) hipLaunchKernelGGL((ib_cn_fast<8, true>), dim3(grid), dim3(block), lds, s, a);
-    else hipLaunchKernelGGL((ib_cn_fast<16, true>), dim3(grid), dim3(block), lds, s, a);
+    if (maxd <= 8) hipLaunchKernelGGL((ib_cn_fast<8, true>), dim3(grid), dim3(block), lds, s, a, cimg, comp);
+    else hipLaunchKernelGGL((ib_cn_fast<16, true>), dim3(grid), dim3(block), lds, s, a, cimg, comp);
   } else {
-    if (maxd <= 8) hipLaunchKernelGGL((ib_cn_fast<8, false>), dim3(grid), dim3(block), lds, s, a);
-    else hipLaunchKernelGGL((ib_cn_fast<16, false>), dim3(grid), dim3(block), lds, s, a);
+    if (maxd <= 8) hipLaunchKernelGGL((ib_cn_fast<8, false>), dim3(grid), dim3(block), lds, s, a, cimg, comp);
+    else hipLaunchKernelGGL((ib_cn_fast<16, false>), dim3(grid), dim3(block), lds, s, a, cimg, comp);
   }
   return hipGetLastError();
 }

@@ -217,6 +217,65 @@ inline std::vector<int32_t> work_order_keyed(const std::vector<int32_t>& nodes, 
   return info;
 }
 
+// Composite final step of the IB check chains (ib_cn_fast, the bodies cn_group_fold_ct<.., CP = true>; under
+// tests/asan/composite_image_check.cpp). For one check degree D* >= 5 the last two steps of outputs 0 .. D*-3,
+// "... -> L(., x_{D-2}) -> F(., x_{D-1})" with L = chain table D*-4 and F = the degree's final table (matching
+// composed), are one table C(t, m)[y] = F(L(t, m), y): 16 nibbles = two dwords per entry (t, m), nibble y & 7 of
+// dword y >> 3. In the LDS it is one more super-region of the quad layout (common.h): the dword of half h of
+// entry (t, m) replicated over the 32 banks at (t << 12) | (m << 8) | (h << 7) | 4 (lane & 31), so the last two
+// ds_read_u8 of a chain become one ds_read_b32 and a v_bfe_u32. The tables are decoder constants: composed once
+// at create.
+constexpr size_t kIbCompBytes = 65536;   // one super-region: 256 entries x 2 halves x 128 B
+constexpr size_t kIbLdsBytes = 160 * 1024;   // a CU's LDS (common.h kLdsBytes)
+// LDS bytes of a pass's nt tables: quads of 4, super-regions of 2 quads (common.h lds_of_quads(regions_of(nt)))
+constexpr size_t ib_table_lds(int nt) { return (size_t)((((nt + 3) >> 2) + 1) >> 1) * 65536; }
+// D*: the check degree >= 5 with the most checks (ties: the larger), if the per-pass kernels are the degree <= 8
+// ones (cm = the largest check degree) and the composite's super-region fits the LDS behind the check pass's
+// cn_tables tables (raw, matching-composed finals, the fold's) and before the two work counters; else 0.
+inline int32_t ib_composite_degree(const std::vector<int32_t>& cn_deg, int cm, int cn_tables) {
+  if (cm > 8 || ib_table_lds(cn_tables) + kIbCompBytes + 64 > kIbLdsBytes) return 0;
+  int64_t cnt[9] = {0};
+  for (int32_t d : cn_deg)
+    if (d >= 5 && d <= 8) ++cnt[d];
+  int32_t best = 0;
+  for (int32_t d = 5; d <= 8; ++d)
+    if (cnt[d] > 0 && (best == 0 || cnt[d] >= cnt[best])) best = d;
+  return best;
+}
+// img[256 h + 16 t + m] = dword h of C(t, m): two quads' worth of raw dwords, staged like a table image.
+// L and F: 256 entries each, (t, m) at 16 t + m (an alphabet below 16 is padded with zeros).
+inline void ib_composite_image(const uint8_t* L, const uint8_t* F, uint32_t* img) {
+  for (int e = 0; e < 256; ++e)
+    for (int h = 0; h < 2; ++h) {
+      uint32_t w = 0;
+      for (int y = 0; y < 8; ++y) w |= (uint32_t)(F[16 * (L[e] & 15) + 8 * h + y] & 15) << (4 * y);
+      img[256 * h + e] = w;
+    }
+}
+
+// Entry (t, m) of chain table l of check pass p in the reference-layout CN vector (pass 0: the first table is
+// Tc x Tc, the others Tc x T; later passes: CM - 2 tables of T x T each).
+inline int64_t ib_cn_raw_index(int Tc, int T, int CM, int p, int l, int t, int m) {
+  const int64_t T2 = (int64_t)T * T;
+  if (p == 0) return l == 0 ? (int64_t)t * Tc + m : (int64_t)Tc * Tc + (int64_t)(l - 1) * Tc * T + (int64_t)t * T + m;
+  return (int64_t)Tc * Tc + (int64_t)(CM - 3) * Tc * T + (int64_t)(p - 1) * (CM - 2) * T2 + l * T2 + (int64_t)t * T + m;
+}
+// The composite image of check pass p for degree D (5 <= D <= CM) from the reference-layout vectors, the fast
+// path's alphabets (Tc = T <= 16): L = chain table D - 4, F = chain table D - 3 with the matching row of degree D
+// composed into it when matching is on - the tables the pass image holds at slots D - 4 and cn_fslot[D].
+inline void ib_composite_pass(const int32_t* cn, const int32_t* mc, bool match, int T, int CM, int p, int D,
+                              uint32_t* img) {
+  uint8_t L[256] = {0}, F[256] = {0};
+  const int64_t mrow = (int64_t)p * T * CM + (int64_t)(D - 1) * T;
+  for (int t = 0; t < T; ++t)
+    for (int m = 0; m < T; ++m) {
+      const int32_t r = cn[ib_cn_raw_index(T, T, CM, p, D - 3, t, m)];
+      L[16 * t + m] = (uint8_t)cn[ib_cn_raw_index(T, T, CM, p, D - 4, t, m)];
+      F[16 * t + m] = (uint8_t)(match ? mc[mrow + r] : r);
+    }
+  ib_composite_image(L, F, img);
+}
+
 // Task tables of the fused kernels (FlFusedArgs, IbFusedArgs).
 struct FusedTasks {
   std::vector<int32_t> cn_task, vn_task, vn_node, vn_slot;

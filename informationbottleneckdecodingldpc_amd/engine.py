@@ -80,12 +80,13 @@ class IBDecoder:
     ``path`` (fast path only): "auto" (the fused on-chip kernel when the code fits in LDS), "passes"
     (one launch per check / variable pass) or "fused" (raises when the code does not fit); both give
     identical results (``ibl_ib_set_path``). ``fused`` tells which one decodes run. ``fold`` switches the per-pass
-    path's degree-2 variable fold (``ibl_ib_set_fold``; ``folded`` = variables it folds, results identical)."""
+    path's degree-2 variable fold (``ibl_ib_set_fold``; ``folded`` = variables it folds, results identical),
+    ``composite`` the composite final step of its check chains (``ibl_ib_set_composite``; results identical)."""
 
     _PATHS = {"auto": _lib.IBL_PATH_AUTO, "passes": _lib.IBL_PATH_PASSES, "fused": _lib.IBL_PATH_FUSED}
 
     def __init__(self, graph: Graph, tables: IBTables, match: bool, max_batch: int, force_generic: bool = False,
-                 path: str = "auto", fold: bool = True):
+                 path: str = "auto", fold: bool = True, composite: bool = True):
         self.graph = graph
         self.tables = tables
         self.match = bool(match)
@@ -109,6 +110,8 @@ class IBDecoder:
         _lib.check(L.ibl_ib_set_path(h, self._PATHS[path]), "ibl_ib_set_path")
         if not fold:
             self.fold = False
+        if not composite:
+            self.composite = False
 
     @property
     def fused(self) -> bool:
@@ -143,6 +146,18 @@ class IBDecoder:
     def fold(self, on: bool) -> None:
         _lib.check(_lib.load().ibl_ib_set_fold(self._h, int(bool(on))), "ibl_ib_set_fold")
         self._fold = bool(on)
+
+    @property
+    def composite(self) -> int:
+        """Check degree whose chains the per-pass fast path ends in the composite table step (``ibl_ib_composite``);
+        0: none planned for this code, or switched off."""
+        d = ctypes.c_int32()
+        _lib.check(_lib.load().ibl_ib_composite(self._h, ctypes.byref(d)), "ibl_ib_composite")
+        return int(d.value)
+
+    @composite.setter
+    def composite(self, on: bool) -> None:
+        _lib.check(_lib.load().ibl_ib_set_composite(self._h, int(bool(on))), "ibl_ib_set_composite")
 
     def fused_ncw(self, B: int) -> int:
         """Codewords per workgroup the fused kernel decodes a batch of ``B`` with (8, or 4 for half

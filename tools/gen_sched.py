@@ -21,6 +21,12 @@ class FC) as one more link, t' = luc(t, q_ch, 0) with q_ch the v_perm_b32 column
 word (lane term = lane4c, which holds the slot of the transposed degree-2 table) - the price of any other lookup,
 taken while t is still alone in a register.
 
+Composite final step (the unrolled bodies cn_group_fold_cp, check degrees 5..8; DESIGN.md "Composite final step of the
+check chains"). For the one check degree whose composite table C(t, m)[y] = F(L(t, m), y) the launch has staged, the
+chains of outputs 0 .. D-3 take their last two steps, "-> L(., in_{D-2}) -> F(., in_{D-1})", as one: a ds_read_b32 of
+the half y >> 3 of C(t, in_{D-2}) (IBL_LUK: column term qk, shared by those chains) and, with the packing one step
+later, nibble y & 7 of it (IBL_PKK: shift sh). Outputs D-2 and D-1 and the fold links are as before.
+
 Column fetches (one ds_read_b64 of a table's whole column for the inputs that meet the same table in every chain)
 were measured on DVB-S2, B=8192, i_max=50, and lost: 170.9k -> 140.9k cw/s (CN 0.464 -> 0.622 ms, VN 0.478 -> 0.526
 ms). The code last stood in the parent of the commit that removed it (DESIGN.md "Retired experiment arms").
@@ -48,6 +54,17 @@ def cn_chains(D):
     for w in range(1, D - 1):
         s0 = ("nib", 0) if w == 1 else ("val", "P", w - 2)              # P_w = P chain after step w-2
         ch.append(dict(id=f"c{w}", start=s0, steps=[st(j, j - 2) for j in range(w + 1, D)], out=w))
+    return ch
+
+
+def cn_chains_composite(D):
+    """cn_chains with the last two steps of outputs 0 .. D-3 as one composite step ("k": a read of C_D at
+    (t, in_{D-2}), nibble in_{D-1} of it; DESIGN.md "Composite final step")."""
+    ch = cn_chains(D)
+    for c in ch:
+        if c["out"] <= D - 3:
+            assert len(c["steps"]) >= 2 and [st[1] for st in c["steps"][-2:]] == [D - 2, D - 1]
+            c["steps"][-2:] = [("k", D - 2, None, None)]
     return ch
 
 
@@ -201,8 +218,8 @@ def main():
 #     itself the scheduler, at the register cap in a block this long, advances the chains diagonally and drains the
 #     LDS queue 78 times per item instead of 41.)
 # One line per chain step: the IBL_*<S> macros of ib_kernels.hip expand it over the S sub-slots (names n_0 .. n_{S-1}).
-def emit_unrolled(kind, D, S, L, fold=False):
-    chains = cn_chains(D) if kind == "cn" else vn_chains(D)
+def emit_unrolled(kind, D, S, L, fold=False, comp=False):
+    chains = (cn_chains_composite(D) if comp else cn_chains(D)) if kind == "cn" else vn_chains(D)
     by_id = {c["id"]: c for c in chains}
     sched = schedule(chains, L)
     assert S in (2, 4)
@@ -217,10 +234,10 @@ def emit_unrolled(kind, D, S, L, fold=False):
 
     steps = [(c, k, st) for c in chains for k, st in enumerate(c["steps"])]
     fl = sorted({first_level(c, k) for c, k, _ in steps} - {None}, key=str)
-    u8_in = sorted({st[1] for c, k, st in steps if not first_level(c, k)})
-    uses = {j: {st[2] for c, k, st in steps if st[1] == j and not first_level(c, k)} for j in u8_in}
+    u8_in = sorted({st[1] for c, k, st in steps if not first_level(c, k) and st[0] != "k"})
+    uses = {j: {st[2] for c, k, st in steps if st[1] == j and not first_level(c, k) and st[0] != "k"} for j in u8_in}
     q_final = {j for j in u8_in if j == D - 1 or uses[j] == {"fbase"}}
-    lines = ["  const uint32_t lane4f = lane4 + fbase;"]
+    lines = ["  const uint32_t lane4f = lane4 + fbase;"] + (["  const uint32_t lane4k = lane4 + kSuper;"] if comp else [])
     for a, j in fl:
         lines.append(f"  IBL_E(E{a}_{j}, {'chw' if a == 'c' else f'in[{a}]'}, in[{j}]);")
     defined, links, packs = set(), [], []
@@ -229,6 +246,8 @@ def emit_unrolled(kind, D, S, L, fold=False):
         if key in defined:
             return []
         defined.add(key)
+        if key == "k":   # the composite step's column term and nibble shift, shared by the D - 2 chains that end in it
+            return [f"  IBL_QK{S}(qk, in[{D - 2}], in[{D - 1}], lane4k);", f"  IBL_SH{S}(sh, in[{D - 1}]);"]
         if isinstance(key, tuple):
             return [f"  IBL_QC{S}(qc{key[1]}, FC & {1 << key[1]}, ch{key[1]});"]
         return [f"  IBL_Q{S}(q{key}, in[{key}], {'lane4f' if key in q_final else 'lane4'});"]
@@ -242,7 +261,7 @@ def emit_unrolled(kind, D, S, L, fold=False):
             lines.append(f"  IBL_LINK{S}(f_{cid}, FC & {1 << a}, {v}, qc{a});")
         lines.extend(look)
         for out, v in packs:
-            lines.append(f"  IBL_PK{S}(o[{out}], {v});")
+            lines.append(f"  IBL_PKK{S}(o[{out}], {v[:-2]}, sh);" if v.endswith(":k") else f"  IBL_PK{S}(o[{out}], {v});")
         packs = [(by_id[cid]["out"], f"f_{cid}") for a, cid, v in links] + [d for d in done if d[0] is not None]
         links = [(d[1], d[2], d[3]) for d in done if d[0] is None]
         lines.append("  step_fence();")
@@ -254,6 +273,13 @@ def emit_unrolled(kind, D, S, L, fold=False):
             op, j, sl, _ = c["steps"][k]
             f1 = first_level(c, k)
             name = f"v_{cid}_{k}"
+            if op == "k":   # raw dword of the composite; its nibble is taken when the word is packed
+                pre.extend(need("k"))
+                st = c["start"]
+                look.append(f"  IBL_LUK{S}({name}, {f'v_{cid}_{k - 1}' if k else f'v_{st[1]}_{st[2]}'}, qk);")
+                assert k == len(c["steps"]) - 1 and (k or st[0] == "val")
+                done.append((c["out"], name + ":k"))
+                continue
             if f1:
                 final = sl == "fbase" or j == D - 1
                 look.append(f"  IBL_LU1{S}({name}, E{f1[0]}_{f1[1]}, {'lane4f, 0u' if final else 'lane4, ' + sl});")
@@ -283,15 +309,17 @@ def main_unrolled(a):
     # (the plain check bodies are the folding ones at FC = 0: cn_group_ct in ib_kernels.hip)
     # The variable bodies stop at degree 4, the fused kernel's light bodies: the per-pass variable kernel keeps the
     # loop bodies (unrolled it issued 12 % fewer VALU per lookup and was no faster).
-    for kind, lo, hi, fold in (("cn", 3, 8, True), ("vn", 2, 4, False)):
-        fn = f"{kind}_group{'_fold' if fold else ''}_ct"
+    # cn_group_fold_cp: the form of the one check degree whose composite table is staged (degrees 5..8; issue order
+    # as above, the composite step's nibble select runs with the packing, one step after its read)
+    for kind, lo, hi, fold, comp in (("cn", 3, 8, True, False), ("cn", 5, 8, True, True), ("vn", 2, 4, False, False)):
+        fn = f"{kind}_group{'_fold' if fold else ''}_{'cp' if comp else 'ct'}"
         extra = (", uint32_t lane4c, uint32_t ch0, uint32_t ch1" if fold else "") + (", uint32_t chw" if kind == "vn" else "")
-        print(f"template <int D, {'int FC, ' if fold else ''}int K0, int ST> __device__ __forceinline__ void {fn}({cargs}{extra},")
+        print(f"template <int D, {'int FC, ' if fold else ''}int K0, int ST{', bool LS' if comp else ''}> __device__ __forceinline__ void {fn}({cargs}{extra},")
         print("    uint32_t (&o)[D]) {")
         print(f"  static_assert(D >= {lo} && D <= {hi} && K0 >= 0 && (ST == 1 || ST == 2), \"unrolled bodies: degrees {lo}..{hi}\");")
         for D in range(lo, hi + 1):
             print(f"  if constexpr (D == {D}) {{")
-            print("\n".join("  " + l for l in emit_unrolled(kind, D, Sc if kind == "cn" else Sv, Lc if kind == "cn" else Lv, fold)))
+            print("\n".join("  " + l for l in emit_unrolled(kind, D, Sc if kind == "cn" else Sv, Lc if kind == "cn" else Lv, fold, comp)))
             print("  }")
         print("}")
 

@@ -6,7 +6,8 @@
 Compiles csrc/ib_kernels.hip to gfx950 assembly with the build's flags (_build.py FLAGS; --asm reuses or
 writes FILE.s instead of a temporary) and prints, for every kernel whose name, written as in the source, contains KERNEL
 (e.g. "ib_cn_fast<8,false,1>"), its register / private-segment figures and one line per basic block
-with at least --min-reads ds_read_u8: the ds_read_u8 count, the VALU count, VALU per lookup and the VALU
+with at least --min-reads LDS lookups: the ds_read_u8 count (and, where a body ends its chains in the composite
+step, the ds_read_b32 count beside it; a lookup is either), the VALU count, VALU per lookup and the VALU
 opcode histogram, blocks sorted by lookups (--top N: the first N; --reads: only blocks with these lookup counts,
 e.g. the 10 lookups of a degree-3 variable group of 2 codewords). --sum adds up the named blocks of ONE kernel, a
 block executed N times as LABEL*N: the instructions one item executes where its body is a loop nest ("LABEL+" is
@@ -25,6 +26,16 @@ sys.path.insert(0, ROOT)
 from informationbottleneckdecodingldpc_amd import _build  # noqa: E402
 
 BRANCH = ("s_branch", "s_cbranch", "s_endpgm", "s_setpc", "s_swappc")
+WIDE = "ds_read_b32"   # the composite step's read (the node bodies have no other 4-byte LDS read)
+
+
+def reads(ops):
+    """(ds_read_u8, ds_read_b32) of a block"""
+    return sum(op == "ds_read_u8" for op in ops), sum(op == WIDE for op in ops)
+
+
+def rd(n8, n32):
+    return f"ds_read_u8 {n8:4d}" + (f" + b32 {n32:3d}" if n32 else "")
 
 
 def pretty(name):
@@ -130,36 +141,37 @@ def main():
             bl = blocks(lines[lo + 1:hi])
             m = meta(lines, n)
             tot_v = sum(op.startswith("v_") for _, ops in bl for op in ops)
-            tot_r = sum(op == "ds_read_u8" for _, ops in bl for op in ops)
+            tot_r, tot_w = (sum(x) for x in zip(*(reads(ops) for _, ops in bl)))
             print(f"== {d}")
             print(f"   vgpr {m.get('next_free_vgpr')} sgpr {m.get('next_free_sgpr')} private "
-                  f"{m.get('private_segment_fixed_size')} B; static totals: ds_read_u8 {tot_r}, VALU {tot_v}")
+                  f"{m.get('private_segment_fixed_size')} B; static totals: ds_read_u8 {tot_r}, {WIDE} {tot_w}, VALU {tot_v}")
             if a.sum:
-                by, nr, nv = dict(bl), 0, 0
+                by, nr, nw, nv = dict(bl), 0, 0, 0
                 for term in a.sum:
                     lab, _, n = term.partition("*")
-                    nr += int(n or 1) * sum(op == "ds_read_u8" for op in by[lab])
+                    nr += int(n or 1) * reads(by[lab])[0]
+                    nw += int(n or 1) * reads(by[lab])[1]
                     nv += int(n or 1) * sum(op.startswith("v_") for op in by[lab])
-                print(f"   sum of {' '.join(a.sum)}: ds_read_u8 {nr}  VALU {nv}  VALU/lookup {nv / nr:.2f}")
+                print(f"   sum of {' '.join(a.sum)}: {rd(nr, nw)}  VALU {nv}  VALU/lookup {nv / (nr + nw):.2f}")
                 continue
             rows = []
             for label, ops in bl:
-                nr = sum(op == "ds_read_u8" for op in ops)
-                if nr < a.min_reads:
+                nr, nw = reads(ops)
+                if nr + nw < a.min_reads:
                     continue
                 hist = {}
                 for op in ops:
                     if op.startswith("v_"):
                         hist[op] = hist.get(op, 0) + 1
-                rows.append((nr, sum(hist.values()), label, hist))
+                rows.append((nr + nw, sum(hist.values()), label, hist, nr, nw))
             rows.sort(key=lambda r: (-r[0], r[2]))
             if a.reads:
                 rows = [r for r in rows if r[0] in a.reads]
             if a.top:
                 rows = rows[:a.top]
-            for nr, nv, label, hist in rows:
+            for n, nv, label, hist, nr, nw in rows:
                 h = " ".join(f"{k[2:]}:{v}" for k, v in sorted(hist.items(), key=lambda kv: -kv[1]))
-                print(f"   {label:<12} ds_read_u8 {nr:4d}  VALU {nv:4d}  VALU/lookup {nv / max(nr, 1):5.2f}  | {h}")
+                print(f"   {label:<12} {rd(nr, nw)}  VALU {nv:4d}  VALU/lookup {nv / max(n, 1):5.2f}  | {h}")
     if tmp:
         tmp.cleanup()
 
