@@ -142,6 +142,14 @@ int ibl_ib_set_fold(ibl_ib* h, int32_t on);
 int ibl_ib_composite(const ibl_ib* h, int32_t* degree);
 int ibl_ib_set_composite(ibl_ib* h, int32_t on);
 /*
+ * The same step for the per-pass variable chains (outputs 0 .. D*-3 of a degree-D* variable end in raw table D*-3
+ * and the degree's final table): D* is the variable degree in 5..8 with the most nodes among the variables the pass
+ * walks - with the degree-2 fold on, the ones it leaves, whose tables alone are then staged (DVB-S2 with matching:
+ * 8, one super-region; with the fold off 9: no composite).  Same LDS rule, same kernels, identical results.
+ */
+int ibl_ib_vn_composite(const ibl_ib* h, int32_t* degree);
+int ibl_ib_set_vn_composite(ibl_ib* h, int32_t on);
+/*
  * Codewords per workgroup the fused kernel runs a batch of B with (no reference counterpart; results are
  * identical either way): 8, or 4 (half groups) when 2 * ceil(B / 8) workgroups fit the grid or the
  * environment IBL_FUSED_NCW=4 forces them and the half-group kernel fits the device; 0 when decodes do

@@ -28,7 +28,7 @@ EXPORTS = [
     "ibl_graph_create", "ibl_graph_info", "ibl_graph_destroy",
     "ibl_ib_create", "ibl_ib_path", "ibl_ib_set_path", "ibl_ib_path_in_use", "ibl_ib_fused_ncw", "ibl_ib_decode",
     "ibl_ib_set_small_batch", "ibl_ib_small_batch", "ibl_ib_folded", "ibl_ib_set_fold",
-    "ibl_ib_composite", "ibl_ib_set_composite",
+    "ibl_ib_composite", "ibl_ib_set_composite", "ibl_ib_vn_composite", "ibl_ib_set_vn_composite",
     "ibl_ib_destroy",
     "ibl_float_create", "ibl_float_decode", "ibl_float_destroy", "ibl_count_below",
     "ibl_float_set_path", "ibl_float_path_in_use", "ibl_float_fused_geometry", "ibl_float_folded",
@@ -93,6 +93,8 @@ def load():
     L.ibl_ib_set_fold.argtypes = [_vp, _i32]
     L.ibl_ib_composite.argtypes = [_vp, ctypes.POINTER(_i32)]
     L.ibl_ib_set_composite.argtypes = [_vp, _i32]
+    L.ibl_ib_vn_composite.argtypes = [_vp, ctypes.POINTER(_i32)]
+    L.ibl_ib_set_vn_composite.argtypes = [_vp, _i32]
     L.ibl_ib_decode.argtypes = [_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]
     L.ibl_ib_decode_each.argtypes = [_vp, _vp, _i32, _i32, _vp, _i32, _vp, _vp]
     L.ibl_ib_destroy.argtypes = [_vp]

@@ -41,6 +41,17 @@ struct ibl_ib {
   int32_t comp_deg = 0;
   bool comp_on = true;
   DevBuf<uint32_t> cn_comp;
+  // composite final step of the variable chains (plan.h ib_vn_composite_degree / ib_vn_composite_pass), per work
+  // order of the variable pass: [0] every variable (fold off, or nothing folded), [1] the variables the fold leaves
+  // (the rest list). Per view the variable degree that has one (0: none), its per-pass images ((imax - 1) x 512
+  // dwords) and the LDS bytes of a launch with it. The rest view runs from an image of its own, the tables of the
+  // degrees it walks alone (plan.h ib_vn_slots; DVB-S2 with matching: 8 tables, not 9), with its own final slots.
+  int32_t vcomp_deg[2] = {0, 0};
+  bool vcomp_on = true;
+  DevBuf<uint32_t> vn_comp[2], vn_img_r;
+  size_t vcomp_lds[2] = {0, 0};
+  int vn_nt_r = 0;
+  int32_t vn_fslot_r[kMaxD + 1] = {0};
   // fused on-chip path (IbFusedArgs, short codes): task tables, LDS bytes per workgroup, grid
   int32_t path = IBL_PATH_AUTO;
   bool fused_ok = false, f_half_ok = false;   // f_half_ok: the 4-codeword-group kernel is usable too
@@ -73,9 +84,10 @@ struct IbSlots {   // one pass's LDS table slots (ib_plan_slots)
   std::vector<int> cdeg, vdeg;            // the degrees present
   int cn_nraw = 0, vn_nraw = 0;           // raw (reference) tables of a check / variable pass
   int cn_nt = 0, vn_nt = 0;               // all tables of a pass: raw, matching-composed finals, the fold's
+  IbVnSlots vr;                           // the variable pass over the fold's rest list (planned with its composite)
 };
 struct IbImages {
-  std::vector<uint32_t> cn_img, vn_img, dec_img, cn_comp;
+  std::vector<uint32_t> cn_img, vn_img, dec_img, cn_comp, vn_comp[2], vn_img_r;
 };
 
 Table make_table(int T, const std::function<int(int, int)>& f) {
@@ -203,6 +215,16 @@ IbSlots ib_plan_slots(ibl_ib* h, int32_t flags) {
     }
   }
   if (h->fast) h->comp_deg = ib_composite_degree(g->h_cn_deg, CM, sl.cn_nt);
+  if (h->fast) {   // the variable pass's composite, for either list it may walk
+    h->vcomp_deg[0] = ib_vn_composite_degree(g->h_vn_deg, VM, std::max(sl.vn_nt, 1));
+    if (h->n_folded > 0) {
+      std::vector<int32_t> rdeg((size_t)h->n_rest);
+      for (int32_t p = 0; p < h->n_rest; ++p) rdeg[(size_t)p] = h->fold_vn_info[4 * (size_t)p + 2];
+      sl.vr = ib_vn_slots(rdeg, h->match != 0);
+      h->vcomp_deg[1] = ib_vn_composite_degree(rdeg, VM, std::max(sl.vr.nt, 1));
+      std::memcpy(h->vn_fslot_r, sl.vr.fslot, sizeof(h->vn_fslot_r));
+    }
+  }
   return sl;
 }
 
@@ -254,8 +276,24 @@ IbImages ib_build_images(ibl_ib* h, const IbLuts& lu, const IbSlots& sl) {
       tbs.push_back(make_table(T, [&](int t, int m) { return lu.mv[mrow + vn_raw(k, d - 2, t, m)]; }));
     }
     append_pass(im.vn_img, tbs, regions_of(std::max(sl.vn_nt, 1)));
+    for (int v = 0; v < 2; ++v)   // raw table D* - 3 into D*'s final table, per work order
+      if (h->vcomp_deg[v]) {
+        im.vn_comp[v].resize((size_t)(k + 1) * 512);
+        ib_vn_composite_pass(lu.vn, lu.mv, h->match != 0, Tc, T, VM, k, h->vcomp_deg[v], &im.vn_comp[v][(size_t)k * 512]);
+      }
+    if (h->vcomp_deg[1]) {   // the rest list's own image: the tables of the degrees it walks, slots vn_fslot_r
+      std::vector<Table> rt;
+      for (int l = 0; l < sl.vr.nraw; ++l) rt.push_back(make_table(T, [&](int t, int m) { return vn_raw(k, l, t, m); }));
+      for (int d : sl.vr.deg) {
+        if (!h->match || d < 2) continue;
+        const int64_t mrow = (int64_t)k * T * VM + (int64_t)(d - 1) * T;
+        rt.push_back(make_table(T, [&](int t, int m) { return lu.mv[mrow + vn_raw(k, d - 2, t, m)]; }));
+      }
+      append_pass(im.vn_img_r, rt, regions_of(std::max(sl.vr.nt, 1)));
+    }
   }
   h->vn_nt = regions_of(std::max(sl.vn_nt, 1));
+  h->vn_nt_r = regions_of(std::max(sl.vr.nt, 1));
   for (int k = 0; k < imax; ++k) {
     std::vector<Table> tbs;
     for (int l = 0; l < VM; ++l) tbs.push_back(make_table(T, [&](int t, int m) { return vn_raw(k, l, t, m); }));
@@ -351,6 +389,17 @@ int ib_configure_fast(ibl_ib* h, const IbImages& im) {
       h->comp_deg = 0;
     else if ((rc = h->cn_comp.upload(im.cn_comp)))
       return rc;
+  }
+  for (int v = 0; v < 2; ++v) {   // likewise the variable pass's, per work order
+    if (!h->vcomp_deg[v]) continue;
+    KCfg kc;
+    if (pick_cfg(1, VM, 4 * (v ? h->vn_nt_r : h->vn_nt), g->num_cus, &kc, kIbCompBytes) != IBL_OK ||
+        kc.block != h->kvn.block || kc.grid != h->kvn.grid) {
+      h->vcomp_deg[v] = 0;
+      continue;
+    }
+    h->vcomp_lds[v] = kc.lds;
+    if ((rc = h->vn_comp[v].upload(im.vn_comp[v])) || (v == 1 && (rc = h->vn_img_r.upload(im.vn_img_r)))) return rc;
   }
   size_t priv = 0;
   const char* kname = "";
@@ -619,6 +668,16 @@ int ib_decode_fast(ibl_ib* h, const void* d_ch, int32_t ch_dtype, int32_t B, voi
   };
   HIPCHK(h->timer.timed(0, s, launch_cn));
   cn.gather = nullptr;
+  // likewise the variable passes, by the list they walk; over the rest list from that list's own image and slots
+  const int view = fold ? 1 : 0;
+  const int vcomp = h->vcomp_on ? h->vcomp_deg[view] : 0;
+  const bool rest_img = vcomp && view == 1;
+  if (rest_img) {
+    vn.nt = h->vn_nt_r;
+    std::memcpy(vn.fslot, h->vn_fslot_r, sizeof(vn.fslot));
+  }
+  const uint32_t* vimg = rest_img ? h->vn_img_r.get() : h->vn_img.get();
+  const size_t vlds = vcomp ? h->vcomp_lds[view] : h->kvn.lds;
   uint64_t* trace = nullptr;
   size_t nwv = 0;
 #if IBL_DIAG
@@ -635,11 +694,14 @@ int ib_decode_fast(ibl_ib* h, const void* d_ch, int32_t ch_dtype, int32_t B, voi
 #endif
   for (int j = 1; j < I; ++j) {
     const int32_t* gate = flag_row(h->flags, early && j >= 2, j - 1);
-    vn.img = h->vn_img + (size_t)(j - 1) * h->vn_nt * 256;
+    vn.img = vimg + (size_t)(j - 1) * vn.nt * 256;
+    const uint32_t* vcimg = vcomp ? h->vn_comp[view] + (size_t)(j - 1) * 512 : nullptr;
     vn.gate = gate;
     vn.trace = (trace && j == I / 2) ? trace : nullptr;
     vn.out = cb[j & 1];
-    HIPCHK(h->timer.timed(1, s, [&] { return launch_ib_vn_fast(vn, h->VM, h->kvn.grid, h->kvn.block, h->kvn.lds, s); }));
+    HIPCHK(h->timer.timed(1, s, [&] {
+      return launch_ib_vn_fast(vn, h->VM, h->kvn.grid, h->kvn.block, vlds, s, vcimg, vcomp);
+    }));
     cn.img = h->cn_img + (size_t)j * h->cn_nt * 256;
     if (comp) cimg = h->cn_comp + (size_t)j * 512;
     cn.gate = gate;
@@ -793,6 +855,19 @@ int ibl_ib_composite(const ibl_ib* h, int32_t* degree) {
 int ibl_ib_set_composite(ibl_ib* h, int32_t on) {
   if (!h) return fail(IBL_EINVAL, "decoder is NULL");
   h->comp_on = on != 0;
+  return IBL_OK;
+}
+
+int ibl_ib_vn_composite(const ibl_ib* h, int32_t* degree) {
+  if (!h || !degree) return fail(IBL_EINVAL, "NULL argument");
+  const int view = h->fold_on && h->n_folded > 0 && h->imax > 1 ? 1 : 0;   // the list ib_decode_fast walks
+  *degree = h->vcomp_on ? h->vcomp_deg[view] : 0;
+  return IBL_OK;
+}
+
+int ibl_ib_set_vn_composite(ibl_ib* h, int32_t on) {
+  if (!h) return fail(IBL_EINVAL, "decoder is NULL");
+  h->vcomp_on = on != 0;
   return IBL_OK;
 }
 

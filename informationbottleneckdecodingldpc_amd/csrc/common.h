@@ -277,7 +277,9 @@ hipError_t launch_ib_stage4(const void* ch, int dtype, int n, int B, uint8_t* ch
 // ib_composite_image) staged behind the tables; lds then includes that super-region (kIbCompBytes)
 hipError_t launch_ib_cn_fast(const IbFastArgs& a, int maxd, int grid, int block, size_t lds, hipStream_t s,
                              const uint32_t* cimg = nullptr, int comp = 0);
-hipError_t launch_ib_vn_fast(const IbFastArgs& a, int maxd, int grid, int block, size_t lds, hipStream_t s);
+// comp != 0: likewise the variable degree whose composite final step the launch runs (plan.h ib_vn_composite_pass)
+hipError_t launch_ib_vn_fast(const IbFastArgs& a, int maxd, int grid, int block, size_t lds, hipStream_t s,
+                             const uint32_t* cimg = nullptr, int comp = 0);
 int ib_fast_chunk(int maxd);  // codewords per wave item of the CN/VN kernel for this max degree
 hipError_t launch_ib_dec_fast(const IbDecArgs& a, int grid, int block, size_t lds, hipStream_t s);
 // small-batch per-pass kernels (B <= a few words): grid from the item count, block kSmallBlock

@@ -654,9 +654,20 @@ __device__ __forceinline__ void vn_word(uint32_t lane4, const uint32_t (&in)[D],
   }
 }
 
-template <int D, class Buf>
+// the loop body of the degree whose composite table the variable launch staged (vn_group_cp in ib_sched.inc)
+template <int D>
+__device__ __forceinline__ void vn_word_cp(uint32_t lane4, const uint32_t (&in)[D], uint32_t chw,
+                                           uint32_t fbase, uint32_t (&outw)[D]) {
+#pragma unroll 1
+  for (int k0 = 0; k0 < 8; k0 += vn_cp_sched_s()) vn_group_cp<D>(lane4, in, chw, fbase, outw, k0);
+}
+
+// CP: the item's degree is the one whose composite table this launch staged (ib_phase tests the kernel's argument
+// per item, as for the check pass): outputs 0 .. D-3 end in the composite step
+template <int D, class Buf, bool CP = false>
 __device__ __forceinline__ void vn_compute(const IbFastArgs& a, uint32_t lane4, const Buf& b,
                                            int fslot) {
+  static_assert(!CP || kCompD<D, Buf::kMax>, "composite bodies: degrees 5..8 of the degree <= 8 kernel");
   constexpr int W = Buf::W;
   uint32_t outw[D][W], trow[D];
 #pragma unroll
@@ -674,7 +685,8 @@ __device__ __forceinline__ void vn_compute(const IbFastArgs& a, uint32_t lane4, 
         o[j] = 0;
       }
       // (the loop bodies: unrolled, the variable pass issued 12 % fewer VALU per lookup and was no faster)
-      vn_word<D>(lane4, in, b.chw[i], fbase, o);
+      if constexpr (CP) vn_word_cp<D>(lane4, in, b.chw[i], fbase, o);
+      else vn_word<D>(lane4, in, b.chw[i], fbase, o);
 #pragma unroll
       for (int w = 0; w < D; ++w) outw[w][i] = o[w];
     }
@@ -740,7 +752,7 @@ __device__ __forceinline__ void dec_item(const IbDecArgs& a, uint32_t lane4, int
 // light-first quarters of the block 0: VN 0.4825 ms / 170.4k cw/s, 1: 0.4709 / 171.5k, 2: 0.4703 / 171.8k,
 // 3: 0.4782 / 171.1k; round 5 (quad layout): 1 quarter best (IBL_MIX16 = 4).
 
-// LDS of the CN / VN kernels: [nt table quads (common.h layout)][the check pass's composite super-region, if
+// LDS of the CN / VN kernels: [nt table quads (common.h layout)][the pass's composite super-region, if
 // staged][2 work counters]
 __device__ __forceinline__ int* lds_counters(const uint8_t* lds, const IbFastArgs& a, bool comp = false) {
   return reinterpret_cast<int*>(const_cast<uint8_t*>(lds) + lds_of_quads(a.nt) + (comp ? (size_t)kSuper : 0));
@@ -749,7 +761,7 @@ __device__ __forceinline__ void stage_pass(uint8_t* lds, const IbFastArgs& a) {
   if (threadIdx.x < 2) lds_counters(lds, a)[threadIdx.x] = 0;
   stage_tables(lds, a.img, a.nt);
 }
-// The check pass with a composite: its image (cimg: 2 quads' worth of raw dwords, plan.h ib_composite_image) is
+// A check or variable pass with a composite: its image (cimg: 2 quads' worth of raw dwords, plan.h ib_composite_image) is
 // staged as the two quads of the super-region behind the tables', by stage_tables' rounds over one list of chunks -
 // the tables' first, then the composite's 8 - so all global loads still leave in one dependent round trip (DVB-S2:
 // 8 + 8 chunks, one per wave of a 1024-thread block). The bodies address the composite at kSuper: the host plans it
@@ -803,7 +815,14 @@ __device__ __forceinline__ void ib_phase(const IbFastArgs& a, uint32_t lane4, in
     if constexpr (VN) {
       switch (cur.d) {
         case 1: if constexpr (DLO < 1) vn_compute<1>(a, lane4, cur, 0); break;
-#define X(D) case D: if constexpr (D > DLO && D <= Buf::kMax) vn_compute<D>(a, lane4, cur, a.fslot[D]); break;
+#define X(D) case D: if constexpr (D > DLO && D <= Buf::kMax) { \
+          if constexpr (kCompD<D, Buf::kMax>) {   /* heavy phase only: these degrees lie above kLightD */ \
+            if (comp == D) { \
+              vn_compute<D, Buf, true>(a, lane4, cur, a.fslot[D]); \
+              break; \
+            } \
+          } \
+          vn_compute<D>(a, lane4, cur, a.fslot[D]); } break;
         IBL_DEG_CASES(X)
 #undef X
         default: break;
@@ -923,10 +942,16 @@ __device__ __forceinline__ void ib_pass(const IbFastArgs& a, const uint8_t* lds,
   // the waves light-first measured VN 0.4205 ms against 0.433 ms for half (the round-2 choice). Round 6, three
   // alternating repetitions on each of two boxes (profiles/r06_light_first_share_sweep_*.txt): 6 of 16 beat 4 of
   // 16 in all six (C4 +0.26 % / +0.4 %, VN -1 % / -1.5 %); 3, 5, 8 and 10 did not.
+  // With the composite final step of the variable chains the heavy share of the pass shrank: 4 of 16 beat 6 of 16 in
+  // three alternating runs on one box (profiles/ib_vn_composite_c4_ab.json: C4 +0.5 %, VN 0.325 -> 0.320 ms), 8 lost.
+  // The max-degree-16 kernel keeps round 6's share (IBL_MIX16_WIDE): it has no composite and was not re-measured.
 #ifndef IBL_MIX16
-#define IBL_MIX16 6
+#define IBL_MIX16 4
 #endif
-  const bool light_first = VN && (int)(threadIdx.x >> 6) * 16 < wpb * IBL_MIX16;
+#ifndef IBL_MIX16_WIDE
+#define IBL_MIX16_WIDE 6
+#endif
+  const bool light_first = VN && (int)(threadIdx.x >> 6) * 16 < wpb * (MAXD <= 8 ? IBL_MIX16 : IBL_MIX16_WIDE);
 #pragma unroll 1
   for (int r = 0; r < 2; ++r) {
     if ((r == 0) != light_first)
@@ -986,13 +1011,21 @@ __global__ __launch_bounds__(MAXD <= 8 ? IBL_LB8C : IBL_LB16, MAXD <= 8 ? IBL_WP
 }
 
 template <int MAXD>
-__global__ __launch_bounds__(MAXD <= 8 ? IBL_LB8 : IBL_LB16, MAXD <= 8 ? IBL_WPE8 : 1) void ib_vn_fast(IbFastArgs a) {
+__global__ __launch_bounds__(MAXD <= 8 ? IBL_LB8 : IBL_LB16, MAXD <= 8 ? IBL_WPE8 : 1) void ib_vn_fast(IbFastArgs a,
+    const uint32_t* cimg, int comp) {
   extern __shared__ __attribute__((aligned(16))) uint8_t lds[];
   if (!gate_open(a.gate, threadIdx.x & 63)) return;
   lds_at_zero(lds);
-  stage_pass(lds, a);
-  __syncthreads();
-  ib_pass<MAXD, true, false>(a, lds);
+  if constexpr (MAXD <= 8) {   // comp: the variable degree whose composite image cimg is, 0 = none (as ib_cn_fast)
+    if (comp != 0) stage_pass_comp(lds, a, cimg);
+    else stage_pass(lds, a);
+    __syncthreads();
+    ib_pass<MAXD, true, false>(a, lds, comp);
+  } else {
+    stage_pass(lds, a);
+    __syncthreads();
+    ib_pass<MAXD, true, false>(a, lds);
+  }
 }
 
 __global__ __launch_bounds__(1024) void ib_dec_fast(IbDecArgs a) {
@@ -2089,9 +2122,14 @@ hipError_t launch_ib_cn_fast(const IbFastArgs& a, int maxd, int grid, int block,
   }
   return hipGetLastError();
 }
-hipError_t launch_ib_vn_fast(const IbFastArgs& a, int maxd, int grid, int block, size_t lds, hipStream_t s) {
-  if (maxd <= 8) hipLaunchKernelGGL(ib_vn_fast<8>, dim3(grid), dim3(block), lds, s, a);
-  else hipLaunchKernelGGL(ib_vn_fast<16>, dim3(grid), dim3(block), lds, s, a);
+hipError_t launch_ib_vn_fast(const IbFastArgs& a, int maxd, int grid, int block, size_t lds, hipStream_t s,
+                             const uint32_t* cimg, int comp) {
+  // a composite: as for the check pass - the tables take exactly one super-region and the LDS covers both
+  if (comp != 0 && !(maxd <= 8 && comp >= 5 && comp <= 8 && cimg && lds_of_quads(a.nt) == (size_t)kSuper &&
+                     lds >= 2 * (size_t)kSuper + 8))
+    return hipErrorInvalidValue;
+  if (maxd <= 8) hipLaunchKernelGGL(ib_vn_fast<8>, dim3(grid), dim3(block), lds, s, a, cimg, comp);
+  else hipLaunchKernelGGL(ib_vn_fast<16>, dim3(grid), dim3(block), lds, s, a, cimg, comp);
   return hipGetLastError();
 }
 int ib_fast_chunk(int maxd) { return maxd <= 8 ? chunkOf<8>() : chunkOf<16>(); }

@@ -276,6 +276,63 @@ inline void ib_composite_pass(const int32_t* cn, const int32_t* mc, bool match, 
   ib_composite_image(L, F, img);
 }
 
+// Composite final step of the IB variable chains (ib_vn_fast<8>, the bodies vn_group_cp; under
+// tests/asan/vn_composite_image_check.cpp). The chains of outputs 0 .. D-3 of a degree-D variable end in "... ->
+// V_{D-3}(., x_{D-2}) -> final_D(., x_{D-1})", the check chains' shape, so for one variable degree D* in 5..8 the
+// same composite table (layout, image and LDS place of ib_composite_image) takes those two steps as one.
+//
+// Table slots of a variable pass image for the variables a pass walks (`deg`: their degrees): the raw tables up to
+// the largest degree walked and, with matching, one composed final table per walked degree >= 2, in ascending
+// order behind them (without matching a degree's final table is raw table d - 2). The full image (every variable)
+// and the rest image of a folding decoder (the variables the fold leaves to the variable pass) are both planned
+// by this rule; the images differ where the fold takes every variable of a degree.
+struct IbVnSlots {
+  std::vector<int> deg;                  // the degrees walked, ascending
+  int nraw = 0, nt = 0;                  // raw tables; all tables
+  int32_t fslot[kMaxD + 1] = {0};        // per degree <= kMaxD: slot of its final table
+};
+inline IbVnSlots ib_vn_slots(const std::vector<int32_t>& deg, bool match) {
+  IbVnSlots sl;
+  sl.deg.assign(deg.begin(), deg.end());
+  std::sort(sl.deg.begin(), sl.deg.end());
+  sl.deg.erase(std::unique(sl.deg.begin(), sl.deg.end()), sl.deg.end());
+  const int dmax = sl.deg.empty() ? 0 : sl.deg.back();
+  sl.nt = sl.nraw = match ? std::max(dmax - 2, 0) : std::max(dmax - 1, 0);
+  for (int d : sl.deg) {
+    if (d < 2) continue;
+    const int fs = match ? sl.nt++ : d - 2;
+    if (d <= kMaxD) sl.fslot[d] = fs;
+  }
+  return sl;
+}
+// D*: the variable degree in 5..8 with the most nodes among the walked ones (ties: the larger), if the per-pass
+// kernel is the degree <= 8 one (vm = the code's largest variable degree) and the composite's super-region fits the
+// LDS behind the pass's vn_tables tables (ib_vn_slots(..).nt) and before the two work counters; else 0.
+inline int32_t ib_vn_composite_degree(const std::vector<int32_t>& deg, int vm, int vn_tables) {
+  return ib_composite_degree(deg, vm, vn_tables);   // the check side's rule on the walked variables' degrees
+}
+// Entry (t, m) of raw table l of variable pass k in the reference-layout VN vector (per pass: V_0 of Tc x T, then
+// VM - 1 tables of T x T).
+inline int64_t ib_vn_raw_index(int Tc, int T, int VM, int k, int l, int t, int m) {
+  const int64_t T2 = (int64_t)T * T, off = (int64_t)k * ((int64_t)Tc * T + (int64_t)(VM - 1) * T2);
+  return off + (l == 0 ? (int64_t)t * T + m : (int64_t)Tc * T + (int64_t)(l - 1) * T2 + (int64_t)t * T + m);
+}
+// The composite image of variable pass k for degree D (5 <= D <= VM), the fast path's alphabets (Tc = T <= 16):
+// L = raw table D - 3, F = raw table D - 2 with the matching row of degree D composed into it when matching is on -
+// the table the pass image holds at slot fslot[D].
+inline void ib_vn_composite_pass(const int32_t* vn, const int32_t* mv, bool match, int Tc, int T, int VM, int k, int D,
+                                 uint32_t* img) {
+  uint8_t L[256] = {0}, F[256] = {0};
+  const int64_t mrow = (int64_t)k * T * VM + (int64_t)(D - 1) * T;
+  for (int t = 0; t < T; ++t)
+    for (int m = 0; m < T; ++m) {
+      const int32_t r = vn[ib_vn_raw_index(Tc, T, VM, k, D - 2, t, m)];
+      L[16 * t + m] = (uint8_t)vn[ib_vn_raw_index(Tc, T, VM, k, D - 3, t, m)];
+      F[16 * t + m] = (uint8_t)(match ? mv[mrow + r] : r);
+    }
+  ib_composite_image(L, F, img);
+}
+
 // Task tables of the fused kernels (FlFusedArgs, IbFusedArgs).
 struct FusedTasks {
   std::vector<int32_t> cn_task, vn_task, vn_node, vn_slot;

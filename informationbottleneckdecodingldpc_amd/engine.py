@@ -81,12 +81,13 @@ class IBDecoder:
     (one launch per check / variable pass) or "fused" (raises when the code does not fit); both give
     identical results (``ibl_ib_set_path``). ``fused`` tells which one decodes run. ``fold`` switches the per-pass
     path's degree-2 variable fold (``ibl_ib_set_fold``; ``folded`` = variables it folds, results identical),
-    ``composite`` the composite final step of its check chains (``ibl_ib_set_composite``; results identical)."""
+    ``composite`` the composite final step of its check chains (``ibl_ib_set_composite``; results identical),
+    ``vn_composite`` that of its variable chains (``ibl_ib_set_vn_composite``; results identical)."""
 
     _PATHS = {"auto": _lib.IBL_PATH_AUTO, "passes": _lib.IBL_PATH_PASSES, "fused": _lib.IBL_PATH_FUSED}
 
     def __init__(self, graph: Graph, tables: IBTables, match: bool, max_batch: int, force_generic: bool = False,
-                 path: str = "auto", fold: bool = True, composite: bool = True):
+                 path: str = "auto", fold: bool = True, composite: bool = True, vn_composite: bool = True):
         self.graph = graph
         self.tables = tables
         self.match = bool(match)
@@ -112,6 +113,8 @@ class IBDecoder:
             self.fold = False
         if not composite:
             self.composite = False
+        if not vn_composite:
+            self.vn_composite = False
 
     @property
     def fused(self) -> bool:
@@ -158,6 +161,18 @@ class IBDecoder:
     @composite.setter
     def composite(self, on: bool) -> None:
         _lib.check(_lib.load().ibl_ib_set_composite(self._h, int(bool(on))), "ibl_ib_set_composite")
+
+    @property
+    def vn_composite(self) -> int:
+        """Variable degree whose chains the per-pass fast path ends in the composite table step
+        (``ibl_ib_vn_composite``), for the list its variable pass walks now (``fold``); 0: none planned, or off."""
+        d = ctypes.c_int32()
+        _lib.check(_lib.load().ibl_ib_vn_composite(self._h, ctypes.byref(d)), "ibl_ib_vn_composite")
+        return int(d.value)
+
+    @vn_composite.setter
+    def vn_composite(self, on: bool) -> None:
+        _lib.check(_lib.load().ibl_ib_set_vn_composite(self._h, int(bool(on))), "ibl_ib_set_vn_composite")
 
     def fused_ncw(self, B: int) -> int:
         """Codewords per workgroup the fused kernel decodes a batch of ``B`` with (8, or 4 for half

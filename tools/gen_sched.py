@@ -80,6 +80,18 @@ def vn_chains(D):
     return ch
 
 
+def vn_chains_composite(D):
+    """vn_chains with the last two steps of outputs 0 .. D-3, "-> V_{D-3}(., in_{D-2}) -> final(., in_{D-1})", as one
+    composite step ("k", as cn_chains_composite; DESIGN.md "Composite final step of the variable chains")."""
+    ch = vn_chains(D)
+    for c in ch:
+        if c["out"] <= D - 3:
+            assert len(c["steps"]) >= 2 and [st[1] for st in c["steps"][-2:]] == [D - 2, D - 1]
+            assert [st[3] for st in c["steps"][-2:]] == [D - 3, D - 2]
+            c["steps"][-2:] = [("k", D - 2, None, None)]
+    return ch
+
+
 def schedule(chains, L):
     """List scheduling: returns [(time, [(chain, step_index), ...]), ...]."""
     by_id = {c["id"]: c for c in chains}
@@ -166,12 +178,66 @@ def emit_body(kind, D, S, L):
     return lines
 
 
+def emit_body_cp(D, S, L):
+    """The loop-form variable body of the degree whose composite table the launch staged (vn_group_cp<D>, degrees
+    5..8): emit_body("vn", ..) with the chains of outputs 0 .. D-3 ending in one read of the composite's dword (lucw;
+    column term colk, shared by those chains) whose nibble (cnib at shk's shift) is taken when the word is packed.
+    Input D-2 then meets only the final table (on the Q chain), so like input D-1 it carries the table's run-time
+    slot in its lane term and its lookups take no offset."""
+    chains = vn_chains_composite(D)
+    by_id = {c["id"]: c for c in chains}
+    sched = schedule(chains, L)
+    steps = [st for c in chains for st in c["steps"]]
+    u8_in = sorted({st[1] for st in steps if st[0] != "k"})
+    q_final = {j for j in u8_in if j == D - 1 or {st[2] for st in steps if st[1] == j and st[0] != "k"} == {"fbase"}}
+    assert q_final == {D - 2, D - 1}
+    lines = ["  const uint32_t lane4f = lane4 + fbase, lane4k = lane4 + kSuper;"]
+    for j in u8_in:
+        for s in range(S):
+            lines.append(f"  const uint32_t q{j}_{s} = colq(in[{j}], k0 + {s}, {'lane4f' if j in q_final else 'lane4'});")
+    for s in range(S):
+        lines.append(f"  const uint32_t qk_{s} = colk(in[{D - 2}], in[{D - 1}], k0 + {s}, lane4k);")
+        lines.append(f"  const uint32_t sh_{s} = shk(in[{D - 1}], k0 + {s});")
+    for s in range(S):
+        lines.append(f"  const uint32_t c_{s} = nib(chw, k0 + {s});")
+
+    def name(cid, k, s):
+        return f"v_{cid}_{k}_{s}"
+
+    for t, issued in sched:
+        lines.append(f"  // step {t}: " + ", ".join(f"{cid}[{k}]" for cid, k in issued))
+        for cid, k in issued:
+            c = by_id[cid]
+            op, j, sl, _ = c["steps"][k]
+            for s in range(S):
+                if op == "c":
+                    expr = f"luc(c_{s}, q{j}_{s}, {sl})"
+                else:
+                    st = c["start"]
+                    assert k or st[0] == "val"
+                    prev = name(cid, k - 1, s) if k else name(st[1], st[2], s)
+                    expr = f"lucw({prev}, qk_{s})" if op == "k" else f"luc({prev}, q{j}_{s}, {'0u' if j in q_final else sl})"
+                lines.append(f"  const uint32_t {name(cid, k, s)} = {expr};")
+        for cid, k in issued:
+            c = by_id[cid]
+            if k == len(c["steps"]) - 1:
+                def val(s):
+                    return f"cnib({name(cid, k, s)}, sh_{s})" if c["steps"][k][0] == "k" else name(cid, k, s)
+                pk = val(0)
+                for s in range(1, S):
+                    pk = f"{pk} | ({val(s)} << {4 * s})"
+                lines.append(f"  o[{c['out']}] |= ({pk}) << (4 * k0);")
+    return lines
+
+
 def main():
-    """args: S_cn L_cn [S_vn L_vn] (group size and chain lanes per kernel, for degrees <= 8; larger degrees
-    use S = 2, L = 4 so the MAXD = 16 bodies keep their occupancy)."""
+    """args: S_cn L_cn [S_vn L_vn [S_vk L_vk]] (group size and chain lanes per kernel, for degrees <= 8; larger
+    degrees use S = 2, L = 4 so the MAXD = 16 bodies keep their occupancy; S_vk L_vk: the variable pass's composite
+    bodies, default 2 4)."""
     a = [int(x) for x in sys.argv[1:]] or [4, 2, 2, 4]
     Sc, Lc = a[0], a[1]
     Sv, Lv = (a[2], a[3]) if len(a) >= 4 else (Sc, Lc)
+    Sk, Lk = (a[4], a[5]) if len(a) >= 6 else (2, 4)
 
     def cfg(S, L, D):
         return (S, L) if D <= 8 else (2, 4)
@@ -197,6 +263,18 @@ def main():
         print("                                                         uint32_t chw, uint32_t fbase,")
         print(f"                                                         uint32_t (&o)[{D}], int k0) {{")
         print("\n".join(emit_body("vn", D, *cfg(Sv, Lv, D))))
+        print("}")
+    # the variable pass's composite bodies (ib_vn_fast<8>, the degree whose composite table the launch staged)
+    print(f"// Composite final step of the variable chains, degrees 5..8: groups of {Sk} codewords, {Lk} chains.")
+    print(f"__host__ __device__ constexpr int vn_cp_sched_s() {{ return {Sk}; }}")
+    print("template <int D> __device__ __forceinline__ void vn_group_cp(uint32_t lane4, const uint32_t (&in)[D],")
+    print("                                                            uint32_t chw, uint32_t fbase,")
+    print("                                                            uint32_t (&o)[D], int k0);")
+    for D in range(5, 9):
+        print(f"template <> __device__ __forceinline__ void vn_group_cp<{D}>(uint32_t lane4, const uint32_t (&in)[{D}],")
+        print("                                                            uint32_t chw, uint32_t fbase,")
+        print(f"                                                            uint32_t (&o)[{D}], int k0) {{")
+        print("\n".join(emit_body_cp(D, Sk, Lk)))
         print("}")
 
 
@@ -299,7 +377,7 @@ def emit_unrolled(kind, D, S, L, fold=False, comp=False):
 
 
 def main_unrolled(a):
-    Sc, Lc, Sv, Lv = a or [4, 2, 2, 4]
+    Sc, Lc, Sv, Lv = (a or [4, 2, 2, 4])[:4]   # (S_vk L_vk, the variable pass's composite loop bodies: ib_sched.inc only)
     print(f"// GENERATED by tools/gen_sched.py {' '.join(['--unrolled', *map(str, a)])} -- do not edit.")
     print(f"// Unrolled fold schedules of the IB fast path, degrees <= 8 (see tools/gen_sched.py): CN groups of {Sc}")
     print(f"// codewords, {Lc} chains; VN groups of {Sv}, {Lv} chains. K0 = first codeword, ST = stride of the group.")

@@ -22,7 +22,8 @@ VARIANTS = {
     # variable pass co-scheduling: waves with (threadIdx.x >> 8) < IBL_MIX take the light (degree <= 4,
     # HBM-bound) items first, the others the heavy (LDS-bound) ones
     "mix1": ["IBL_MIX16=4"],
-    "mix0": ["IBL_MIX16=0"],    # no light-first waves in the variable pass (round 5 adopted 4 of 16, round 6 6 of 16)
+    # no light-first waves in the variable pass (round 5 adopted 4 of 16, round 6 6 of 16, the variable composite 4 again)
+    "mix0": ["IBL_MIX16=0"],
     "mixw5": ["IBL_MIX16=5"],
     "mixw10": ["IBL_MIX16=10"],
     "mix2": ["IBL_MIX16=8"],
@@ -45,6 +46,10 @@ VARIANTS = {
     "cl3": ['IBL_SCHED_FILE="ib_sched_cl3.inc"'],
     "v4l2": ['IBL_SCHED_FILE="ib_sched_v4l2.inc"'],
     "v2l3": ['IBL_SCHED_FILE="ib_sched_v2l3.inc"'],
+    # the variable pass's composite bodies with 4 codewords x 4 chains / 4 x 2 (the default is 2 x 4); both put
+    # ib_vn_fast<8> at 128 VGPRs with 7 spilled (24 B private segment), which ibl_ib_create refuses
+    "vk44": ['IBL_SCHED_FILE="ib_sched_vk44.inc"'],
+    "vk42": ['IBL_SCHED_FILE="ib_sched_vk42.inc"'],
     # fused IB kernel phase trace (IBL_TRACE_FUSED=<file>)
     "ftrace": ["IBL_FUSED_TRACE=1", "IBL_DIAG=1"],
     # layered min-sum kernel task trace (IBL_TRACE_LAYERED=<file>; tools/trace_layered.py)
@@ -62,8 +67,9 @@ VARIANTS = {
 # per-source flag overrides (replace _build.SRC_FLAGS)
 SRC_FLAGS = {"ieeeon": {"float_kernels.hip": ["-fno-honor-nans"]}}
 # gen_sched.py arguments of the variants that need their own schedule file
-# (S_cn L_cn S_vn L_vn; both generated files, ib_sched_<n>.inc and ib_sched_<n>_unrolled.inc)
-SCHED_ARGS = {"s2n": "2 4 2 4", "w1l4": "4 4 2 4", "w2l4": "4 4 2 4", "cl3": "4 3 2 4", "v4l2": "4 2 4 2", "v2l3": "4 2 2 3"}
+# (S_cn L_cn S_vn L_vn [S_vk L_vk]; both generated files, ib_sched_<n>.inc and ib_sched_<n>_unrolled.inc)
+SCHED_ARGS = {"s2n": "2 4 2 4", "w1l4": "4 4 2 4", "w2l4": "4 4 2 4", "cl3": "4 3 2 4", "v4l2": "4 2 4 2", "v2l3": "4 2 2 3",
+              "vk44": "4 2 2 4 4 4", "vk42": "4 2 2 4 4 2"}
 
 if __name__ == "__main__":
     names = sys.argv[1:] or list(VARIANTS)
