@@ -229,11 +229,6 @@ __device__ __forceinline__ uint32_t valid_nib8(int remaining) {
   return remaining >= 8 ? 0xFFFFFFFFu : (remaining <= 0 ? 0u : ((1u << (4 * remaining)) - 1u));
 }
 
-template <int W> struct RowVec;
-template <> struct RowVec<1> { typedef uint32_t T; };
-template <> struct RowVec<2> { typedef uint2 T; };
-template <> struct RowVec<4> { typedef uint4 T; };
-
 // IBL_NT: message rows are streamed once per pass (0.93 GB per inbox at B = 8192, far beyond the
 // caches): 1 = nontemporal loads and stores of the variable pass's rows (the HBM-bound pass). The
 // check pass keeps plain accesses (its registers are at the cap). A/B on one box (tools/ab.sh, DVB-S2
@@ -249,55 +244,63 @@ template <> struct RowVec<4> { typedef uint4 T; };
 #endif
 typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
-template <int W> struct RowNV;
-template <> struct RowNV<1> { typedef uint32_t T; };
-template <> struct RowNV<2> { typedef u32x2_t T; };
-template <> struct RowNV<4> { typedef u32x4_t T; };
 
-template <int W, bool NT = false>
-__device__ __forceinline__ void load_row(const uint8_t* p, uint32_t (&r)[W]) {
-  if constexpr (NT) {
-    using T = typename RowNV<W>::T;
-    const T v = __builtin_nontemporal_load(reinterpret_cast<const T*>(p));
-    if constexpr (W == 1) {
-      r[0] = v;
-    } else {
-#pragma unroll
-      for (int i = 0; i < W; ++i) r[i] = v[i];
-    }
-  } else {
-    const auto v = *reinterpret_cast<const typename RowVec<W>::T*>(p);
-    if constexpr (W == 1) {
-      r[0] = v;
-    } else if constexpr (W == 2) {
-      r[0] = v.x; r[1] = v.y;
-    } else {
-      r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w;
-    }
-  }
+// Rows addressed from a scalar row base. base + row * ldb is wave-uniform (row is a scalar load or a v_readlane),
+// and the lane's part is the 32-bit byte offset the item already holds, so a row access needs no vector address
+// arithmetic: the row is a raw buffer of its own (ldb bytes, so a lane past the row's end is dropped, not written to
+// the next row) and the lane offset its vector offset. As a 64-bit pointer sum the compiler adds the lane offset to
+// the buffer's base once per item and pays a 64-bit vector add (v_lshl_add_u64) per row, on the busiest unit of the
+// per-pass kernels; the global scalar-base form is not selected because the widened offset lives in another block.
+// A row's descriptor has no 32-bit limit on the buffer's size. NT: the nontemporal policy of the plain accesses.
+// The row is pinned to a scalar register (nothing where it is one already): where the compiler merges the store
+// sequences of two degrees it carries the rows in vector registers, and a descriptor built from those gets a waterfall
+// loop around every access, although the values are uniform.
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t row_rsrc(const uint8_t* base, uint32_t row, uint32_t ldb) {
+  asm("" : "+s"(row));
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(base + (size_t)row * ldb), 0, (int)ldb, 0x00020000);
 }
-
 template <int W, bool NT = false>
-__device__ __forceinline__ void store_row(uint8_t* p, const uint32_t (&r)[W]) {
-  if constexpr (NT) {
-    using T = typename RowNV<W>::T;
-    T v;
-    if constexpr (W == 1) {
-      v = r[0];
-    } else {
-#pragma unroll
-      for (int i = 0; i < W; ++i) v[i] = r[i];
-    }
-    __builtin_nontemporal_store(v, reinterpret_cast<T*>(p));
-  } else if constexpr (W == 1) {
-    *reinterpret_cast<uint32_t*>(p) = r[0];
+__device__ __forceinline__ void load_row_at(const uint8_t* base, uint32_t row, uint32_t ldb, uint32_t off,
+                                            uint32_t (&r)[W]) {
+  const __amdgpu_buffer_rsrc_t rs = row_rsrc(base, row, ldb);
+  constexpr int aux = NT ? 2 : 0;
+  if constexpr (W == 1) {
+    r[0] = __builtin_amdgcn_raw_buffer_load_b32(rs, off, 0, aux);
   } else if constexpr (W == 2) {
-    *reinterpret_cast<uint2*>(p) = make_uint2(r[0], r[1]);
+    const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, aux);
+    r[0] = v[0]; r[1] = v[1];
   } else {
-    *reinterpret_cast<uint4*>(p) = make_uint4(r[0], r[1], r[2], r[3]);
+    const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, off, 0, aux);
+#pragma unroll
+    for (int i = 0; i < W; ++i) r[i] = v[i];
+  }
+}
+template <int W, bool NT = false>
+__device__ __forceinline__ void store_row_at(uint8_t* base, uint32_t row, uint32_t ldb, uint32_t off,
+                                             const uint32_t (&r)[W]) {
+  const __amdgpu_buffer_rsrc_t rs = row_rsrc(base, row, ldb);
+  constexpr int aux = NT ? 2 : 0;
+  if constexpr (W == 1) {
+    __builtin_amdgcn_raw_buffer_store_b32(r[0], rs, off, 0, aux);
+  } else if constexpr (W == 2) {
+    u32x2_t v;
+    v[0] = r[0]; v[1] = r[1];
+    __builtin_amdgcn_raw_buffer_store_b64(v, rs, off, 0, aux);
+  } else {
+    u32x4_t v;
+#pragma unroll
+    for (int i = 0; i < W; ++i) v[i] = r[i];
+    __builtin_amdgcn_raw_buffer_store_b128(v, rs, off, 0, aux);
   }
 }
 
+// After an item's last row store. The store sequences of two degrees (or fold classes) end alike, and merged into
+// one block their descriptors become vector-register values (above). An asm statement with operands is never merged,
+// and so neither is the store before it: ID tells the items' bodies apart.
+template <int ID>
+__device__ __forceinline__ void stores_end(uint32_t row) {
+  asm volatile("" ::"s"(row), "n"(ID));
+}
 
 // A wave item's inputs, fetched one item ahead of its computation (register double buffer):
 // the row loads of item k+1 are issued before item k is computed, so HBM latency overlaps the
@@ -355,11 +358,12 @@ __device__ __forceinline__ void fetch_item(const IbFastArgs& a, int item, int la
 #pragma unroll
   for (int j = 0; j < MAXD; ++j) {
     const int e = b.st + min(j, b.d - 1);
-    const uint8_t* row = GATHER ? a.ch8 + (size_t)sload(a.gather, e) * a.ldb : a.in + (size_t)e * a.ldb;
-    load_row<W, VN ? (bool)IBL_NT : ((bool)IBL_NT_CN && !GATHER)>(row + b.off, b.row[j]);
+    constexpr bool NT = VN ? (bool)IBL_NT : ((bool)IBL_NT_CN && !GATHER);
+    if constexpr (GATHER) load_row_at<W, NT>(a.ch8, (uint32_t)sload(a.gather, e), (uint32_t)a.ldb, b.off, b.row[j]);
+    else load_row_at<W, NT>(a.in, (uint32_t)e, (uint32_t)a.ldb, b.off, b.row[j]);
   }
   if (VN) {
-    load_row<W, IBL_NT>(a.ch8 + (size_t)node * a.ldb + b.off, b.chw);
+    load_row_at<W, IBL_NT>(a.ch8, (uint32_t)node, (uint32_t)a.ldb, b.off, b.chw);
   } else {
 #pragma unroll
     for (int i = 0; i < W; ++i) b.chw[i] = 0;
@@ -507,8 +511,8 @@ __device__ __forceinline__ void cn_compute(const IbFastArgs& a, uint32_t lane4, 
   uint32_t outw[D][W], trow[D];
   uint32_t chf[2][W] = {};
   if constexpr (FC != 0 && !GATHER) {
-    if constexpr ((FC & 1) != 0) load_row<W>(a.ch8 + (size_t)b.fv0 * (uint32_t)a.ldb + b.off, chf[0]);
-    if constexpr ((FC & 2) != 0) load_row<W>(a.ch8 + (size_t)b.fv1 * (uint32_t)a.ldb + b.off, chf[1]);
+    if constexpr ((FC & 1) != 0) load_row_at<W>(a.ch8, (uint32_t)b.fv0, (uint32_t)a.ldb, b.off, chf[0]);
+    if constexpr ((FC & 2) != 0) load_row_at<W>(a.ch8, (uint32_t)b.fv1, (uint32_t)a.ldb, b.off, chf[1]);
   }
 #pragma unroll
   for (int w = 0; w < D; ++w) trow[w] = __builtin_amdgcn_readlane(b.tgv, w);
@@ -572,7 +576,7 @@ __device__ __forceinline__ void cn_compute(const IbFastArgs& a, uint32_t lane4, 
   }
   if constexpr (FC == 0 || KEEP) {
 #pragma unroll
-    for (int w = 0; w < D; ++w) store_row<W, (bool)IBL_NT_CN>(a.out + (size_t)trow[w] * (uint32_t)a.ldb + b.off, outw[w]);
+    for (int w = 0; w < D; ++w) store_row_at<W, (bool)IBL_NT_CN>(a.out, trow[w], (uint32_t)a.ldb, b.off, outw[w]);
   }
   if constexpr (FC != 0 && KEEP) {
     const uint32_t lane4c = lane4 + slot_off(a.fold_slot);
@@ -582,24 +586,25 @@ __device__ __forceinline__ void cn_compute(const IbFastArgs& a, uint32_t lane4, 
       uint32_t fw[W];
 #pragma unroll
       for (int i = 0; i < W; ++i) fw[i] = fold_word(outw[D - 2 + fa][i], GATHER ? b.row[D - 2 + fa][i] : chf[fa][i], lane4c);
-      store_row<W, (bool)IBL_NT_CN>(fout + (size_t)(uint32_t)(fa ? b.fd1 : b.fd0) * (uint32_t)a.ldb + b.off, fw);
+      store_row_at<W, (bool)IBL_NT_CN>(fout, (uint32_t)(fa ? b.fd1 : b.fd0), (uint32_t)a.ldb, b.off, fw);
     }
   } else if constexpr (FC != 0) {
 #pragma unroll
-    for (int w = 0; w < D - 2; ++w) store_row<W, (bool)IBL_NT_CN>(a.out + (size_t)trow[w] * (uint32_t)a.ldb + b.off, outw[w]);
+    for (int w = 0; w < D - 2; ++w) store_row_at<W, (bool)IBL_NT_CN>(a.out, trow[w], (uint32_t)a.ldb, b.off, outw[w]);
     // the two trailing outputs: compile-time destinations (a run-time choice of the base pointer would go
     // through a pointer table in scratch)
     if constexpr ((FC & 1) != 0) {
-      store_row<W, (bool)IBL_NT_CN>(fout + (size_t)(uint32_t)b.fd0 * (uint32_t)a.ldb + b.off, outw[D - 2]);
+      store_row_at<W, (bool)IBL_NT_CN>(fout, (uint32_t)b.fd0, (uint32_t)a.ldb, b.off, outw[D - 2]);
     } else {
-      store_row<W, (bool)IBL_NT_CN>(a.out + (size_t)trow[D - 2] * (uint32_t)a.ldb + b.off, outw[D - 2]);
+      store_row_at<W, (bool)IBL_NT_CN>(a.out, trow[D - 2], (uint32_t)a.ldb, b.off, outw[D - 2]);
     }
     if constexpr ((FC & 2) != 0) {
-      store_row<W, (bool)IBL_NT_CN>(fout + (size_t)(uint32_t)b.fd1 * (uint32_t)a.ldb + b.off, outw[D - 1]);
+      store_row_at<W, (bool)IBL_NT_CN>(fout, (uint32_t)b.fd1, (uint32_t)a.ldb, b.off, outw[D - 1]);
     } else {
-      store_row<W, (bool)IBL_NT_CN>(a.out + (size_t)trow[D - 1] * (uint32_t)a.ldb + b.off, outw[D - 1]);
+      store_row_at<W, (bool)IBL_NT_CN>(a.out, trow[D - 1], (uint32_t)a.ldb, b.off, outw[D - 1]);
     }
   }
+  stores_end<D * 8 + FC * 2 + KEEP>(trow[D - 1]);
 }
 
 // folding check pass: the item's class is wave-uniform (one check per item)
@@ -692,7 +697,8 @@ __device__ __forceinline__ void vn_compute(const IbFastArgs& a, uint32_t lane4, 
     }
   }
 #pragma unroll
-  for (int w = 0; w < D; ++w) store_row<W, IBL_NT>(a.out + (size_t)trow[w] * (uint32_t)a.ldb + b.off, outw[w]);
+  for (int w = 0; w < D; ++w) store_row_at<W, IBL_NT>(a.out, trow[w], (uint32_t)a.ldb, b.off, outw[w]);
+  stores_end<D>(trow[D - 1]);
 }
 
 // ------------------------------------------------------------- decision output
