@@ -399,7 +399,7 @@ int ibl_float_decode_each(ibl_float* h, const void* d_llr, int32_t llr_dtype, in
  *   (IBL_EINVAL) and the degree range (IBL_EUNSUPPORTED); ibl_last_error names the first offending check.
  * ibl_layered_create   validates the layers, builds the device plan and allocates a [max_batch][N] fp32 staging
  *   buffer.  alpha, beta >= 0, llr_max > 0 (the project's value: 150).  precision: IBL_F32; IBL_F64 returns
- *   IBL_EUNSUPPORTED (fp64 and layered BP are not built).
+ *   IBL_EUNSUPPORTED (fp64 is not built; layered BP is ibl_layered_create_bp, "Layered BP" below).
  *   Fit rule: the decoder is one fused on-chip kernel — one wave owns one codeword, whose APP LLRs (4 N bytes)
  *   and compressed check state (12 bytes per check: corrected m1, m2, argmin position | sign bits) stay in LDS
  *   through all iterations.  A workgroup holds cw_per_group = min(8, floor(160 KiB / (4 N + 12 n_c))) codewords;
@@ -472,6 +472,65 @@ int ibl_layered_geometry(const ibl_layered* h, int32_t B, int32_t* cw_per_group,
 int ibl_layered_set_compaction(ibl_layered* h, int32_t every, int32_t min_free_pct);
 int ibl_layered_compaction_stats(const ibl_layered* h, void* stream, int32_t* compactions, int32_t* extent);
 void ibl_layered_destroy(ibl_layered* h);
+
+/*
+ * Layered BP: layered (row-serial) belief propagation, fp32.  Layers, the per-codeword early stop, iters[] and out[]
+ * are those of "Layered min-sum" above; the check update is the box-plus of the flooding fp32 BP decoder.
+ *
+ * Semantics, per codeword:
+ *   P[v] = channel LLR;  R[e] = 0
+ *   for it = 1..imax:
+ *     for each layer in order, each check c of it, edges e_0..e_{D-1} in ascending column order:
+ *         Q_k = P[v_k] - R[e_k]                        (one rounded subtraction, NOT clamped)
+ *         D == 2:  R'_0 = clamp(Q_1), R'_1 = clamp(Q_0)
+ *         D >= 3:  S_{D-1} = Q_{D-1};  S_j = Q_j [+] S_{j+1}  (j = D-2 .. 1)
+ *                  R'_0 = S_1;  F = Q_0
+ *                  for w = 1 .. D-2:  R'_w = F [+] S_{w+1};  F = Q_w [+] F
+ *                  R'_{D-1} = F                          (3(D-2) box-pluses)
+ *         R[e_k] = R'_k;   P[v_k] = Q_k + R'_k          (one rounded addition)
+ *     early stop, iters[], out[]: exactly as "Layered min-sum" (per codeword, frozen at the stop)
+ *   a [+] b is the fp32 box-plus of the flooding BP check node: magnitude
+ *     min(|a|,|b|) + ln(1 + e^-(|a|+|b|)) - ln(1 + e^-||a|-|b||) on the hardware's base-2 exp / log, clamped to
+ *     [0, llr_max], sign sgn(a) sgn(b).  It clamps its result, so S_j, F and every R' of a check of degree >= 3 lie
+ *     in [-llr_max, llr_max]; clamp is the clamp to +-llr_max, needed for the degree-2 messages only.
+ *   Why Q is not clamped (the layered min-sum rule, Q = clamp(P - R), P = Q + R, is unstable with box-plus messages):
+ *     once that clamp bites, P loses the other checks' contributions, and the next check sees a small Q for a
+ *     variable that was firmly known.  WLAN N = 648 at 2.5 dB with llr_max 30 then leaves NO codeword of 64 with a
+ *     zero syndrome from iteration 10 on; with the rule above all 64 stay converged (tests/test_cpu_layered_bp.py).
+ *     |P| is bounded by |llr| + (variable degree) * llr_max.
+ *   Preconditions: channel LLRs finite, |llr| + 16 * llr_max below FLT_MAX.
+ *   Supported: check degrees 2..16 (a check above 16 is IBL_EUNSUPPORTED, the message names it), variable degrees
+ *   up to 16 (what the precondition's bound covers; no kernel depends on the variable degree), IBL_F32 only.
+ *   Parity with this specification is by value (|x - y| <= 1e-5 max(|x|, |y|) + 1e-4 against an fp64 evaluation), not
+ *   bit for bit: the transcendentals are the hardware's.  The two paths below run one check core in one operation
+ *   order and give each other's bits.
+ *
+ * ibl_layered_create_bp  validates as ibl_layered_create_path (llr_max > 0 and finite).  IBL_F64 is IBL_EUNSUPPORTED
+ *   ("fp64 is not built").  path:
+ *     IBL_PATH_FUSED   one wave owns one codeword: P[N] and R[E], one fp32 word per edge, stay in LDS through all
+ *                      iterations (lane = check; the task walk, stop, group loop and transposed staging of the
+ *                      min-sum fused kernel).  Fit rule: cw_per_group = min(8, floor(160 KiB / (4 N + 4 E)));
+ *                      IBL_EUNSUPPORTED when that is 0 (N = 1944 rate 1/2, E = 6,966: 35,640 B, 4 codewords; DVB-S2
+ *                      N = 64800 does not fit).  R is laid out task by task, edge k of lane i of a task of `count`
+ *                      checks at rfirst + count k + i: the lanes touch consecutive words, and R is exactly E words.
+ *     IBL_PATH_PASSES  per-layer kernels over HBM: P [N][ldb] and R [E][ldb] fp32 (a row per edge), lane = codeword,
+ *                      one launch per layer, a wave updating one check for 64 codewords.  The masks, the packed
+ *                      syndrome, finalise and output launches are the min-sum path's.  The first iteration takes
+ *                      R = 0 without reading or zeroing the E rows.  An iteration moves 16 E bytes per codeword
+ *                      (P and R of every edge read and written), the first 12 E.  The handle owns about 4 N + 4 E
+ *                      bytes per codeword of max_batch rounded up to 64: DVB-S2 N = 64800 rate 1/2 (E = 226,799)
+ *                      1.17 MB per codeword, 9.6 GB at 8192.  Launch chain, "no allocation, no host
+ *                      synchronisation, capturable" as on the min-sum per-layer path.
+ *     IBL_PATH_AUTO    the fused kernel when the code fits by the rule above, else the per-layer kernels.
+ *   The handle is an ibl_layered: ibl_layered_decode (IBL_F32 in and out), _path_in_use, _geometry and _destroy work
+ *   as documented above; ibl_layered_is_wide and ibl_layered_is_fixed give 0; ibl_layered_set_compaction and
+ *   ibl_layered_compaction_stats return IBL_EUNSUPPORTED ("compaction is not built for the BP decoder").
+ * ibl_layered_is_bp  *bp = 1 for a handle of ibl_layered_create_bp, else 0; NULL arguments are IBL_EINVAL.
+ */
+int ibl_layered_create_bp(const ibl_graph* g, int32_t n_layers, const int32_t* layer_ptr, const int32_t* layer_checks,
+                          int32_t imax, float llr_max, int32_t precision, int32_t max_batch, int32_t path,
+                          ibl_layered** out);
+int ibl_layered_is_bp(const ibl_layered* h, int32_t* bp);
 
 /*
  * Layered min-sum, fixed point: a second arithmetic of the layered decoder above, integer throughout — 8-bit APP

@@ -12,6 +12,10 @@ plus a layered normalised / offset min-sum decoder the reference does not have:
 
     from informationbottleneckdecodingldpc_amd import Min_Sum_Layered_Decoder_class_irregular
 
+and its belief-propagation counterpart (box-plus check update on the same schedule):
+
+    from informationbottleneckdecodingldpc_amd import BeliefPropagation_Layered_Decoder_class_irregular
+
 and for the channel side / drivers:
 
     from informationbottleneckdecodingldpc_amd.awgn_quantizer import AWGN_Channel_Quantizer  # device sampling
@@ -30,6 +34,9 @@ def __getattr__(name):
     if name == "Min_Sum_Layered_Decoder_class_irregular":
         from .min_sum_layered_decoder_irreg import Min_Sum_Layered_Decoder_class_irregular
         return Min_Sum_Layered_Decoder_class_irregular
+    if name == "BeliefPropagation_Layered_Decoder_class_irregular":
+        from .bp_layered_decoder_irreg import BeliefPropagation_Layered_Decoder_class_irregular
+        return BeliefPropagation_Layered_Decoder_class_irregular
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

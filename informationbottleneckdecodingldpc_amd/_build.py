@@ -12,7 +12,7 @@ CSRC = os.path.join(PKG, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 LIB = os.path.join(PKG, "libibldpc.so")
 SOURCES = ["ib_kernels.hip", "float_kernels.hip", "channel_kernels.hip", "encoder_kernels.hip", "layered_kernels.hip",
-           "capi_core.hip", "capi_ib.hip", "capi_float.hip", "capi_layered.hip", "capi_encoder.hip", "comm.hip"]
+           "layered_bp_kernels.hip", "capi_core.hip", "capi_ib.hip", "capi_float.hip", "capi_layered.hip", "capi_encoder.hip", "comm.hip"]
 ARCH = os.environ.get("IBLDPC_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", INCLUDE, "-I", CSRC,
@@ -26,8 +26,14 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", INCLUDE, 
 # layered_kernels: the layered decoder's arithmetic is specified as individually rounded fp32 operations
 # (include/ibldpc.h "Layered min-sum"), and HIP device code contracts a * b + c into an FMA by default: no
 # contraction there. It takes none of float_kernels' flags.
+# layered_bp_kernels: Q = P - R and P = Q + R' are specified as individually rounded operations too (include/ibldpc.h
+# "Layered BP"), so no contraction, as layered_kernels; the shared box-plus (boxplus.h) writes its one FMA out, so its
+# values are float_kernels' under either setting. Messages are never NaN (finite inputs, a clamped box-plus), so
+# -fno-honor-nans spares the quieting v_max before every min / median of the box-plus (4 per operation). The IEEE
+# mode bit stays on: the file uses threadIdx / blockIdx, which -mno-amdgpu-ieee would turn into calls.
 SRC_FLAGS = {"float_kernels.hip": ["-fno-honor-nans", "-mno-amdgpu-ieee"],
-             "layered_kernels.hip": ["-ffp-contract=off"]}
+             "layered_kernels.hip": ["-ffp-contract=off"],
+             "layered_bp_kernels.hip": ["-ffp-contract=off", "-fno-honor-nans"]}
 
 
 def _stale(out: str, deps) -> bool:

@@ -48,7 +48,7 @@ EXPORTS = [
     "ibl_layers_validate", "ibl_layered_create", "ibl_layered_decode", "ibl_layered_geometry", "ibl_layered_destroy",
     "ibl_layered_create_path", "ibl_layered_path_in_use", "ibl_layered_create_fixed", "ibl_layered_is_fixed",
     "ibl_layered_set_compaction", "ibl_layered_compaction_stats", "ibl_layered_is_wide",
-    "ibl_layered_create_fixed_fused",
+    "ibl_layered_create_fixed_fused", "ibl_layered_create_bp", "ibl_layered_is_bp",
 ]
 IBL_COMM_ID_BYTES = 128
 
@@ -149,6 +149,8 @@ def load():
                                            ctypes.POINTER(_vp)]
     L.ibl_layered_create_fixed_fused.argtypes = [_vp, _i32, _i32p, _i32p, _i32, _i32, _i32, _i32, _f32, _i32,
                                                  ctypes.POINTER(_vp)]
+    L.ibl_layered_create_bp.argtypes = [_vp, _i32, _i32p, _i32p, _i32, _f32, _i32, _i32, _i32, ctypes.POINTER(_vp)]
+    L.ibl_layered_is_bp.argtypes = [_vp, ctypes.POINTER(_i32)]
     L.ibl_layered_is_fixed.argtypes = [_vp, ctypes.POINTER(_i32)]
     L.ibl_layered_is_wide.argtypes = [_vp, ctypes.POINTER(_i32)]
     L.ibl_layered_decode.argtypes =[_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]

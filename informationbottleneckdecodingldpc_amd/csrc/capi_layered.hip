@@ -1,7 +1,8 @@
 // C ABI (include/ibldpc.h): the layered normalised / offset min-sum decoder (layered_plan.h, layered_kernels.hip):
 // the fused on-chip kernel for codes whose codeword state fits the LDS, the per-layer path over HBM otherwise, and
 // the fixed-point arithmetic on the per-layer path (ibl_layered_create_fixed) and fused on chip
-// (ibl_layered_create_fixed_fused).
+// (ibl_layered_create_fixed_fused); and the layered BP decoder (layered_bp_kernels.hip, ibl_layered_create_bp) on both
+// paths.
 #include <cmath>
 #include <cstring>
 
@@ -46,6 +47,11 @@ struct ibl_layered {
   // cw_per_group, cw_bytes and bpc as on the fp32 fused handle, and the [max_batch][ldn] int8 codeword rows of
   // layered_plan.h fixfused_buf_bytes(n_v, max_batch)
   DevBuf<int8_t> buf8;
+  // layered BP (ibl_layered_create_bp; fixed = 0, wide = 0): fused = 1 uses task, idx, buf, n_tasks, cw_per_group,
+  // cw_bytes (4 N + 4 E) and bpc as above; fused = 0 uses rec, layer_slot, P, the masks, the counter and bits, and R
+  // [E][ldb], the check messages (layered_plan.h laybp_pass_bytes)
+  int32_t bp = 0;
+  DevBuf<float> R;
 };
 
 namespace {
@@ -150,6 +156,56 @@ int layered_run_fixed(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int3
     if (early_stop && it < h->imax) HIPCHK(launch_layfix_stop(a, it, s));
   }
   HIPCHK(launch_layfix_stage_out(a, d_out, out_dtype, s));
+  return IBL_OK;
+}
+
+// Layered BP, per-layer path: the min-sum chain with the BP stage-in and layer kernels; the first iteration's layers
+// take R = 0 without reading it.
+int layered_run_bp_passes(ibl_layered* h, const float* d_llr, int32_t B, float* d_out, int32_t early_stop,
+                          int32_t* d_iters, hipStream_t s) {
+  const ibl_graph* g = h->g;
+  LayPassArgs a{};
+  // M1 is R. M2 and PS repeat it only because the shared launchers (launch_lay_syndrome, _finalise, _stage_out)
+  // refuse null state pointers; their kernels read none of the three. A shared kernel that starts to touch M2 or PS
+  // must stop serving this handle (layered_kernels.hip is not changed by this decoder, so its check stands).
+  a.P = h->P; a.M1 = h->R; a.M2 = h->R; a.PS = reinterpret_cast<uint32_t*>(h->R.get());
+  a.done = h->done; a.unsat = h->unsat; a.running = h->running; a.bits = h->bits; a.rec = h->rec;
+  a.cols = g->csr_cols; a.iters = d_iters;
+  a.alpha = 1.f; a.beta = 0.f; a.llr_max = h->llr_max;
+  a.n_v = g->n_v; a.n_c = g->n_c; a.B = B; a.ntiles = pass_tiles(B);
+  h->last_B = B;
+  h->last_compact = 0;
+  HIPCHK(launch_laybp_stage_in(a, d_llr, h->imax, s));
+  const int32_t n_layers = (int32_t)h->layer_slot.size() - 1;
+  for (int32_t it = 1; it <= h->imax; ++it) {
+    for (int32_t l = 0; l < n_layers; ++l) {
+      const int32_t s0 = h->layer_slot[l], n = h->layer_slot[l + 1] - s0;
+      HIPCHK(launch_laybp_layer(a, it == 1, s0, n, s));
+    }
+    if (early_stop && it < h->imax) {
+      HIPCHK(launch_lay_syndrome(a, 1, s));
+      HIPCHK(launch_lay_finalise(a, it, s));
+    }
+  }
+  HIPCHK(launch_lay_stage_out(a, d_out, s));
+  return IBL_OK;
+}
+
+// transpose, the fused kernel, transpose
+int layered_run_bp_fused(ibl_layered* h, const float* d_llr, int32_t B, float* d_out, int32_t early_stop,
+                         int32_t* d_iters, hipStream_t s) {
+  const ibl_graph* g = h->g;
+  HIPCHK(launch_lay_transpose(d_llr, h->buf, g->n_v, B, s));
+  LayeredArgs a{};
+  a.buf = h->buf; a.task = h->task; a.idx = h->idx; a.iters = d_iters;
+  a.alpha = 1.f; a.beta = 0.f; a.llr_max = h->llr_max;
+  a.n_v = g->n_v; a.n_c = g->n_c; a.n_tasks = h->n_tasks; a.B = B; a.imax = h->imax;
+  a.early = early_stop ? 1 : 0;
+  a.cw_per_group = h->cw_per_group; a.cw_bytes = (int32_t)h->cw_bytes;
+  int32_t grid = 0;
+  layered_geometry(h, B, &a.ngroups, &grid);
+  HIPCHK(launch_laybp_fused(a, grid, (size_t)h->cw_per_group * h->cw_bytes, s));
+  HIPCHK(launch_lay_transpose(h->buf, d_out, B, g->n_v, s));
   return IBL_OK;
 }
 
@@ -339,6 +395,85 @@ int ibl_layered_create_fixed_fused(const ibl_graph* g, int32_t n_layers, const i
   return IBL_OK;
 }
 
+int ibl_layered_create_bp(const ibl_graph* g, int32_t n_layers, const int32_t* layer_ptr, const int32_t* layer_checks,
+                          int32_t imax, float llr_max, int32_t precision, int32_t max_batch, int32_t path,
+                          ibl_layered** out) {
+  if (!out) return fail(IBL_EINVAL, "out is NULL");
+  *out = nullptr;
+  if (!g) return fail(IBL_EINVAL, "graph is NULL");
+  if (precision == kF64) return fail(IBL_EUNSUPPORTED, "the layered BP decoder is fp32 only (fp64 is not built)");
+  if (precision != kF32) return fail(IBL_EINVAL, "precision must be IBL_F32");
+  if (imax < 1 || max_batch < 1) return fail(IBL_EINVAL, "imax and max_batch must be >= 1");
+  if (!(llr_max > 0.f) || std::isinf(llr_max)) return fail(IBL_EINVAL, "llr_max must be finite and > 0");
+  if (int rc = check_path(path)) return rc;
+  const std::vector<int32_t> ip = graph_indptr(g);
+  int rc = ibl_layers_validate(g->n_v, g->n_c, ip.data(), g->h_cols.data(), n_layers, layer_ptr, layer_checks);
+  if (rc) return rc;
+  const int32_t bad = laybp_unsupported_check(g->n_c, ip.data());
+  if (bad >= 0)
+    return fail(IBL_EUNSUPPORTED, "check " + std::to_string(bad) + " has degree " +
+                                      std::to_string(ip[(size_t)bad + 1] - ip[bad]) +
+                                      ": layered BP supports check degrees 2..16");
+  const int64_t n_e = ip[(size_t)g->n_c];
+  const int32_t cw = laybp_cw_per_group(g->n_v, n_e);
+  HIPCHK(hipSetDevice(g->device));
+  if (path == IBL_PATH_PASSES || (path == IBL_PATH_AUTO && cw < 1)) {
+    LayeredPassPlan pl;
+    plan_layered_passes(g->n_c, ip.data(), n_layers, layer_ptr, layer_checks, &pl);
+    if (pass_grid(pl.max_layer, max_batch) > 0x7fffffffll ||
+        pass_grid(pass_pack_runs(std::max(g->n_v, g->n_c)), max_batch) > 0x7fffffffll ||
+        ((int64_t)g->n_v * pass_tiles(max_batch) + kLayPassWaves - 1) / kLayPassWaves > 0x7fffffffll)
+      return fail(IBL_EINVAL, "max_batch is too large for the per-layer kernels' grids");
+    size_t priv = 0, priv_shared = 0;
+    HIPCHK(laybp_pass_private_bytes(&priv));
+    HIPCHK(lay_pass_private_bytes(&priv_shared));   // the shared pack, syndrome, finalise and stage-out kernels
+    if ((rc = refuse_private(std::max(priv, priv_shared), "a per-layer layered BP kernel has a ",
+                             "-byte private segment (register spill): rebuild required")))
+      return rc;
+    std::unique_ptr<ibl_layered> h(new ibl_layered());
+    h->g = g; h->imax = imax; h->max_batch = max_batch; h->llr_max = llr_max;
+    h->fused = 0; h->bp = 1;
+    h->layer_slot = pl.layer_slot;
+    const LayeredBpBytes by = laybp_pass_bytes(g->n_v, n_e, max_batch);
+    if ((rc = h->rec.upload(pl.rec)) || (rc = h->P.alloc(by.P / 4)) || (rc = h->R.alloc(by.R / 4)) ||
+        (rc = h->done.alloc(by.mask / 8)) || (rc = h->unsat.alloc(by.mask / 8)) || (rc = h->running.alloc(1)) ||
+        (rc = h->bits.alloc(by.bits / 8)))
+      return rc;
+    *out = h.release();
+    return IBL_OK;
+  }
+  if (cw < 1)
+    return fail(IBL_EUNSUPPORTED, "code does not fit the layered BP kernel: one codeword needs 4 N + 4 E = " +
+                                      std::to_string(laybp_cw_bytes(g->n_v, n_e)) + " bytes of LDS, a workgroup has " +
+                                      std::to_string(kLayLds));
+  LayeredBpPlan pl;
+  plan_layered_bp(g->n_v, g->n_c, ip.data(), g->h_cols.data(), n_layers, layer_ptr, layer_checks, &pl);
+  std::unique_ptr<ibl_layered> h(new ibl_layered());
+  h->g = g; h->imax = imax; h->max_batch = max_batch; h->llr_max = llr_max;
+  h->fused = 1; h->bp = 1;
+  h->n_tasks = pl.n_tasks; h->cw_per_group = pl.cw_per_group; h->cw_bytes = pl.cw_bytes;
+  if ((rc = h->task.upload(pl.task)) || (rc = h->idx.upload(pl.idx)) ||
+      (rc = h->buf.alloc((size_t)max_batch * (size_t)g->n_v)))
+    return rc;
+  int bpc = 0;
+  size_t priv = 0;
+  const hipError_t e = laybp_fused_occupancy(h->cw_per_group, (size_t)h->cw_per_group * h->cw_bytes, &bpc, &priv);
+  if (e != hipSuccess) return fail(IBL_EHIP, std::string("layered BP kernel occupancy: ") + hipGetErrorString(e));
+  if (bpc < 1) return fail(IBL_EHIP, "no occupancy for the layered BP kernel");
+  if ((rc = refuse_private(priv, "the layered BP kernel has a ",
+                           "-byte private segment (register spill): rebuild required")))
+    return rc;
+  h->bpc = bpc;
+  *out = h.release();
+  return IBL_OK;
+}
+
+int ibl_layered_is_bp(const ibl_layered* h, int32_t* bp) {
+  if (!h || !bp) return fail(IBL_EINVAL, "NULL argument");
+  *bp = h->bp;
+  return IBL_OK;
+}
+
 int ibl_layered_is_fixed(const ibl_layered* h, int32_t* fixed) {
   if (!h || !fixed) return fail(IBL_EINVAL, "NULL argument");
   *fixed = h->fixed;
@@ -356,6 +491,7 @@ int ibl_layered_set_compaction(ibl_layered* h, int32_t every, int32_t min_free_p
   if (every < 0 || (every > 0 && (min_free_pct < 1 || min_free_pct > 100)))
     return fail(IBL_EINVAL, "every must be >= 0 (0: off) and min_free_pct lie in [1, 100]");
   if (!h) return fail(IBL_EINVAL, "decoder is NULL");
+  if (h->bp) return fail(IBL_EUNSUPPORTED, "compaction is not built for the BP decoder");
   if (h->fixed) return fail(IBL_EUNSUPPORTED, "compaction is not built for the fixed-point decoder");
   if (h->fused) return fail(IBL_EUNSUPPORTED, "compaction needs the per-layer path");
   if (every == 0) {
@@ -382,6 +518,7 @@ int ibl_layered_set_compaction(ibl_layered* h, int32_t every, int32_t min_free_p
 
 int ibl_layered_compaction_stats(const ibl_layered* h, void* stream, int32_t* compactions, int32_t* extent) {
   if (!h || !compactions || !extent) return fail(IBL_EINVAL, "NULL argument");
+  if (h->bp) return fail(IBL_EUNSUPPORTED, "compaction is not built for the BP decoder");
   if (h->fixed) return fail(IBL_EUNSUPPORTED, "compaction is not built for the fixed-point decoder");
   if (h->fused) return fail(IBL_EUNSUPPORTED, "compaction needs the per-layer path");
   *compactions = 0;
@@ -435,6 +572,9 @@ int ibl_layered_decode(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int
   const ibl_graph* g = h->g;
   hipStream_t s = (hipStream_t)stream;
   HIPCHK(hipSetDevice(g->device));
+  if (h->bp)
+    return (h->fused ? layered_run_bp_fused : layered_run_bp_passes)(
+        h, static_cast<const float*>(d_llr), B, static_cast<float*>(d_out), early_stop, d_iters, s);
   if (!h->fused)
     return layered_decode_passes(h, static_cast<const float*>(d_llr), B, static_cast<float*>(d_out), early_stop,
                                  d_iters, s);

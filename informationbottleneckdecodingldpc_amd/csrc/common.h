@@ -433,6 +433,17 @@ hipError_t launch_lay_stage_out_c(const LayPassArgs& a, const LayCompactArgs& c,
 hipError_t launch_lay_compact(const LayPassArgs& a, const LayCompactArgs& c, uint32_t* PO, hipStream_t s);
 hipError_t lay_compact_private_bytes(size_t* bytes);
 
+// Layered BP (layered_bp_kernels.hip; include/ibldpc.h "Layered BP"). The fused kernel takes LayeredArgs (alpha and
+// beta unused; cw_bytes = 4 N + 4 E; task / idx of layered_plan.h LayeredBpPlan). The per-layer kernels take
+// LayPassArgs with M1 = R [E][ldb], the check messages, a row per CSR edge; M2 and PS repeat that pointer (the
+// shared syndrome / finalise / stage-out launchers ask for non-null ones and read neither).
+hipError_t laybp_fused_occupancy(int cw_per_group, size_t lds, int* blocks_per_cu, size_t* private_bytes);
+hipError_t launch_laybp_fused(const LayeredArgs& a, int grid, size_t lds, hipStream_t s);
+hipError_t launch_laybp_stage_in(const LayPassArgs& a, const float* llr, int imax, hipStream_t s);
+// first: the first iteration's form, which takes R = 0 without reading it
+hipError_t launch_laybp_layer(const LayPassArgs& a, bool first, int slot0, int n_checks, hipStream_t s);
+hipError_t laybp_pass_private_bytes(size_t* bytes);
+
 // Fixed-point per-layer path (include/ibldpc.h "Layered min-sum, fixed point"): a lane owns 4 consecutive
 // codewords, rows [row][ldb] with ldb = ntiles4 * 256 (layered_plan.h "fixed point"). The masks, the packed hard
 // decisions, `running`, `rec` and `cols` are those of LayPassArgs, per 64 codewords, so the packed syndrome and the

@@ -25,6 +25,7 @@
 #include <type_traits>
 
 #include "common.h"
+#include "boxplus.h"
 
 namespace ibl {
 
@@ -108,20 +109,7 @@ __device__ __forceinline__ double boxplus(double a, double b, double lm) {
   const double boxp = log((1.0 + exp(a + b)) / (exp(a) + exp(b)));
   return clampllr(boxp, lm);
 }
-// fp32: |a [+] b| = min(|a|,|b|) + ln(1 + e^-(|a|+|b|)) - ln(1 + e^-||a|-|b||)  (>= 0), sign =
-// sgn(a) sgn(b). Evaluated on the hardware base-2 exp/log (v_exp_f32 / v_log_f32, ~1 ulp): no
-// range reduction or denormal fix-ups, 4 transcendentals + ~12 VALU per operation. a or b = 0
-// gives sum == dif, so the two log terms cancel exactly and the result is 0, as in the reference.
-__device__ __forceinline__ float boxplus(float a, float b, float lm) {
-  constexpr float kLog2e = 1.4426950408889634f, kLn2 = 0.6931471805599453f;
-  const float aa = fabsf(a), ab = fabsf(b);
-  const float mn = fminf(aa, ab);
-  const float u = __builtin_amdgcn_exp2f(-(aa + ab) * kLog2e);
-  const float v = __builtin_amdgcn_exp2f(-fabsf(aa - ab) * kLog2e);
-  float mag = fmaf(kLn2, __builtin_amdgcn_logf(1.f + u) - __builtin_amdgcn_logf(1.f + v), mn);
-  mag = __builtin_amdgcn_fmed3f(mag, 0.f, lm);  // rounding may leave -ulp for tiny min; clamp to [0, lm] (:69)
-  return ((a < 0.f) != (b < 0.f)) ? -mag : mag;
-}
+// the fp32 box-plus, boxplus(float, float, lm): boxplus.h (shared with the layered BP kernels)
 
 __device__ __forceinline__ bool fl_gate(const int32_t* gate, int lane) {
   if (!gate) return true;

@@ -5,8 +5,9 @@
 // (tests/test_cpu_layered.py), tests/asan/layered_pass_plan_check.cpp (tests/test_cpu_layered_passes.py),
 // tests/asan/layered_fixed_plan_check.cpp (tests/test_cpu_layered_fixed.py),
 // tests/asan/layered_compact_plan_check.cpp (tests/test_cpu_layered_compact.py),
-// tests/asan/layered_wide_plan_check.cpp (tests/test_cpu_layered_wide.py) and
-// tests/asan/layered_fixed_fused_plan_check.cpp (tests/test_cpu_layered_fixed_fused.py).
+// tests/asan/layered_wide_plan_check.cpp (tests/test_cpu_layered_wide.py),
+// tests/asan/layered_fixed_fused_plan_check.cpp (tests/test_cpu_layered_fixed_fused.py) and
+// tests/asan/layered_bp_plan_check.cpp (tests/test_cpu_layered_bp.py).
 //
 // A layer is a set of checks no two of which share a variable; the layers are disjoint, cover every check and
 // are decoded in order (include/ibldpc.h "Layered min-sum"). The device plan cuts every layer into tasks of up
@@ -19,6 +20,7 @@
 
 #include <algorithm>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace ibl {
@@ -218,6 +220,78 @@ inline void plan_layered_passes(int32_t n_c, const int32_t* indptr, int32_t n_la
       pl->rec.push_back(indptr[c + 1] - indptr[c]);
     }
   }
+}
+
+// ---- layered BP (include/ibldpc.h "Layered BP"; layered_bp_kernels.hip; checked by
+// tests/asan/layered_bp_plan_check.cpp) ---------------------------------------------------------------------------
+// BP keeps the check messages R whole: one fp32 word per edge and codeword next to P. Check degrees 2..kLayBpMaxD.
+constexpr int kLayBpMaxD = 16;
+
+// the first check whose degree the BP kernels have no body for, or -1. Precondition: a valid indptr.
+inline int32_t laybp_unsupported_check(int32_t n_c, const int32_t* indptr) {
+  for (int32_t c = 0; c < n_c; ++c) {
+    const int32_t d = indptr[c + 1] - indptr[c];
+    if (d < kLayMinD || d > kLayBpMaxD) return c;
+  }
+  return -1;
+}
+// LDS bytes one codeword occupies in the fused kernel: P (4 N) and R (4 E)
+inline size_t laybp_cw_bytes(int32_t n_v, int64_t n_e) { return (size_t)4 * (size_t)n_v + (size_t)4 * (size_t)n_e; }
+// Codewords a workgroup keeps on chip (one wave each): 0 = the code does not fit.
+inline int32_t laybp_cw_per_group(int32_t n_v, int64_t n_e) {
+  return (int32_t)std::min<size_t>((size_t)kLayMaxCw, (size_t)kLayLds / laybp_cw_bytes(n_v, n_e));
+}
+
+// The fused kernel's plan: the tasks and variable indices of plan_layered (idx rows padded to 64 lanes), a task's
+// fourth word being the first R word of the task instead of a state slot: edge k of lane i of a task has its
+// message at R[rfirst + count k + i] — rows of `count` words, not 64, so R is exactly E words, the words a task
+// touches for one k are consecutive, and the tasks' ranges tile [0, E) in task order.
+struct LayeredBpPlan {
+  std::vector<int32_t> task;   // per task {first idx, count (1..64), degree, first R word}
+  std::vector<int32_t> idx;    // variable of edge k of lane i of a task at [first + 64 k + i]; padding 0
+  int32_t n_tasks = 0, cw_per_group = 0;
+  int64_t n_e = 0;
+  size_t cw_bytes = 0;
+};
+// Precondition: validate_layers(...) == 0 and laybp_unsupported_check(...) < 0.
+inline void plan_layered_bp(int32_t n_v, int32_t n_c, const int32_t* indptr, const int32_t* cols, int32_t n_layers,
+                            const int32_t* layer_ptr, const int32_t* layer_checks, LayeredBpPlan* pl) {
+  LayeredPlan ms;
+  plan_layered(n_v, n_c, indptr, cols, n_layers, layer_ptr, layer_checks, &ms);
+  pl->task = std::move(ms.task);
+  pl->idx = std::move(ms.idx);
+  pl->n_tasks = ms.n_tasks;
+  int64_t r = 0;
+  for (int32_t t = 0; t < pl->n_tasks; ++t) {
+    pl->task[(size_t)4 * t + 3] = (int32_t)r;
+    r += (int64_t)pl->task[(size_t)4 * t + 1] * pl->task[(size_t)4 * t + 2];
+  }
+  pl->n_e = r;   // == indptr[n_c]: every check is in one task
+  pl->cw_bytes = laybp_cw_bytes(n_v, r);
+  pl->cw_per_group = laybp_cw_per_group(n_v, r);
+}
+
+// Per-layer path: the records and layer slots are plan_layered_passes' (rec = {CSR offset, degree} per slot); the
+// message of edge k of the check in a slot is row rec[2 slot] + k of R [E][ldb], the CSR edge itself. Byte sizes of
+// the device scratch a handle of max_batch owns: about 4 N + 4 E bytes per codeword.
+struct LayeredBpBytes {
+  size_t P = 0;       // [n_v][ldb] fp32
+  size_t R = 0;       // [E][ldb] fp32
+  size_t mask = 0;    // each of finished, unsatisfied: one 64-bit word per tile
+  size_t counter = 0;
+  size_t bits = 0;    // packed hard decisions: one 64-bit word per variable and tile
+  size_t total = 0;   // P + R + 2 mask + counter + bits
+};
+inline LayeredBpBytes laybp_pass_bytes(int32_t n_v, int64_t n_e, int32_t max_batch) {
+  LayeredBpBytes b;
+  const size_t ldb = (size_t)pass_ldb(max_batch);
+  b.P = (size_t)4 * (size_t)n_v * ldb;
+  b.R = (size_t)4 * (size_t)n_e * ldb;
+  b.mask = (size_t)8 * (size_t)pass_tiles(max_batch);
+  b.counter = 4;
+  b.bits = (size_t)8 * (size_t)n_v * (size_t)pass_tiles(max_batch);
+  b.total = b.P + b.R + 2 * b.mask + b.counter + b.bits;
+  return b;
 }
 
 // ---- compaction of the running codewords, fp32 per-layer path (include/ibldpc.h "Layered min-sum", compaction;

@@ -517,6 +517,47 @@ class LayeredDecoder:
             self._h = None
 
 
+class LayeredBPDecoder:
+    """Layered (row-serial) belief-propagation decoder, fp32 (``ibl_layered_create_bp``; semantics in
+    include/ibldpc.h "Layered BP"): the schedule, layers and per-codeword early stop of :class:`LayeredDecoder`
+    with the box-plus check update of the flooding fp32 BP decoder. ``path``: ``"fused"`` (default) the on-chip
+    kernel, one wave per codeword with its APP values and one fp32 message per edge in LDS (4 N + 4 E bytes a
+    codeword, up to 8 codewords a workgroup); ``"passes"`` per-layer kernels over HBM for codes of any length
+    (``codes.dvbs2_layers`` for DVB-S2; about 4 N + 4 E bytes per codeword of ``max_batch``: 1.17 MB for DVB-S2
+    rate 1/2); ``"auto"`` the fused kernel when the codeword fits. Both paths give the same bits.
+    Check degrees 2..16. Raises :class:`_lib.IBLError` (``IBL_EUNSUPPORTED``) for a check above degree 16 and when
+    ``path="fused"`` and a codeword does not fit in LDS. There is no compaction."""
+
+    _PATHS = LayeredDecoder._PATHS
+
+    def __init__(self, graph: Graph, layers, imax: int, max_batch: int, llr_max: float = 150.0, path: str = "fused",
+                 precision=torch.float32):
+        if path not in self._PATHS:
+            raise ValueError('path must be "fused", "passes" or "auto"')
+        self.path = path
+        self.graph = graph
+        self.imax = int(imax)
+        self.max_batch = int(max_batch)
+        self.llr_max = float(llr_max)
+        self.device = graph.device
+        if precision not in _DT_FL:
+            raise ValueError("precision must be torch.float32 (float64 is refused by the library)")
+        nl, ptr, chk = _lib.pack_layers(layers)
+        if chk.size == 0:
+            chk = np.zeros(1, np.int32)
+        self.n_layers = nl
+        h = ctypes.c_void_p()
+        _lib.check(_lib.load().ibl_layered_create_bp(graph.handle, nl, ptr, chk, self.imax, self.llr_max,
+                                                     _DT_FL[precision], self.max_batch, self._PATHS[path],
+                                                     ctypes.byref(h)), "ibl_layered_create_bp")
+        self._h = h
+
+    path_in_use = LayeredDecoder.path_in_use
+    geometry = LayeredDecoder.geometry
+    decode = LayeredDecoder.decode
+    __del__ = LayeredDecoder.__del__
+
+
 class LayeredFixedDecoder:
     """Layered min-sum in fixed point (``ibl_layered_create_fixed``; semantics in include/ibldpc.h "Layered
     min-sum, fixed point"): 8-bit APP values, messages saturated at ``q_max``, magnitudes corrected as

@@ -38,6 +38,8 @@ from .engine import LayeredDecoder, LayeredFixedDecoder, count_below
 
 class Min_Sum_Layered_Decoder_class_irregular(CodeMixin):
 
+    _DECODER_NAME = "layered min-sum"   # in messages; the layered BP subclass names itself
+
     def __init__(self, filename, imax_, cardinality_T_channel_, msg_at_time_, *, layers=None, Z=None,
                  alpha: float = 1.0, beta: float = 0.0, llr_max: float = 150.0, path: str = "fused",
                  fixed: bool = False, scale: float = 2.0, q_max: int = 31, compact=None):
@@ -101,7 +103,7 @@ class Min_Sum_Layered_Decoder_class_irregular(CodeMixin):
         if not return_buffer and not bool(torch.isfinite(llr).all().item()):
             # host output synchronises anyway: the decoder's precondition is checked instead of returning
             # unspecified values
-            raise ValueError("channel LLRs must be finite (layered min-sum precondition)")
+            raise ValueError(f"channel LLRs must be finite ({self._DECODER_NAME} precondition)")
         iters = torch.empty(llr.shape[1], dtype=torch.int32, device=self.device)
         out = self._dec.decode(llr, early_stop=early_stop, iters=iters)
         self.last_iterations = iters
