@@ -1,6 +1,8 @@
 """CPU: the layered BP decoder's specification and host side (include/ibldpc.h "Layered BP") — the numpy
 restatement against an independent scalar one, its float32 form against its float64 form, the instability of the
-min-sum clamp rule that the specification avoids, the named inputs of the GPU tests, the new C ABI names, the
+min-sum clamp rule that the specification avoids, the named inputs of the GPU tests and the premises of
+tests/test_gpu_layered_bp_edges.py (nonzero codewords with a spread of stops, what the all-zero inputs cannot see,
+the two clamps, exact ties), the new C ABI names, the
 drop-in class's refusals, the host plan under AddressSanitizer / UndefinedBehaviorSanitizer as a stand-alone program
 (tests/asan/layered_bp_plan_check.cpp; nothing loaded into Python is sanitized), and the private segments of the
 new kernels in the built code object."""
@@ -132,6 +134,288 @@ def test_named_inputs_meet_their_conditions():
     assert int(exc_w.sum()) <= br.excuse_cap(32)
     _, _, exc_w27 = wlan_reference(27, 20, True)
     assert int(exc_w27.sum()) <= br.excuse_cap(32)
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# the premises of tests/test_gpu_layered_bp_edges.py
+# ---------------------------------------------------------------------------------------------------------------
+# iterations of the float64 reference on tests/_codewords.py layered_input(name), B = 130, i_max 8, llr_max 150
+SPREAD_HIST = {"wlan": [0, 63, 39, 13, 3, 3, 1, 0, 8], "mixed": [0, 84, 21, 6, 4, 3, 0, 1, 11],
+               "dvb": [0, 2, 92, 6, 21, 1, 0, 0, 8]}
+SPREAD_CONVERGED = {"wlan": 122, "mixed": 119, "dvb": 122}
+
+
+def _findings(label, res, ref):
+    print(f"{label}: H5 violations {int(res['bad'].sum())} in columns "
+          f"{np.flatnonzero(res['bad'].any(axis=0)).tolist()}, "
+          f"hard flips {res['flips']}, iters differ at {np.flatnonzero(res['differ']).tolist()} (excusable "
+          f"{np.flatnonzero(ref[2]).tolist()}), reference iters {np.bincount(ref[1]).tolist()}")
+
+
+@pytest.mark.parametrize("name", ["wlan", "mixed", "dvb"])
+def test_spread_batches(name):
+    """br.spread_input: nonzero codewords at two noise levels, the all-zero codeword and sign-random noise
+    (tests/_codewords.py layered_input; on wlan the noise columns at half magnitude, see
+    test_spread_inputs_bear_one_ulp_transcendentals), B = 130: the float64 reference stops at four or more distinct
+    iterations, never stops a noise column and decides the transmitted bits on every column it converges. The float32 form against it under
+    br.compare_columns: no value outside H5, no hard flip, iters unequal on excusable columns only and within the
+    cap of 3 (measured: 0, 1 and 0 columns on wlan, mixed and dvb). On mixed that one column (1) stops an iteration
+    apart; against the reference's FROZEN values it shows 398 entries outside H5, which is why compare_columns
+    takes the reference's values at the decoder's own stop iteration."""
+    from tests import _codewords as cw
+    H, _, layers, _ = cw.code(name)
+    llr, bits, kinds = br.spread_input(name)
+    ref = br.spread_reference(name)
+    out, it, exc, P_at, conv = ref
+    imax = cw.IMAX_LAYERED
+    same = np.array_equal(llr, cw.layered_input(name)[0])
+    assert same == (name != "wlan") and np.array_equal(llr[:, kinds != cw.KIND_NOISE],
+                                                       cw.layered_input(name)[0][:, kinds != cw.KIND_NOISE])
+    assert imax == 8 and P_at.shape == (imax,) + llr.shape and llr.shape[1] == 130
+    if not same:       # the stops are those of layered_input as it is: its noise columns never stop either
+        assert np.array_equal(br.layered_bp_decode(H, layers, cw.layered_input(name)[0], imax)[1], it)
+    hist = np.bincount(it, minlength=imax + 1).tolist()
+    print(f"{name}: reference iters {hist}, converged {int(conv.sum())}, excusable {np.flatnonzero(exc).tolist()}")
+    assert hist == SPREAD_HIST[name] and int(conv.sum()) == SPREAD_CONVERGED[name]
+    assert len(set(it[conv].tolist())) >= 4
+    assert (kinds == cw.KIND_NOISE).sum() == 8 and (it[kinds == cw.KIND_NOISE] == imax).all()
+    assert not conv[kinds == cw.KIND_NOISE].any()
+    assert np.array_equal((out < 0)[:, conv], (bits == 1)[:, conv])
+    assert bits[:, conv].any(axis=0).sum() >= 100          # nonzero codewords among the converged
+    # the recorded values are the frozen ones at each column's stop iteration
+    assert all(np.array_equal(P_at[it[b] - 1][:, b], out[:, b]) for b in range(130))
+    # odd tiles hold early stoppers only: whole-tile skips beside running tiles
+    assert (it[64:128] <= 4).all() and (it[:64] == imax).any()
+    o32, i32 = br.layered_bp_decode(H, layers, llr, imax, dtype=np.float32)
+    res = br.compare_columns(o32, i32, ref)
+    _findings(f"{name} float32 form", res, ref)
+    assert not res["bad"].any() and res["flips"] == 0 and not res["unexcused"].any()
+    assert res["excused"] <= br.excuse_cap(130) == 3
+    if name == "mixed":
+        assert np.flatnonzero(res["differ"]).tolist() == [1]
+        frozen = br.h5_violations(o32, out)
+        assert frozen[:, 1].sum() > 100 and not np.delete(frozen, 1, axis=1).any()
+
+
+def _worst_share_of_h5(x, ref):
+    """max over the rows of |x - ref| / (H5's bound), per column."""
+    x, ref = np.asarray(x, np.float64), np.asarray(ref, np.float64)
+    return (np.abs(x - ref) / (br.REL * np.maximum(np.abs(x), np.abs(ref)) + br.TOL_ABS)).max(axis=0)
+
+
+@pytest.mark.parametrize("name,draws", [("wlan", 4), ("mixed", 2), ("dvb", 1)])
+def test_spread_inputs_bear_one_ulp_transcendentals(name, draws):
+    """Whether an input can be held to H5 on EVERY column for 8 iterations is a property of the input: the float32
+    form with each transcendental moved by up to 1 ulp at random (br.one_ulp: the hardware's exp2 and log2 are good
+    to about 1 ulp, numpy's are not the only legitimate ones) must stay well inside H5, stop off, i_max 8. It stays
+    below 0.7 of the bound on br.spread_input (measured: wlan 0.10, mixed 0.25, dvb 0.52; the noise columns 0.02,
+    0.07, 0.52). On tests/_codewords.py layered_input("wlan") as it is it does not: the noise columns, which never
+    converge, double a rounding difference every iteration and leave H5 by iteration 8 (draws 0 and 1: 1.44 and
+    1.34 times the bound; an MI355X: 1.24 times, on column 43), every other column stays at 0.1 of it or below.
+    That is why spread_input halves those columns on wlan (seed and Eb/N0 are unchanged)."""
+    from tests import _codewords as cw
+    H, _, layers, _ = cw.code(name)
+    llr, _, kinds = br.spread_input(name)
+    noise = kinds == cw.KIND_NOISE
+    want = br.layered_bp_decode(H, layers, llr, cw.IMAX_LAYERED, early_stop=False)[0]
+    for draw in range(draws):
+        got = br.layered_bp_decode(H, layers, llr, cw.IMAX_LAYERED, early_stop=False, dtype=np.float32,
+                                   ulp=br.one_ulp(np.random.default_rng(draw)))[0]
+        share = _worst_share_of_h5(got, want)
+        print(f"{name} draw {draw}: worst share of H5's bound {share.max():.2f}, on the noise columns "
+              f"{share[noise].max():.2f}")
+        assert share.max() < 0.7
+    if name == "wlan":
+        assert (share[noise] < 0.05).all()
+        full = cw.layered_input("wlan")[0]
+        want = br.layered_bp_decode(H, layers, full, cw.IMAX_LAYERED, early_stop=False)[0]
+        for draw in range(2):
+            got = br.layered_bp_decode(H, layers, full, cw.IMAX_LAYERED, early_stop=False, dtype=np.float32,
+                                       ulp=br.one_ulp(np.random.default_rng(draw)))[0]
+            share = _worst_share_of_h5(got, want)
+            print(f"layered_input(wlan) draw {draw}: noise columns {np.round(share[noise], 2).tolist()}, others "
+                  f"{share[~noise].max():.2f}")
+            assert share[noise].max() > 1.0 and share[~noise].max() < 0.15
+
+
+def test_compare_columns_rule():
+    """A decoder that is the reference itself passes; one column moved to another iteration's values passes only
+    when that column is excusable and its iters says so; a non-excusable column is judged against the frozen
+    values whatever its iters."""
+    out, it, exc, P_at, _ = br.spread_reference("mixed")
+    ref = (out, it, exc, P_at)
+    res = br.compare_columns(out, it, ref)
+    assert not res["bad"].any() and res["flips"] == 0 and not res["differ"].any() and res["excused"] == 0
+    b = int(np.flatnonzero(exc)[0])
+    other = int(it[b]) - 1 if it[b] == 8 else int(it[b]) + 1
+    o2, i2 = out.copy(), it.copy()
+    o2[:, b], i2[b] = P_at[other - 1][:, b], other
+    res = br.compare_columns(o2, i2, ref)
+    assert not res["bad"].any() and res["excused"] == 1 and not res["unexcused"].any()
+    res = br.compare_columns(o2, it, ref)                      # the values moved, iters does not say so
+    assert res["bad"][:, b].any() and not res["differ"].any()
+    res = br.compare_columns(out, i2, ref)                     # iters moved, the values did not
+    assert res["bad"][:, b].any()
+    c = int(np.flatnonzero(~exc & (it < 7))[0])
+    o3, i3 = out.copy(), it.copy()
+    o3[:, c], i3[c] = P_at[it[c]][:, c], it[c] + 1
+    res = br.compare_columns(o3, i3, ref)
+    assert res["unexcused"][c] and res["bad"][:, c].any()
+    assert np.array_equal(br.reference_for_columns(i3, (out, it, exc)), out)     # without P_at: as before
+
+
+@pytest.mark.parametrize("rule", br.WRONG_STOP_RULES)
+def test_wrong_stop_rules_pass_all_zero_and_fail_on_the_spread_batch(rule):
+    """The reference with a wrong stop rule ("no decision is 1"; the syndrome gathered through variable v - 1): on
+    the all-zero inputs of tests/test_gpu_layered_bp.py, wlan_input(27) at i_max 20 and dvb_input() at i_max 10,
+    its iteration counts are those of the true rule, so no test on those inputs would notice; on the spread batch
+    of the WLAN code (and of mixed) they differ on columns that are not excusable: every nonzero codeword the
+    reference converges before i_max (measured: 114 of 130 on wlan, 111 on mixed, for both rules)."""
+    from tests import _codewords as cw
+    zero_inputs = (("wlan_input(27)", wlan_input(27), 20, wlan_reference(27, 20, True)[1]),
+                   ("dvb_input()", dvb_input(), 10, dvb_reference(10, True)[1]))
+    for what, (H, layers, llr), imax, true_it in zero_inputs:
+        _, wrong_it = br.layered_bp_decode(H, layers, llr, imax, stop_rule=rule)
+        print(f"{rule.__name__} on {what}: {np.bincount(wrong_it).tolist()} (true rule "
+              f"{np.bincount(true_it).tolist()})")
+        assert len(set(true_it.tolist())) >= 4 and np.array_equal(wrong_it, true_it)
+    for name in ("wlan", "mixed"):
+        H, _, layers, _ = cw.code(name)
+        llr, bits, kinds = br.spread_input(name)
+        _, it, exc, _, conv = br.spread_reference(name)
+        _, wrong_it = br.layered_bp_decode(H, layers, llr, cw.IMAX_LAYERED, stop_rule=rule)
+        differ = wrong_it != it
+        print(f"{rule.__name__} on layered_input({name}): {int(differ.sum())} of 130 counts differ, "
+              f"{int((differ & ~exc).sum())} of them not excusable")
+        nonzero = bits.any(axis=0) & cw.converged(it)
+        assert (differ & ~exc).sum() >= 1 and differ[nonzero].all() and nonzero.sum() >= 100
+        assert np.array_equal(wrong_it[kinds == cw.KIND_ZERO], it[kinds == cw.KIND_ZERO])
+
+
+def _clamp_census(H, layers, llr, imax, L):
+    """Instruments the reference: per check update of a running codeword, in iterations that are run."""
+    n = dict(deg2_beyond=0, two_beyond=0)
+
+    def seen(it, Q, done):
+        beyond = (np.abs(Q) > L)[:, :, ~done]
+        if Q.shape[1] == 2:
+            n["deg2_beyond"] += int(beyond.any(axis=1).sum())
+        else:
+            n["two_beyond"] += int((beyond.sum(axis=1) >= 2).sum())
+
+    br.layered_bp_decode(H, layers, llr, imax, llr_max=L, check_hook=seen)
+    return n
+
+
+@pytest.mark.parametrize("name", ["mixed", "wlan"])
+def test_saturating_input_meets_both_clamps(name):
+    """br.saturating_input (seed 22, 3 dB: nothing had to be changed to meet the premises). Counted in the
+    reference: a degree-2 check with |Q| > llr_max (mixed; the WLAN code has no check of degree 2) and a check of
+    degree >= 3 with two |Q| > llr_max, on running codewords. The reference without the degree-2 clamp, and
+    separately without the box-plus's upper clamp, leaves H5 on a column the true reference converges (measured:
+    on all 15 of them). The reference converges 15 of 16 columns at a spread of stops and decides their bits; the
+    float32 form is within H5 with no flip on those, finite everywhere, and within H5 on every column after one
+    iteration — also when the huge entries take random signs. Two entries of 2^126 in one box-plus leave
+    (|a| + |b|) log2(e) = 2.45e38 finite; "overflow" is the same input with 2^127 for 2^126, still inside the
+    precondition, where |a| + |b| is inf in fp32: same stops, same bars."""
+    H, layers, C = br.edge_code(name)
+    llr = br.saturating_input(name)
+    assert (np.abs(llr) == br.HUGE).sum() >= 64 and (np.abs(llr) == 150).sum() >= 64
+    assert float(br.HUGE) + 16 * 150.0 < np.finfo(np.float32).max
+    assert float(br.HUGE_INF) + 16 * 150.0 < np.finfo(np.float32).max
+    with np.errstate(over="ignore"):
+        assert np.isfinite((br.HUGE + br.HUGE) * np.float32(1.4426950408889634)) and np.isinf(br.HUGE_INF + br.HUGE_INF)
+    out, it, exc, _, conv = br.edge_reference("saturating", name, br.EDGE_IMAX, True)
+    census = _clamp_census(H, layers, llr, br.EDGE_IMAX, 150.0)
+    print(f"{name} saturating: reference iters {np.bincount(it).tolist()}, converged {int(conv.sum())} of 16, "
+          f"excusable {np.flatnonzero(exc).tolist()}, {census}")
+    assert int(conv.sum()) == 15 and len(set(it[conv].tolist())) >= 3
+    assert np.array_equal((out < 0)[:, conv], (C == 1)[:, conv])
+    assert census["two_beyond"] > 0
+    variants = [dict(clamp_boxplus=False)]
+    if name == "mixed":
+        assert census["deg2_beyond"] > 0
+        variants.append(dict(clamp_deg2=False))
+    else:
+        assert 2 not in np.diff(sp.csr_matrix(H).indptr)
+    for kw in variants:
+        v_out, _ = br.layered_bp_decode(H, layers, llr, br.EDGE_IMAX, **kw)
+        hit = br.h5_violations(v_out, out).any(axis=0) & conv
+        print(f"   {kw}: outside H5 on converged columns {np.flatnonzero(hit).tolist()}")
+        assert hit.any()
+    for kind in ("saturating", "overflow"):
+        x = br.edge_input(kind, name)
+        k_out, k_it, _, _, k_conv = br.edge_reference(kind, name, br.EDGE_IMAX, True)
+        assert int(k_conv.sum()) == 15 and np.array_equal(k_it, it)
+        o32, i32 = br.layered_bp_decode(H, layers, x, br.EDGE_IMAX, dtype=np.float32)
+        assert np.isfinite(o32).all() and np.array_equal(i32, k_it)
+        assert not br.h5_violations(o32, k_out)[:, k_conv].any()
+        assert not ((o32 < 0) != (k_out < 0))[:, k_conv].any()
+    for kind in ("saturating", "overflow", "frustrated"):
+        first = br.edge_reference(kind, name, 1, True)
+        o1, i1 = br.layered_bp_decode(H, layers, br.edge_input(kind, name), 1, dtype=np.float32)
+        res = br.compare_columns(o1, i1, first)
+        assert not res["bad"].any() and res["flips"] == 0 and not res["differ"].any()
+    huge = np.abs(llr) == br.HUGE
+    signs = np.sign(br.saturating_input(name, True))[huge] * np.where(C == 1, -1, 1)[huge]
+    assert (signs < 0).sum() >= 16 and (signs > 0).sum() >= 16
+
+
+def test_small_llr_max_and_quantised_inputs():
+    """br.small_llr_max_input (mixed, 2 dB, llr_max 7.5): the reference stops at several iterations and the float32
+    form is within the bars on every column. br.quantised_input: zeros of either sign; with the stop on every
+    column of mixed is excusable (iters unconstrained), so the GPU test runs it with the stop off."""
+    H, layers, C = br.edge_code("mixed")
+    ref = br.edge_reference("small_llr_max", "mixed", br.EDGE_IMAX, True, br.SMALL_LLR_MAX)
+    out, it, exc, _, conv = ref
+    print(f"small llr_max: reference iters {np.bincount(it).tolist()}, converged {np.flatnonzero(conv).tolist()}, "
+          f"excusable {np.flatnonzero(exc).tolist()}")
+    assert len(set(it[conv].tolist())) >= 3 and 1 <= (~conv).sum() and np.abs(out).max() > br.SMALL_LLR_MAX
+    assert np.array_equal((out < 0)[:, conv], (C == 1)[:, conv])
+    o32, i32 = br.layered_bp_decode(H, layers, br.small_llr_max_input(), br.EDGE_IMAX, llr_max=br.SMALL_LLR_MAX,
+                                    dtype=np.float32)
+    res = br.compare_columns(o32, i32, ref)
+    assert not res["bad"].any() and res["flips"] == 0 and not res["unexcused"].any() and res["excused"] <= 1
+    for name in ("mixed", "wlan"):
+        q = br.quantised_input(name)
+        assert (np.signbit(q) & (q == 0)).sum() >= 100 and (~np.signbit(q) & (q == 0)).sum() >= 100
+        assert np.array_equal(q, np.rint(q))
+        on = br.edge_reference("quantised", name, br.EDGE_IMAX, True)
+        off = br.edge_reference("quantised", name, br.EDGE_IMAX, False)
+        print(f"quantised {name}: excusable with the stop on {int(on[2].sum())} of 16")
+        assert not off[2].any() and (off[1] == br.EDGE_IMAX).all()
+        o32, i32 = br.layered_bp_decode(*br.edge_code(name)[:2], q, br.EDGE_IMAX, early_stop=False, dtype=np.float32)
+        res = br.compare_columns(o32, i32, off)
+        assert not res["bad"].any() and not res["differ"].any()
+    assert br.edge_reference("quantised", "mixed", br.EDGE_IMAX, True)[2].all()
+
+
+def test_ties_in_the_first_iteration():
+    """The WLAN spread batch's LLRs are 16 levels at either noise level, their halves on the noise columns, and
+    their negatives: box-pluses of iteration 1 meet |a| == |b| exactly (counted in the reference), and so do those
+    of the quantised inputs."""
+    from tests import _codewords as cw
+    H, _, layers, _ = cw.code("wlan")
+    llr, _, kinds = br.spread_input("wlan")
+    assert np.unique(np.abs(llr[:, kinds != cw.KIND_NOISE])).size <= 32
+    for what, x, Hc, lay in (("wlan spread", llr, H, layers),
+                             ("quantised mixed", br.quantised_input("mixed"), *br.edge_code("mixed")[:2])):
+        n = dict(ties=0, nonzero_ties=0, boxplus=0)
+
+        def seen(it, Q, done):
+            if it != 1 or Q.shape[1] == 2:
+                return None
+
+            def on(a, b):
+                tie = np.abs(a) == np.abs(b)
+                n["ties"] += int(tie.sum())
+                n["nonzero_ties"] += int((tie & (a != 0)).sum())
+                n["boxplus"] += tie.size
+            return on
+
+        br.layered_bp_decode(Hc, lay, x, 1, check_hook=seen)
+        print(f"{what}: {n}")
+        assert n["nonzero_ties"] >= 1 and n["boxplus"] > n["ties"]
 
 
 # ---------------------------------------------------------------------------------------------------------------

@@ -2,7 +2,8 @@
 of its specification (tests/_layered_bp_ref.py). Every comparison with the reference asks that `out` is within
 SURVEY H5, that no hard decision differs outside H5's band around zero, and that `iters` is equal except on
 excusable codewords (tests/_layered_bp_ref.py reference_with_excusable), of which at most 2 % of a batch, rounded up,
-may be excused. The fused kernel and the per-layer kernels are held to IDENTICAL bits of each other."""
+may be excused; where the reference recorded its values after every iteration, an excused codeword that stopped at
+another iteration is compared with the reference's values at that iteration. The fused kernel and the per-layer kernels are held to IDENTICAL bits of each other."""
 import numpy as np
 import pytest
 import scipy.sparse as sp
@@ -29,30 +30,35 @@ def gpu_decode(dec, llr, early=True):
 
 
 def compare(got, ref, label):
-    """got = (out, iters) of a decoder, ref = (out, iters, excusable) of the reference for the same columns."""
+    """got = (out, iters) of a decoder, ref = (out, iters, excusable[, P_at, ...]) of the reference for the same
+    columns. With P_at (reference_with_excusable(record=True)) an excusable column whose iters differ is compared
+    with the reference's values at the decoder's own stop iteration (br.reference_for_columns); every other column,
+    and every column without P_at, with the reference's `out`. -> br.compare_columns' findings."""
     out, it = got
-    r_out, r_it, exc = ref
+    r_it, exc = ref[1], ref[2]
     B = out.shape[1]
-    bad = br.h5_violations(out, r_out)
-    flips = _hard_flips(out.astype(np.float64), r_out)
-    differ = it != r_it
+    res = br.compare_columns(out, it, ref)
+    bad, flips, differ, want = res["bad"], res["flips"], res["differ"], res["want"]
+    assert flips == _hard_flips(out.astype(np.float64), want)
     with np.errstate(divide="ignore", invalid="ignore"):
-        rel = np.abs(out - r_out) / np.maximum(np.abs(out), np.abs(r_out))
+        rel = np.abs(out - want) / np.maximum(np.abs(out), np.abs(want))
     print(f"{label}: B={B} H5 violations {int(bad.sum())} in columns {np.nonzero(bad.any(axis=0))[0].tolist()}, "
-          f"max |diff| {float(np.abs(out - r_out).max()):.3g}, max rel {float(np.nanmax(rel)):.3g}, hard flips {flips}, "
+          f"max |diff| {float(np.abs(out - want).max()):.3g}, max rel {float(np.nanmax(rel)):.3g}, hard flips {flips}, "
           f"iters differ at {np.nonzero(differ)[0].tolist()} (excusable {np.nonzero(exc)[0].tolist()}), "
           f"reference iters {np.bincount(r_it).tolist()}")
     assert not bad.any()
     assert flips == 0
     assert not (differ & ~exc).any()
     assert int((differ & exc).sum()) <= br.excuse_cap(B)
+    return res
 
 
 def cut(ref, B=None, cols=None):
-    out, it, exc = ref
-    if cols is not None:
-        return out[:, cols], it[cols], exc[cols]
-    return out[:, :B], it[:B], exc[:B]
+    """The reference of the first B columns, or of the columns `cols` (out, iters, excusable and, if there, P_at)."""
+    sel = slice(0, B) if cols is None else cols
+    out, it, exc = ref[:3]
+    head = (out[:, sel], it[sel], exc[sel])
+    return head + (ref[3][:, :, sel],) if len(ref) > 3 and ref[3] is not None else head
 
 
 # ---------------------------------------------------------------------------------------------------------------
