@@ -533,6 +533,70 @@ int ibl_layered_create_bp(const ibl_graph* g, int32_t n_layers, const int32_t* l
 int ibl_layered_is_bp(const ibl_layered* h, int32_t* bp);
 
 /*
+ * Layered BP, half-precision state: the "Layered BP" decoder above with its two state arrays, P and R, stored as IEEE
+ * binary16 and every operation still done in fp32.  It halves the bytes an iteration moves on the per-layer path and
+ * the LDS a codeword takes in the fused kernel.  Layers, the per-codeword early stop, iters[] and out[] are those of
+ * "Layered BP".
+ *
+ *   h(x) = round-to-nearest-even to binary16 of clamp(x, -65504, +65504)   (subnormal halves are kept)
+ *   f(y) = the exact conversion of a binary16 value to fp32
+ *
+ * Semantics, per codeword:
+ *   P[v] = h(llr[v] + 0);  R[e] = +0
+ *   for it = 1..imax:
+ *     for each layer in order, each check c of it, edges e_0..e_{D-1} in ascending column order:
+ *         Q_k    = f(P[v_k]) - f(R[e_k])               (one rounded fp32 subtraction, NOT clamped)
+ *         R'_k   : the fp32 forward-backward box-plus order of "Layered BP" on the Q_k
+ *                  (D == 2: R'_0 = clamp(Q_1), R'_1 = clamp(Q_0), the clamp to +-llr_max)
+ *         R[e_k] = h(R'_k)
+ *         P[v_k] = h(Q_k + f(R[e_k]))                   (one rounded fp32 addition, with the ROUNDED message)
+ *     early stop: as "Layered BP", on the decisions x_v = (f(P[v]) < 0) BY VALUE: h turns a tiny negative sum into
+ *       -0, which decides 0 (the fp32 decoders never hold a -0; no kernel of this decoder reads a sign bit)
+ *   out[v][b] = f(P[v]) of codeword b, frozen at its stop; iters[] as "Layered BP".
+ *   Every output value is therefore a binary16 value.
+ *   The result is defined for every finite input: the clamp in h precedes the conversion, so nothing becomes inf or
+ *   NaN.  The bound |P| <= |llr| + d_v * llr_max of "Layered BP" holds only while |llr| + 16 * llr_max <= 65504;
+ *   beyond that P saturates at +-65504, the sums above lose the other checks' contributions and the decoder no
+ *   longer decodes meaningfully.  Precondition for meaningful decoding: channel LLRs finite and
+ *   |llr| + 16 * llr_max <= 65504 (llr_max = 150: |llr| <= 63,104).
+ *   Input and output stay [N][B] IBL_F32; binary16 input and output are not built.
+ *   Supported: check degrees 2..16 (a check of degree 17 or more is IBL_EUNSUPPORTED, the message names it), variable
+ *   degrees up to 16.
+ *   Parity with this specification is by value, not bit for bit, wherever a box-plus is evaluated: the
+ *   transcendentals are the hardware's.  (A code whose checks all have degree 2 has no box-plus and is decoded bit
+ *   for bit.)  The two paths below run one check core in one operation order and give each other's bits.
+ *
+ * ibl_layered_create_bp_half  validates as ibl_layered_create_bp, in its order and with its messages (there is no
+ *   precision argument).  path:
+ *     IBL_PATH_FUSED   the fused kernel of "Layered BP" with the wave's LDS slice P16[N] | R16[E].  Fit rule:
+ *                      cw_bytes = 2 N + 2 E rounded up to 4, cw_per_group = min(8, floor(160 KiB / cw_bytes));
+ *                      IBL_EUNSUPPORTED when that is 0, the message naming "2 N + 2 E" (N = 1944 rate 1/2:
+ *                      17,820 B, 8 codewords a workgroup where the fp32 state holds 4; DVB-S2 N = 64800 does not
+ *                      fit).  The staging is the fp32 kernel's [B][N] fp32 transpose; the wave converts as it reads
+ *                      and writes its row.
+ *     IBL_PATH_PASSES  per-layer kernels over HBM: P16 [N][ldb] and R16 [E][ldb], a lane owning two consecutive
+ *                      codewords (one dword of a row), a wave updating one check for 128 codewords; ldb is max_batch
+ *                      rounded up to 128.  The masks of finished and unsatisfied codewords and the packed hard
+ *                      decisions stay per 64 codewords (mask words past the batch are all ones), the packed syndrome
+ *                      and the finalise launch are the min-sum path's, the pack of the hard decisions and the output
+ *                      launch are this decoder's.  The first iteration takes R = 0 without reading or zeroing the E
+ *                      rows.  An iteration moves 8 E bytes per codeword, the first 6 E.  The handle owns about
+ *                      2 N + 2 E bytes per codeword: DVB-S2 N = 64800 rate 1/2 583 KB per codeword, 4.8 GB at 8192.
+ *                      "No allocation, no host synchronisation, no read-back, capturable" as on every per-layer path.
+ *     IBL_PATH_AUTO    the fused kernel when the code fits by the rule above, else the per-layer kernels.
+ *   The handle is an ibl_layered: ibl_layered_decode (IBL_F32 in and out), _path_in_use, _geometry and _destroy work
+ *   as documented above; ibl_layered_is_bp gives 1, ibl_layered_is_wide and ibl_layered_is_fixed give 0;
+ *   ibl_layered_set_compaction and ibl_layered_compaction_stats return IBL_EUNSUPPORTED ("compaction is not built for
+ *   the BP decoder").
+ * ibl_layered_is_half  *half = 1 for a handle of ibl_layered_create_bp_half, 0 for every other handle; NULL arguments
+ *   are IBL_EINVAL.
+ */
+int ibl_layered_create_bp_half(const ibl_graph* g, int32_t n_layers, const int32_t* layer_ptr,
+                               const int32_t* layer_checks, int32_t imax, float llr_max, int32_t max_batch,
+                               int32_t path, ibl_layered** out);
+int ibl_layered_is_half(const ibl_layered* h, int32_t* half);
+
+/*
  * Layered min-sum, fixed point: a second arithmetic of the layered decoder above, integer throughout — 8-bit APP
  * values, messages saturated at q_max (6 bits at most) — on the per-layer path over HBM (ibl_layered_create_fixed) or fused
  * on chip for the codes that fit (ibl_layered_create_fixed_fused).  Layers, the per-codeword

@@ -12,7 +12,8 @@ CSRC = os.path.join(PKG, "csrc")
 INCLUDE = os.path.join(ROOT, "include")
 LIB = os.path.join(PKG, "libibldpc.so")
 SOURCES = ["ib_kernels.hip", "float_kernels.hip", "channel_kernels.hip", "encoder_kernels.hip", "layered_kernels.hip",
-           "layered_bp_kernels.hip", "capi_core.hip", "capi_ib.hip", "capi_float.hip", "capi_layered.hip", "capi_encoder.hip", "comm.hip"]
+           "layered_bp_kernels.hip", "layered_half_kernels.hip", "capi_core.hip", "capi_ib.hip", "capi_float.hip",
+           "capi_layered.hip", "capi_encoder.hip", "comm.hip"]
 ARCH = os.environ.get("IBLDPC_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", INCLUDE, "-I", CSRC,
@@ -31,9 +32,12 @@ FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-I", INCLUDE, 
 # values are float_kernels' under either setting. Messages are never NaN (finite inputs, a clamped box-plus), so
 # -fno-honor-nans spares the quieting v_max before every min / median of the box-plus (4 per operation). The IEEE
 # mode bit stays on: the file uses threadIdx / blockIdx, which -mno-amdgpu-ieee would turn into calls.
+# layered_half_kernels: the same check core on half-precision state (include/ibldpc.h "Layered BP, half-precision
+# state"), the same flags for the same reasons.
 SRC_FLAGS = {"float_kernels.hip": ["-fno-honor-nans", "-mno-amdgpu-ieee"],
              "layered_kernels.hip": ["-ffp-contract=off"],
-             "layered_bp_kernels.hip": ["-ffp-contract=off", "-fno-honor-nans"]}
+             "layered_bp_kernels.hip": ["-ffp-contract=off", "-fno-honor-nans"],
+             "layered_half_kernels.hip": ["-ffp-contract=off", "-fno-honor-nans"]}
 
 
 def _stale(out: str, deps) -> bool:

@@ -49,6 +49,7 @@ EXPORTS = [
     "ibl_layered_create_path", "ibl_layered_path_in_use", "ibl_layered_create_fixed", "ibl_layered_is_fixed",
     "ibl_layered_set_compaction", "ibl_layered_compaction_stats", "ibl_layered_is_wide",
     "ibl_layered_create_fixed_fused", "ibl_layered_create_bp", "ibl_layered_is_bp",
+    "ibl_layered_create_bp_half", "ibl_layered_is_half",
 ]
 IBL_COMM_ID_BYTES = 128
 
@@ -151,6 +152,8 @@ def load():
                                                  ctypes.POINTER(_vp)]
     L.ibl_layered_create_bp.argtypes = [_vp, _i32, _i32p, _i32p, _i32, _f32, _i32, _i32, _i32, ctypes.POINTER(_vp)]
     L.ibl_layered_is_bp.argtypes = [_vp, ctypes.POINTER(_i32)]
+    L.ibl_layered_create_bp_half.argtypes = [_vp, _i32, _i32p, _i32p, _i32, _f32, _i32, _i32, ctypes.POINTER(_vp)]
+    L.ibl_layered_is_half.argtypes = [_vp, ctypes.POINTER(_i32)]
     L.ibl_layered_is_fixed.argtypes = [_vp, ctypes.POINTER(_i32)]
     L.ibl_layered_is_wide.argtypes = [_vp, ctypes.POINTER(_i32)]
     L.ibl_layered_decode.argtypes =[_vp, _vp, _i32, _i32, _vp, _i32, _i32, _vp, _vp]

@@ -5,13 +5,16 @@ The reference has no layered decoder. This class subclasses the layered min-sum 
 (:mod:`.min_sum_layered_decoder_irreg`) the way the flooding BP class subclasses the flooding min-sum one: the same
 constructor shape, ``decode_OpenCL_belief_propagation`` instead of ``decode_OpenCL_min_sum``, so ``ber.run_ber``
 takes it as a BP decoder. Keyword-only extensions: ``layers``, ``Z`` and ``path`` (``"fused"``, ``"passes"``,
-``"auto"``) as the min-sum class has them, and ``llr_max``. BP has no correction, fixed-point form or compaction:
-``alpha``, ``beta``, ``fixed`` and ``compact`` raise ``ValueError``.
+``"auto"``) as the min-sum class has them, ``llr_max``, and ``state_dtype`` (``torch.float32``, the default, or
+``torch.float16``: the state kept in binary16, :class:`.engine.LayeredBPDecoder`). BP has no correction, fixed-point
+form or compaction: ``alpha``, ``beta``, ``fixed`` and ``compact`` raise ``ValueError``.
 
-fp32, check degrees 2..16. The early stop is per codeword; ``last_iterations`` holds the int32 device tensor of the
-last decode's iteration counts.
+fp32 arithmetic, input and output, check degrees 2..16. The early stop is per codeword; ``last_iterations`` holds the
+int32 device tensor of the last decode's iteration counts.
 """
 from __future__ import annotations
+
+import torch
 
 from .engine import LayeredBPDecoder
 from .min_sum_layered_decoder_irreg import Min_Sum_Layered_Decoder_class_irregular
@@ -24,7 +27,7 @@ class BeliefPropagation_Layered_Decoder_class_irregular(Min_Sum_Layered_Decoder_
     _REFUSED = ("alpha", "beta", "fixed", "compact")
 
     def __init__(self, filename, imax_, cardinality_T_channel_, msg_at_time_, *, layers=None, Z=None,
-                 llr_max: float = 150.0, path: str = "fused", **refused):
+                 llr_max: float = 150.0, path: str = "fused", state_dtype=torch.float32, **refused):
         for name in refused:
             if name in self._REFUSED:
                 raise ValueError(f"{name} is not a parameter of the layered BP decoder (no correction, fixed-point "
@@ -32,6 +35,9 @@ class BeliefPropagation_Layered_Decoder_class_irregular(Min_Sum_Layered_Decoder_
             raise TypeError(f"__init__() got an unexpected keyword argument {name!r}")
         if path not in LayeredBPDecoder._PATHS:
             raise ValueError('path must be "fused", "passes" or "auto"')
+        if state_dtype not in LayeredBPDecoder._STATE:
+            raise ValueError("state_dtype must be torch.float32 or torch.float16")
+        self.state_dtype = state_dtype
         super().__init__(filename, imax_, cardinality_T_channel_, msg_at_time_, layers=layers, Z=Z, llr_max=llr_max,
                          path=path)
 
@@ -41,7 +47,7 @@ class BeliefPropagation_Layered_Decoder_class_irregular(Min_Sum_Layered_Decoder_
         self.context = dev
         self.msg_at_time = int(msg_at_time_)
         self._dec = LayeredBPDecoder(self._graph_on(dev), self.layers, self.imax, self.msg_at_time,
-                                     llr_max=self.llr_max, path=self.path)
+                                     llr_max=self.llr_max, path=self.path, state_dtype=self.state_dtype)
 
     def decode_OpenCL_belief_propagation(self, received_blocks, buffer_in=False, return_buffer=False):
         return self._decode(received_blocks, buffer_in, return_buffer)

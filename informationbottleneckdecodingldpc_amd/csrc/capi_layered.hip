@@ -2,7 +2,7 @@
 // the fused on-chip kernel for codes whose codeword state fits the LDS, the per-layer path over HBM otherwise, and
 // the fixed-point arithmetic on the per-layer path (ibl_layered_create_fixed) and fused on chip
 // (ibl_layered_create_fixed_fused); and the layered BP decoder (layered_bp_kernels.hip, ibl_layered_create_bp) on both
-// paths.
+// paths, with fp32 or half-precision state (layered_half_kernels.hip, ibl_layered_create_bp_half).
 #include <cmath>
 #include <cstring>
 
@@ -52,6 +52,11 @@ struct ibl_layered {
   // [E][ldb], the check messages (layered_plan.h laybp_pass_bytes)
   int32_t bp = 0;
   DevBuf<float> R;
+  // layered BP with half-precision state (ibl_layered_create_bp_half; bp = 1, half = 1): fused = 1 as the fp32 BP
+  // handle with cw_bytes = 2 N + 2 E rounded up to 4; fused = 0 uses rec, layer_slot, the masks, the counter and bits,
+  // and P16 [n_v][ldb], R16 [E][ldb] (layered_plan.h layhp_pass_bytes)
+  int32_t half = 0;
+  DevBuf<uint16_t> P16, R16;
 };
 
 namespace {
@@ -205,6 +210,47 @@ int layered_run_bp_fused(ibl_layered* h, const float* d_llr, int32_t B, float* d
   int32_t grid = 0;
   layered_geometry(h, B, &a.ngroups, &grid);
   HIPCHK(launch_laybp_fused(a, grid, (size_t)h->cw_per_group * h->cw_bytes, s));
+  HIPCHK(launch_lay_transpose(h->buf, d_out, B, g->n_v, s));
+  return IBL_OK;
+}
+
+// Layered BP, half state, per-layer path: layered_run_bp_passes' chain with the half kernels and their own pack
+int layered_run_half_passes(ibl_layered* h, const float* d_llr, int32_t B, float* d_out, int32_t early_stop,
+                            int32_t* d_iters, hipStream_t s) {
+  const ibl_graph* g = h->g;
+  LayHalfArgs a{};
+  a.P = h->P16; a.R = h->R16; a.done = h->done; a.unsat = h->unsat; a.running = h->running; a.bits = h->bits;
+  a.rec = h->rec; a.cols = g->csr_cols; a.iters = d_iters; a.llr_max = h->llr_max;
+  a.n_v = g->n_v; a.n_c = g->n_c; a.B = B; a.ntiles = pass_tiles(B); a.ntiles2 = half_tiles(B);
+  h->last_B = B;
+  h->last_compact = 0;
+  HIPCHK(launch_layhp_stage_in(a, d_llr, h->imax, s));
+  const int32_t n_layers = (int32_t)h->layer_slot.size() - 1;
+  for (int32_t it = 1; it <= h->imax; ++it) {
+    for (int32_t l = 0; l < n_layers; ++l) {
+      const int32_t s0 = h->layer_slot[l], n = h->layer_slot[l + 1] - s0;
+      HIPCHK(launch_layhp_layer(a, it == 1, s0, n, s));
+    }
+    if (early_stop && it < h->imax) HIPCHK(launch_layhp_stop(a, it, s));
+  }
+  HIPCHK(launch_layhp_stage_out(a, d_out, s));
+  return IBL_OK;
+}
+
+// transpose, the fused kernel (which converts as it stages a row in and out), transpose
+int layered_run_half_fused(ibl_layered* h, const float* d_llr, int32_t B, float* d_out, int32_t early_stop,
+                           int32_t* d_iters, hipStream_t s) {
+  const ibl_graph* g = h->g;
+  HIPCHK(launch_lay_transpose(d_llr, h->buf, g->n_v, B, s));
+  LayeredArgs a{};
+  a.buf = h->buf; a.task = h->task; a.idx = h->idx; a.iters = d_iters;
+  a.alpha = 1.f; a.beta = 0.f; a.llr_max = h->llr_max;
+  a.n_v = g->n_v; a.n_c = g->n_c; a.n_tasks = h->n_tasks; a.B = B; a.imax = h->imax;
+  a.early = early_stop ? 1 : 0;
+  a.cw_per_group = h->cw_per_group; a.cw_bytes = (int32_t)h->cw_bytes;
+  int32_t grid = 0;
+  layered_geometry(h, B, &a.ngroups, &grid);
+  HIPCHK(launch_layhp_fused(a, grid, (size_t)h->cw_per_group * h->cw_bytes, s));
   HIPCHK(launch_lay_transpose(h->buf, d_out, B, g->n_v, s));
   return IBL_OK;
 }
@@ -468,6 +514,84 @@ int ibl_layered_create_bp(const ibl_graph* g, int32_t n_layers, const int32_t* l
   return IBL_OK;
 }
 
+int ibl_layered_create_bp_half(const ibl_graph* g, int32_t n_layers, const int32_t* layer_ptr,
+                               const int32_t* layer_checks, int32_t imax, float llr_max, int32_t max_batch,
+                               int32_t path, ibl_layered** out) {
+  if (!out) return fail(IBL_EINVAL, "out is NULL");
+  *out = nullptr;
+  if (!g) return fail(IBL_EINVAL, "graph is NULL");
+  if (imax < 1 || max_batch < 1) return fail(IBL_EINVAL, "imax and max_batch must be >= 1");
+  if (!(llr_max > 0.f) || std::isinf(llr_max)) return fail(IBL_EINVAL, "llr_max must be finite and > 0");
+  if (int rc = check_path(path)) return rc;
+  const std::vector<int32_t> ip = graph_indptr(g);
+  int rc = ibl_layers_validate(g->n_v, g->n_c, ip.data(), g->h_cols.data(), n_layers, layer_ptr, layer_checks);
+  if (rc) return rc;
+  const int32_t bad = laybp_unsupported_check(g->n_c, ip.data());
+  if (bad >= 0)
+    return fail(IBL_EUNSUPPORTED, "check " + std::to_string(bad) + " has degree " +
+                                      std::to_string(ip[(size_t)bad + 1] - ip[bad]) +
+                                      ": layered BP supports check degrees 2..16");
+  const int64_t n_e = ip[(size_t)g->n_c];
+  const int32_t cw = layhp_cw_per_group(g->n_v, n_e);
+  HIPCHK(hipSetDevice(g->device));
+  if (path == IBL_PATH_PASSES || (path == IBL_PATH_AUTO && cw < 1)) {
+    LayeredPassPlan pl;
+    plan_layered_passes(g->n_c, ip.data(), n_layers, layer_ptr, layer_checks, &pl);
+    if (half_grid(pl.max_layer, max_batch) > 0x7fffffffll ||
+        pass_grid(pass_pack_runs(std::max(g->n_v, g->n_c)), max_batch) > 0x7fffffffll ||
+        ((int64_t)g->n_v * half_tiles(max_batch) + kLayPassWaves - 1) / kLayPassWaves > 0x7fffffffll)
+      return fail(IBL_EINVAL, "max_batch is too large for the per-layer kernels' grids");
+    size_t priv = 0, priv_shared = 0;
+    HIPCHK(layhp_pass_private_bytes(&priv));
+    HIPCHK(lay_pass_private_bytes(&priv_shared));   // the shared syndrome and finalise kernels
+    if ((rc = refuse_private(std::max(priv, priv_shared), "a per-layer half-state layered BP kernel has a ",
+                             "-byte private segment (register spill): rebuild required")))
+      return rc;
+    std::unique_ptr<ibl_layered> h(new ibl_layered());
+    h->g = g; h->imax = imax; h->max_batch = max_batch; h->llr_max = llr_max;
+    h->fused = 0; h->bp = 1; h->half = 1;
+    h->layer_slot = pl.layer_slot;
+    const LayeredBpBytes by = layhp_pass_bytes(g->n_v, n_e, max_batch);
+    if ((rc = h->rec.upload(pl.rec)) || (rc = h->P16.alloc(by.P / 2)) || (rc = h->R16.alloc(by.R / 2)) ||
+        (rc = h->done.alloc(by.mask / 8)) || (rc = h->unsat.alloc(by.mask / 8)) || (rc = h->running.alloc(1)) ||
+        (rc = h->bits.alloc(by.bits / 8)))
+      return rc;
+    *out = h.release();
+    return IBL_OK;
+  }
+  if (cw < 1)
+    return fail(IBL_EUNSUPPORTED, "code does not fit the half-state layered BP kernel: one codeword needs 2 N + 2 E = " +
+                                      std::to_string(layhp_cw_bytes(g->n_v, n_e)) + " bytes of LDS, a workgroup has " +
+                                      std::to_string(kLayLds));
+  LayeredBpPlan pl;
+  plan_layered_bp_half(g->n_v, g->n_c, ip.data(), g->h_cols.data(), n_layers, layer_ptr, layer_checks, &pl);
+  std::unique_ptr<ibl_layered> h(new ibl_layered());
+  h->g = g; h->imax = imax; h->max_batch = max_batch; h->llr_max = llr_max;
+  h->fused = 1; h->bp = 1; h->half = 1;
+  h->n_tasks = pl.n_tasks; h->cw_per_group = pl.cw_per_group; h->cw_bytes = pl.cw_bytes;
+  if ((rc = h->task.upload(pl.task)) || (rc = h->idx.upload(pl.idx)) ||
+      (rc = h->buf.alloc((size_t)max_batch * (size_t)g->n_v)))
+    return rc;
+  int bpc = 0;
+  size_t priv = 0;
+  const hipError_t e = layhp_fused_occupancy(h->cw_per_group, (size_t)h->cw_per_group * h->cw_bytes, &bpc, &priv);
+  if (e != hipSuccess)
+    return fail(IBL_EHIP, std::string("half-state layered BP kernel occupancy: ") + hipGetErrorString(e));
+  if (bpc < 1) return fail(IBL_EHIP, "no occupancy for the half-state layered BP kernel");
+  if ((rc = refuse_private(priv, "the half-state layered BP kernel has a ",
+                           "-byte private segment (register spill): rebuild required")))
+    return rc;
+  h->bpc = bpc;
+  *out = h.release();
+  return IBL_OK;
+}
+
+int ibl_layered_is_half(const ibl_layered* h, int32_t* half) {
+  if (!h || !half) return fail(IBL_EINVAL, "NULL argument");
+  *half = h->half;
+  return IBL_OK;
+}
+
 int ibl_layered_is_bp(const ibl_layered* h, int32_t* bp) {
   if (!h || !bp) return fail(IBL_EINVAL, "NULL argument");
   *bp = h->bp;
@@ -572,6 +696,9 @@ int ibl_layered_decode(ibl_layered* h, const void* d_llr, int32_t llr_dtype, int
   const ibl_graph* g = h->g;
   hipStream_t s = (hipStream_t)stream;
   HIPCHK(hipSetDevice(g->device));
+  if (h->half)
+    return (h->fused ? layered_run_half_fused : layered_run_half_passes)(
+        h, static_cast<const float*>(d_llr), B, static_cast<float*>(d_out), early_stop, d_iters, s);
   if (h->bp)
     return (h->fused ? layered_run_bp_fused : layered_run_bp_passes)(
         h, static_cast<const float*>(d_llr), B, static_cast<float*>(d_out), early_stop, d_iters, s);

@@ -444,6 +444,38 @@ hipError_t launch_laybp_stage_in(const LayPassArgs& a, const float* llr, int ima
 hipError_t launch_laybp_layer(const LayPassArgs& a, bool first, int slot0, int n_checks, hipStream_t s);
 hipError_t laybp_pass_private_bytes(size_t* bytes);
 
+// the packed syndrome's second step and the finalise kernel alone (two launches), for a caller that packs the hard
+// decisions itself: reads done, unsat, running, bits, rec, cols, iters, n_v, n_c, B and ntiles of `a` only
+hipError_t launch_lay_syndrome_finalise(const LayPassArgs& a, int it, hipStream_t s);
+
+// Layered BP with half-precision state (layered_half_kernels.hip; include/ibldpc.h "Layered BP, half-precision
+// state"). The fused kernel takes LayeredArgs as laybp_fused does (cw_bytes = 2 N + 2 E rounded up to 4). The
+// per-layer kernels: a lane owns 2 consecutive codewords, rows [row][ldb] of halves with ldb = ntiles2 * 128
+// (layered_plan.h "layered BP, half state"); masks, packed hard decisions, `running`, `rec` and `cols` are those of
+// LayPassArgs, per 64 codewords.
+struct LayHalfArgs {
+  uint16_t* P;              // [n_v][ldb] APP LLRs, binary16
+  uint16_t* R;              // [E][ldb] check messages, binary16, a row per CSR edge
+  uint64_t* done;           // [2 ntiles2] as LayPassArgs::done; the words past ntiles are all ones
+  uint64_t* unsat;          // [2 ntiles2]
+  int32_t* running;
+  uint64_t* bits;           // [ntiles][n_v]
+  const int32_t* rec;
+  const int32_t* cols;
+  int32_t* iters;           // [B] or nullptr
+  float llr_max;
+  int32_t n_v, n_c, B, ntiles, ntiles2;   // tiles of 64 (masks, bits) and of 128 (rows) codewords of B
+};
+hipError_t layhp_fused_occupancy(int cw_per_group, size_t lds, int* blocks_per_cu, size_t* private_bytes);
+hipError_t launch_layhp_fused(const LayeredArgs& a, int grid, size_t lds, hipStream_t s);
+hipError_t launch_layhp_stage_in(const LayHalfArgs& a, const float* llr, int imax, hipStream_t s);
+// first: the first iteration's form, which takes R = 0 without reading it
+hipError_t launch_layhp_layer(const LayHalfArgs& a, bool first, int slot0, int n_checks, hipStream_t s);
+// pack the hard decisions of the half rows (by value), XOR the packed words per check, finish the satisfied codewords
+hipError_t launch_layhp_stop(const LayHalfArgs& a, int it, hipStream_t s);
+hipError_t launch_layhp_stage_out(const LayHalfArgs& a, float* out, hipStream_t s);
+hipError_t layhp_pass_private_bytes(size_t* bytes);
+
 // Fixed-point per-layer path (include/ibldpc.h "Layered min-sum, fixed point"): a lane owns 4 consecutive
 // codewords, rows [row][ldb] with ldb = ntiles4 * 256 (layered_plan.h "fixed point"). The masks, the packed hard
 // decisions, `running`, `rec` and `cols` are those of LayPassArgs, per 64 codewords, so the packed syndrome and the

@@ -5,8 +5,8 @@
 // The schedule, the task walk, the per-codeword stop, the masks and the staging are those of the layered min-sum
 // decoder (layered_kernels.hip), whose transpose, pack, syndrome, finalise and stage-out kernels this decoder
 // launches as they stand. What differs is the check update — the forward-backward box-plus of the flooding fp32 BP
-// check node (boxplus.h) — and the state: BP has no compressed form of a check's outgoing messages, so R is kept
-// whole, one fp32 word per edge and codeword.
+// check node (boxplus.h), stated once in layered_bp_core.h for this file and layered_half_kernels.hip — and the state:
+// BP has no compressed form of a check's outgoing messages, so R is kept whole, one fp32 word per edge and codeword.
 //
 // Arithmetic: Q = P - R and P = Q + R' are one rounded fp32 operation each, Q is NOT clamped (the specification says
 // why). The file is built with -ffp-contract=off like layered_kernels.hip; the box-plus states its one fused
@@ -14,51 +14,11 @@
 #include "common.h"
 #include "boxplus.h"
 #include "layered_plan.h"
+#include "layered_bp_core.h"
 
 namespace ibl {
 
 namespace {
-
-#define LAYBP_CASES                                                                                            \
-  LAY_CASE(2) LAY_CASE(3) LAY_CASE(4) LAY_CASE(5) LAY_CASE(6) LAY_CASE(7) LAY_CASE(8) LAY_CASE(9) LAY_CASE(10) \
-  LAY_CASE(11) LAY_CASE(12) LAY_CASE(13) LAY_CASE(14) LAY_CASE(15) LAY_CASE(16)
-
-// The BP check update of one check of degree D, the one statement of it for both kernels: load_p(k) is P of edge k,
-// load_r(k) its R of the previous iteration, store_p / store_r(k, x) write the new ones back; all four are called
-// inside the unrolled loops, so a caller's memory accesses sit where the arithmetic uses them. S_j and F are box-plus
-// results and so lie inside the clamp; only the degree-2 messages, which are copies of Q, need a clamp of their own.
-// 3 (D - 2) box-pluses.
-template <int D, class LoadP, class LoadR, class StoreP, class StoreR>
-__device__ __forceinline__ void lay_bp(LoadP load_p, LoadR load_r, StoreP store_p, StoreR store_r, float L) {
-  static_assert(D >= kLayMinD && D <= kLayBpMaxD, "degree body out of range");
-  float q[D];
-#pragma unroll
-  for (int k = 0; k < D; ++k) q[k] = load_p(k) - load_r(k);
-  if constexpr (D == 2) {
-    const float r0 = __builtin_amdgcn_fmed3f(q[1], -L, L), r1 = __builtin_amdgcn_fmed3f(q[0], -L, L);
-    store_r(0, r0);
-    store_p(0, q[0] + r0);
-    store_r(1, r1);
-    store_p(1, q[1] + r1);
-  } else {
-    float S[D];   // S[j] = Q_j [+] ... [+] Q_{D-1}, j >= 1
-    S[D - 1] = q[D - 1];
-#pragma unroll
-    for (int j = D - 2; j >= 1; --j) S[j] = boxplus(q[j], S[j + 1], L);
-    store_r(0, S[1]);
-    store_p(0, q[0] + S[1]);
-    float F = q[0];   // Q_0 [+] ... [+] Q_{w-1}
-#pragma unroll
-    for (int w = 1; w <= D - 2; ++w) {
-      const float r = boxplus(F, S[w + 1], L);
-      store_r(w, r);
-      store_p(w, q[w] + r);
-      F = boxplus(q[w], F, L);
-    }
-    store_r(D - 1, F);
-    store_p(D - 1, q[D - 1] + F);
-  }
-}
 
 // One task of checks of degree D of the fused kernel: the lane's check reads its variable indices at idx + 64 k and
 // keeps its messages at R + cnt k (idx, R: the task's, already advanced by the lane).

@@ -819,6 +819,18 @@ hipError_t launch_lay_syndrome(const LayPassArgs& a, int packed, hipStream_t s) 
   return lay_pass_launch((const void*)lay_syndrome_packed, pass_items(pass_pack_runs(a.n_c), a.B), p, s);
 }
 
+hipError_t launch_lay_syndrome_finalise(const LayPassArgs& a, int it, hipStream_t s) {
+  if (!a.done || !a.unsat || !a.running || !a.bits || !a.rec || !a.cols || a.n_v < 1 || a.n_c < 1 || a.B < 1 ||
+      a.ntiles != pass_tiles(a.B))
+    return hipErrorInvalidValue;
+  LayPassArgs args = a;
+  void* ps[] = {&args};
+  const hipError_t e = lay_pass_launch((const void*)lay_syndrome_packed, pass_items(pass_pack_runs(a.n_c), a.B), ps, s);
+  if (e != hipSuccess) return e;
+  void* pf[] = {&args, (void*)&it};
+  return lay_pass_launch((const void*)lay_finalise, a.ntiles, pf, s);
+}
+
 hipError_t launch_lay_finalise(const LayPassArgs& a, int it, hipStream_t s) {
   if (!lay_pass_args_ok(a)) return hipErrorInvalidValue;
   LayPassArgs args = a;

@@ -6,8 +6,9 @@
 // tests/asan/layered_fixed_plan_check.cpp (tests/test_cpu_layered_fixed.py),
 // tests/asan/layered_compact_plan_check.cpp (tests/test_cpu_layered_compact.py),
 // tests/asan/layered_wide_plan_check.cpp (tests/test_cpu_layered_wide.py),
-// tests/asan/layered_fixed_fused_plan_check.cpp (tests/test_cpu_layered_fixed_fused.py) and
-// tests/asan/layered_bp_plan_check.cpp (tests/test_cpu_layered_bp.py).
+// tests/asan/layered_fixed_fused_plan_check.cpp (tests/test_cpu_layered_fixed_fused.py),
+// tests/asan/layered_bp_plan_check.cpp (tests/test_cpu_layered_bp.py) and
+// tests/asan/layered_half_plan_check.cpp (tests/test_cpu_layered_half.py).
 //
 // A layer is a set of checks no two of which share a variable; the layers are disjoint, cover every check and
 // are decoded in order (include/ibldpc.h "Layered min-sum"). The device plan cuts every layer into tasks of up
@@ -288,6 +289,57 @@ inline LayeredBpBytes laybp_pass_bytes(int32_t n_v, int64_t n_e, int32_t max_bat
   b.P = (size_t)4 * (size_t)n_v * ldb;
   b.R = (size_t)4 * (size_t)n_e * ldb;
   b.mask = (size_t)8 * (size_t)pass_tiles(max_batch);
+  b.counter = 4;
+  b.bits = (size_t)8 * (size_t)n_v * (size_t)pass_tiles(max_batch);
+  b.total = b.P + b.R + 2 * b.mask + b.counter + b.bits;
+  return b;
+}
+
+// ---- layered BP, half state (include/ibldpc.h "Layered BP, half-precision state"; layered_half_kernels.hip; checked
+// by tests/asan/layered_half_plan_check.cpp) --------------------------------------------------------------------------
+// P and R are IEEE binary16. Fused: the wave's LDS slice is P16[N] | R16[E], rounded up to whole dwords so that the
+// next wave's slice is aligned; the tasks and variable indices are plan_layered_bp's. Per layer: a lane owns 2
+// consecutive codewords (one dword of a row), P16 [n_v][ldb] and R16 [E][ldb] with ldb a multiple of kLayHalfTile; a
+// wave item is (check of the layer, tile of kLayHalfTile codewords). The plan (LayeredPassPlan), the masks of
+// finished and unsatisfied codewords and the packed hard decisions stay per kLayTile codewords, the mask arrays padded
+// to whole tiles of kLayHalfTile (the padding words all ones: finished).
+constexpr int kLayHalfCw = 2;                               // codewords per lane
+constexpr int kLayHalfTile = kLayHalfCw * kLayTile;         // codewords per wave item
+
+inline size_t layhp_cw_bytes(int32_t n_v, int64_t n_e) {
+  return ((size_t)2 * (size_t)n_v + (size_t)2 * (size_t)n_e + 3) / 4 * 4;
+}
+// Codewords a workgroup keeps on chip (one wave each): 0 = the code does not fit.
+inline int32_t layhp_cw_per_group(int32_t n_v, int64_t n_e) {
+  return (int32_t)std::min<size_t>((size_t)kLayMaxCw, (size_t)kLayLds / layhp_cw_bytes(n_v, n_e));
+}
+// The fused kernel's plan: plan_layered_bp's tasks, indices and R layout, with the half state's bytes and fit.
+// Precondition: validate_layers(...) == 0 and laybp_unsupported_check(...) < 0.
+inline void plan_layered_bp_half(int32_t n_v, int32_t n_c, const int32_t* indptr, const int32_t* cols, int32_t n_layers,
+                                 const int32_t* layer_ptr, const int32_t* layer_checks, LayeredBpPlan* pl) {
+  plan_layered_bp(n_v, n_c, indptr, cols, n_layers, layer_ptr, layer_checks, pl);
+  pl->cw_bytes = layhp_cw_bytes(n_v, pl->n_e);
+  pl->cw_per_group = layhp_cw_per_group(n_v, pl->n_e);
+}
+
+inline int32_t half_tiles(int32_t B) { return pass_tiles(B, kLayHalfTile); }
+inline int64_t half_ldb(int32_t B) { return pass_ldb(B, kLayHalfTile); }
+// words of each mask array: the kLayTile tiles of whole tiles of kLayHalfTile
+inline int64_t half_mask_words(int32_t B) { return (int64_t)half_tiles(B) * kLayHalfCw; }
+inline int64_t half_items(int32_t n_checks, int32_t B) { return pass_items(n_checks, B, kLayHalfTile); }
+inline int64_t half_grid(int32_t n_checks, int32_t B) { return pass_grid(n_checks, B, kLayHalfTile); }
+// the word `word` of the finished mask as the stage-in writes it for a batch of B: all ones past the batch
+constexpr uint64_t half_done_word(int32_t word, int32_t B) {
+  const int64_t left = (int64_t)B - (int64_t)word * kLayTile;
+  return left >= kLayTile ? 0ull : left <= 0 ? ~0ull : ~0ull << left;
+}
+// byte sizes of the device scratch a per-layer handle of max_batch owns: about 2 N + 2 E bytes per codeword
+inline LayeredBpBytes layhp_pass_bytes(int32_t n_v, int64_t n_e, int32_t max_batch) {
+  LayeredBpBytes b;
+  const size_t ldb = (size_t)half_ldb(max_batch);
+  b.P = (size_t)2 * (size_t)n_v * ldb;
+  b.R = (size_t)2 * (size_t)n_e * ldb;
+  b.mask = (size_t)8 * (size_t)half_mask_words(max_batch);
   b.counter = 4;
   b.bits = (size_t)8 * (size_t)n_v * (size_t)pass_tiles(max_batch);
   b.total = b.P + b.R + 2 * b.mask + b.counter + b.bits;

@@ -518,23 +518,33 @@ class LayeredDecoder:
 
 
 class LayeredBPDecoder:
-    """Layered (row-serial) belief-propagation decoder, fp32 (``ibl_layered_create_bp``; semantics in
+    """Layered (row-serial) belief-propagation decoder (``ibl_layered_create_bp``; semantics in
     include/ibldpc.h "Layered BP"): the schedule, layers and per-codeword early stop of :class:`LayeredDecoder`
     with the box-plus check update of the flooding fp32 BP decoder. ``path``: ``"fused"`` (default) the on-chip
     kernel, one wave per codeword with its APP values and one fp32 message per edge in LDS (4 N + 4 E bytes a
     codeword, up to 8 codewords a workgroup); ``"passes"`` per-layer kernels over HBM for codes of any length
     (``codes.dvbs2_layers`` for DVB-S2; about 4 N + 4 E bytes per codeword of ``max_batch``: 1.17 MB for DVB-S2
     rate 1/2); ``"auto"`` the fused kernel when the codeword fits. Both paths give the same bits.
+    ``state_dtype``: ``torch.float32`` (default) or ``torch.float16``. With float16 the APP values and the messages
+    are stored as IEEE binary16 while every operation stays fp32 (``ibl_layered_create_bp_half``; include/ibldpc.h
+    "Layered BP, half-precision state"): 2 N + 2 E bytes a codeword on either path, so a code of twice the size fits
+    the fused kernel and an iteration of the per-layer kernels moves half the bytes. Input and output stay float32
+    (every output value is a binary16 value); meaningful decoding needs ``|llr| + 16 llr_max <= 65504``.
+    :attr:`half` tells which state a decoder keeps.
     Check degrees 2..16. Raises :class:`_lib.IBLError` (``IBL_EUNSUPPORTED``) for a check above degree 16 and when
     ``path="fused"`` and a codeword does not fit in LDS. There is no compaction."""
 
     _PATHS = LayeredDecoder._PATHS
+    _STATE = (torch.float32, torch.float16)
 
     def __init__(self, graph: Graph, layers, imax: int, max_batch: int, llr_max: float = 150.0, path: str = "fused",
-                 precision=torch.float32):
+                 precision=torch.float32, state_dtype=torch.float32):
         if path not in self._PATHS:
             raise ValueError('path must be "fused", "passes" or "auto"')
+        if state_dtype not in self._STATE:
+            raise ValueError("state_dtype must be torch.float32 or torch.float16")
         self.path = path
+        self.state_dtype = state_dtype
         self.graph = graph
         self.imax = int(imax)
         self.max_batch = int(max_batch)
@@ -547,10 +557,24 @@ class LayeredBPDecoder:
             chk = np.zeros(1, np.int32)
         self.n_layers = nl
         h = ctypes.c_void_p()
-        _lib.check(_lib.load().ibl_layered_create_bp(graph.handle, nl, ptr, chk, self.imax, self.llr_max,
-                                                     _DT_FL[precision], self.max_batch, self._PATHS[path],
-                                                     ctypes.byref(h)), "ibl_layered_create_bp")
+        if state_dtype == torch.float16:
+            if precision != torch.float32:
+                raise ValueError("state_dtype=torch.float16 computes in float32: precision must be torch.float32")
+            _lib.check(_lib.load().ibl_layered_create_bp_half(graph.handle, nl, ptr, chk, self.imax, self.llr_max,
+                                                              self.max_batch, self._PATHS[path], ctypes.byref(h)),
+                       "ibl_layered_create_bp_half")
+        else:
+            _lib.check(_lib.load().ibl_layered_create_bp(graph.handle, nl, ptr, chk, self.imax, self.llr_max,
+                                                         _DT_FL[precision], self.max_batch, self._PATHS[path],
+                                                         ctypes.byref(h)), "ibl_layered_create_bp")
         self._h = h
+
+    @property
+    def half(self) -> bool:
+        """Whether the decoder keeps its state in binary16 (``ibl_layered_is_half``)."""
+        w = ctypes.c_int32()
+        _lib.check(_lib.load().ibl_layered_is_half(self._h, ctypes.byref(w)), "ibl_layered_is_half")
+        return bool(w.value)
 
     path_in_use = LayeredDecoder.path_in_use
     geometry = LayeredDecoder.geometry
